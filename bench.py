@@ -36,10 +36,19 @@ rank processes itself, one per GPU, before anything touches the GPU) or
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``.
 ``--device cpu`` rehearses the same multi-rank path on the CPU (gloo, the
 fp64 reference scorer), which is how the CPU test-suite covers it.
+
+A plain run sets up, warms up, times the --steps steps and prints the result
+line.  ``--full`` adds what is measured in runs of its own after the timed
+steps: the p50 decision latency on unpipelined steps (``null`` in the result
+line of a plain run).  ``--dump-outputs DIR`` writes what the last timed step
+computed (rank 0: the fleet verdict in host memory and the per-row results of
+its shard) as ``DIR/<name>.npy``; the fleet is seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import json
 import os
 import socket
@@ -104,6 +113,22 @@ def extra_warmup_steps(warm_ms: float, per_step_ms: float, min_ms: float, cap: i
     return min(cap, int((min_ms - warm_ms) / max(per_step_ms, 1e-3)) + 1)
 
 
+def dump_outputs(dirname: str, verdict, o, n_cur: int) -> None:
+    """``--dump-outputs``: the fleet verdict ([S, 4] fp32, as the control plane
+    reads it from host memory) and the per-row results behind it (``o``, a
+    CanaryOutputs) as ``<name>.npy``, float32 (80k rows: ~25 MB in all)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    d = o.decide
+    bits = torch.arange(64, dtype=torch.int64, device=d.flags.device)
+    flags = ((d.flags.unsqueeze(-1) >> bits) & 1).reshape(d.flags.shape[0], -1)[:, :n_cur]
+    arrays = {"verdict": verdict, "pvals": o.pvals, "pstats": o.pstats, "diff": o.diff, "stats": d.stats,
+              "flags": flags, "count": d.count, "score": d.score, "valid": d.valid}
+    for name, a in arrays.items():
+        a = a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def _device_census(info, dev) -> tuple[int, str]:
     """(distinct devices across ranks, backend).  Ranks sharing one GPU
     (FOREMAST_DEVICE_INDEX rehearsal over gloo) count once."""
@@ -165,6 +190,12 @@ def main() -> None:
     ap.add_argument("--warmup-min-ms", type=float, default=300.0,
                     help="after the --warmup steps, keep stepping (untimed) until this much warm-up wall time has "
                          "passed, so the timed steps start at steady-state clocks (all ranks run the same count)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the p50 decision latency on unpipelined steps "
+                         "(a plain run only sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (rank 0: "
+                         "the fleet verdict and the per-row results of its shard, float32)")
     args = ap.parse_args()
 
     if args.gpus is not None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -220,6 +251,7 @@ def main() -> None:
     compute = torch.cuda.current_stream(dev)
     comm = torch.cuda.Stream(dev)
     decides = [None] * depth
+    outs = [None] * depth                        # CanaryOutputs per slot (--dump-outputs)
     if split:
         # tick = front kernel on the compute stream; its decision runs in
         # publish() on the comm stream, so tick k's decision + all-gather +
@@ -231,10 +263,11 @@ def main() -> None:
                 ticks.append(rep)
                 decides[i] = (lambda o=o: scorer.decide_only(cur, o))
             else:
-                f, d, _ = scorer.split_launchers(hist, base, cur, args.hist, packed_out=packed[i], slot=i,
+                f, d, o = scorer.split_launchers(hist, base, cur, args.hist, packed_out=packed[i], slot=i,
                                                  front_stream=compute, decide_stream=comm)
                 ticks.append(f)
                 decides[i] = d
+            outs[i] = o
     elif args.no_graph:
         ticks = [lambda p=p: scorer.score(hist, base, cur, args.hist, packed_out=p) for p in packed]
     else:
@@ -364,27 +397,37 @@ def main() -> None:
     D.barrier()
     elapsed = D.all_reduce_max(t1 - t0, dev)
 
-    # decision latency, measured after the throughput run on unpipelined
-    # steps: GPU time from the start of a tick to the fleet verdict in rank
-    # 0's host memory (timing events stay out of the timed loop)
-    t_a, t_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    lat: list[float] = []
-    for _ in range(max(5, min(args.steps, 50))):
-        slot = gstep[0] % depth
-        t_a.record(compute)
-        ticks[slot]()
-        ev_tick[slot].record(compute)
-        publish(slot, t_b)
-        t_b.synchronize()
-        gstep[0] += 1
-        lat.append(t_a.elapsed_time(t_b))
-    p50 = D.all_reduce_max(statistics.median(lat) / 1e3, dev)
+    last = (gstep[0] - 1) % depth
+    if args.dump_outputs and info.is_main:
+        # the last timed step: its verdict in host memory, its slot's per-row
+        # buffers (unsplit ticks share the scorer's one buffer set)
+        o_last = outs[last] if outs[last] is not None else \
+            dataclasses.replace(scorer._alloc(cur.shape[0], cur.shape[1]), packed=packed[last])
+        dump_outputs(args.dump_outputs, hosts[last][:S].numpy(), o_last, cur.shape[1])
+
+    p50 = None
+    if args.full:
+        # decision latency, measured after the throughput run on unpipelined
+        # steps: GPU time from the start of a tick to the fleet verdict in rank
+        # 0's host memory (timing events stay out of the timed loop)
+        t_a, t_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        lat: list[float] = []
+        for _ in range(max(5, min(args.steps, 50))):
+            slot = gstep[0] % depth
+            t_a.record(compute)
+            ticks[slot]()
+            ev_tick[slot].record(compute)
+            publish(slot, t_b)
+            t_b.synchronize()
+            gstep[0] += 1
+            lat.append(t_a.elapsed_time(t_b))
+        p50 = D.all_reduce_max(statistics.median(lat) / 1e3, dev)
     if peer is not None:
         peer.check()
     n_dev, backend = _device_census(info, dev)
     ms = elapsed / args.steps * 1e3
     windows = S * M
-    verdict = hosts[(gstep[0] - 1) % depth][:S].numpy() if info.is_main else None
+    verdict = hosts[last][:S].numpy() if info.is_main else None
     if info.is_main:
         n_anom = int((verdict[:, 0] == 1).sum())
         out = {
@@ -399,7 +442,7 @@ def main() -> None:
             "warmup_extra_steps": extra,
             "warmup_ms": round(w_ms, 1),
             "ms_per_step": ms,
-            "p50_decision_latency_ms": p50 * 1e3,
+            "p50_decision_latency_ms": None if p50 is None else p50 * 1e3,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -460,8 +503,10 @@ def run_cpu(args, info) -> None:
     gathered = torch.empty((world * s_pad, 4), dtype=torch.float32)
     lat: list[float] = []
 
+    last_o = [None]
+
     def step() -> torch.Tensor:
-        o = scorer.score(hist, base, cur, args.hist)
+        o = last_o[0] = scorer.score(hist, base, cur, args.hist)
         return D.all_gather_rows(o.packed.contiguous(), gathered)
 
     for _ in range(args.warmup):
@@ -480,6 +525,8 @@ def run_cpu(args, info) -> None:
     ms = elapsed / args.steps * 1e3
     if info.is_main:
         verdict = g[:S].numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, verdict, last_o[0], cur.shape[1])
         print(json.dumps({
             "metric": "metric windows scored/sec (node) + p50 decision latency, 10k-service canary [CPU rehearsal]",
             "value": S * M / (ms / 1e3), "unit": "windows/s", "n_gpus": 0, "n_ranks": world, "backend": backend,

@@ -34,6 +34,41 @@ def test_bench_json_contract(extra):
     assert abs(out["value"] - 300 * 8 / (out["ms_per_step"] / 1e3)) / out["value"] < 1e-6
     # the fault injection of the synthetic fleet is visible in the verdicts
     assert 0 < out["services_flagged"] < 300
+    # a plain run times its steps and nothing else: the latency is --full's
+    assert out["p50_decision_latency_ms"] is None
+
+
+DUMPED = {"verdict": (4,), "pvals": (6,), "pstats": (6,), "diff": (), "stats": (4,), "flags": (50,), "count": (),
+          "score": (), "valid": ()}
+
+
+def _check_dump(d, out, services):
+    """The dumped arrays of a run: float32, one row per service (verdict) or
+    per service x metric, and the verdict is the one the result line counts."""
+    import numpy as np
+    assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in DUMPED)
+    arrays = {n: np.load(os.path.join(d, n + ".npy")) for n in DUMPED}
+    for n, a in arrays.items():
+        rows = services if n == "verdict" else services * 8
+        assert a.dtype == np.float32 and a.shape == (rows, *DUMPED[n]), (n, a.dtype, a.shape)
+    assert int((arrays["verdict"][:, 0] == 1).sum()) == out["services_flagged"]
+    assert np.array_equal(arrays["flags"].sum(axis=1), arrays["count"])
+    return arrays
+
+
+@pytest.mark.gpu
+def test_bench_full_measures_latency_and_dumps_last_step(tmp_path):
+    """``--full`` adds the p50 decision latency to the same result line;
+    ``--dump-outputs`` writes the last timed step's verdict and per-row
+    results, which an odd step count leaves in the second slot's buffers."""
+    out = _bench("--services", "300", "--steps", "3", "--warmup", "2", "--full", "--dump-outputs", str(tmp_path))
+    assert REQUIRED <= set(out) and out["steps"] == 3
+    assert out["p50_decision_latency_ms"] > 0
+    a = _check_dump(str(tmp_path), out, 300)
+    # the verdict rows follow from the per-row results dumped next to them:
+    # a service is flagged when any of its metric rows has anomalous points
+    import numpy as np
+    assert np.array_equal(a["verdict"][:, 0] == 1, (a["count"].reshape(300, 8) > 0).any(axis=1))
 
 
 @pytest.mark.gpu
@@ -66,6 +101,23 @@ def test_bench_self_launches_ranks_on_cpu():
     assert o1["n_ranks"] == 1 and o1["backend"] == "none"
     # the sharded fleet verdict gathered on rank 0 equals the single-rank one
     assert o1["services_flagged"] == o2["services_flagged"] > 0
+
+
+def test_bench_dump_outputs_repeats_on_cpu(tmp_path):
+    """``--dump-outputs`` on the CPU rehearsal: the same arrays as on the GPU,
+    and the same arguments give the same arrays (the fleet is seeded), so two
+    builds can be compared output for output."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        d = str(tmp_path / name)
+        r = _bench_cpu("--dump-outputs", d)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        runs.append(_check_dump(d, out, 64))
+    for n in DUMPED:
+        assert np.array_equal(runs[0][n], runs[1][n], equal_nan=True), n
 
 
 def test_bench_rejects_gpus_world_mismatch():
