@@ -64,6 +64,9 @@ class BrainConfig:
     min_wilcoxon: int = 20                   # MIN_WILCOXON_DATA_POINTS
     min_kruskal: int = 5                     # MIN_KRUSKAL_DATA_POINTS
     pairwise_threshold_factor: float = 0.8   # [inferred] "lower threshold" factor (design.md:35)
+    # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
+    # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
+    multivariate_threshold: float | None = None
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -130,6 +133,9 @@ class BrainConfig:
                 return r
         return MetricRule(self.threshold, self.bound, self.min_lower_bound)
 
+    def mvn_threshold(self) -> float:
+        return self.threshold if self.multivariate_threshold is None else self.multivariate_threshold
+
     def algorithm_for(self, alias: str) -> str:
         """Model of a metric: its metric type's ``ml_algorithmN`` override, else
         the global ``ML_ALGORITHM``.  The brain groups the rows of a cycle by
@@ -162,6 +168,8 @@ class BrainConfig:
         c.min_wilcoxon = _i(env, "MIN_WILCOXON_DATA_POINTS", c.min_wilcoxon)
         c.min_kruskal = _i(env, "MIN_KRUSKAL_DATA_POINTS", c.min_kruskal)
         c.pairwise_threshold_factor = _f(env, "ML_PAIRWISE_THRESHOLD_FACTOR", c.pairwise_threshold_factor)
+        if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
+            c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

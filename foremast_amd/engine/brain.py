@@ -272,7 +272,9 @@ class Brain(BrainStateMixin):
             pairs = self._pairs(rows) if algo == "bivariate_normal" else None
             dec = zoo.decide(algo, hist, T, cur, hor, R, tables, diff,
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
-                             pairs=pairs, cache=self._cache_ctx(rows, algo))
+                             pairs=pairs, cache=self._cache_ctx(rows, algo),
+                             groups=self._groups(rows) if algo == "multivariate_normal" else None,
+                             mvn_threshold=self.cfg.mvn_threshold())
             out = {k: getattr(dec, k).detach().cpu().numpy() for k in keys}
             flags = dec.flags
         else:
@@ -286,7 +288,9 @@ class Brain(BrainStateMixin):
                                  zoo.make_tables([r.alias for r in sub], self.cfg, self.device),
                                  None if diff is None else diff.index_select(0, it),
                                  lstm_model=self._lstm_for(sub) if algo == "lstm" else self.lstm_model,
-                                 pairs=pairs, cache=self._cache_ctx(sub, algo))
+                                 pairs=pairs, cache=self._cache_ctx(sub, algo),
+                                 groups=self._groups(sub) if algo == "multivariate_normal" else None,
+                                 mvn_threshold=self.cfg.mvn_threshold())
                 for k in keys:
                     v = getattr(dec, k).detach()
                     if k not in out:
@@ -355,6 +359,14 @@ class Brain(BrainStateMixin):
                 singles.append(idx[-1])
         f = lambda v: torch.tensor(v, dtype=torch.int64)
         return f(ia), f(ib), f(singles)
+
+    @staticmethod
+    def _groups(rows: list[Row]):
+        """Joint-detector groups: the rows of each job, in chunks of 8."""
+        by_job: dict[int, list[int]] = {}
+        for i, r in enumerate(rows):
+            by_job.setdefault(r.job, []).append(i)
+        return zoo.mvn_groups(by_job.values())
 
     # ------------------------------------------------------------------ cycle
     def run_once(self) -> dict:

@@ -17,6 +17,7 @@ holt_winters_multiplicative     multiplicative HW (seasonal ratio)      K3 + K2 
 prophet                         trend+hinges+daily/weekly Fourier LSQ   K10 (f32 MFMA)
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
+multivariate_normal             joint Mahalanobis over all metrics      K12
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -25,6 +26,8 @@ advanced over their new samples instead of re-fitting the grid.
 
 Thresholds are in sigma units per metric (``BrainConfig.rule_for``), lowered
 by ``pairwise_threshold_factor`` on rows whose canary distribution differs.
+``multivariate_normal`` takes one joint threshold (``mvn_threshold``), turned
+into a cut on the Mahalanobis distance per number of live members.
 """
 from __future__ import annotations
 
@@ -39,7 +42,7 @@ from ..ops import lsq as LQ
 from ..ops import smoothing as SM
 
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
-              "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal")
+              "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -47,7 +50,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "double_exponential_smoothing": "double_exponential_smoothing", "holt": "double_exponential_smoothing",
            "holt_winters": "holt_winters", "hw": "holt_winters", "triple_exponential_smoothing": "holt_winters",
            "holt_winters_multiplicative": "holt_winters_multiplicative", "hw_mul": "holt_winters_multiplicative",
-           "prophet": "prophet", "lstm": "lstm", "bivariate_normal": "bivariate_normal", "bivariate": "bivariate_normal"}
+           "prophet": "prophet", "lstm": "lstm", "bivariate_normal": "bivariate_normal", "bivariate": "bivariate_normal",
+           "multivariate_normal": "multivariate_normal", "multivariate": "multivariate_normal",
+           "mvn": "multivariate_normal"}
 
 
 def canonical(name: str) -> str:
@@ -110,7 +115,8 @@ def _valid(hist: torch.Tensor, T: int, cur: torch.Tensor, min_hist: int) -> torc
 
 def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizon: torch.Tensor, M: int,
            tables: Tables, diff: torch.Tensor | None = None, window: int = 60, period: int | None = None,
-           lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None) -> RowDecision:
+           lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
+           groups=None, mvn_threshold: float | None = None) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -131,6 +137,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         return _expand_stats(dec, n)
     if algo == "bivariate_normal":
         return _bivariate(hist, T, cur, M, tables, pairs)
+    if algo == "multivariate_normal":
+        return _multivariate(hist, T, cur, M, tables, diff, groups, mvn_threshold)
     if H is None:
         H = int(horizon.max().item()) if horizon.numel() else 1
     H = max(int(H), 1)
@@ -274,6 +282,90 @@ def _bivariate(hist, T, cur, M, tables, pairs=None) -> RowDecision:
         up_all[singles] = sub.stats[:, 2:3].expand(-1, n)
         lo_all[singles] = sub.stats[:, 3:4].expand(-1, n)
     valid = _valid(hist, T, cur, tables.min_hist)
+    return RowDecision(up_all, lo_all, flags_all, count_all, score_all, valid)
+
+
+MVN_MAX_K = 8
+
+
+def mvn_groups(jobs) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Row groups of the joint detector; ``jobs`` holds each job's row indices.
+    A job's rows are cut into chunks of 8 in row order; a leftover of one row
+    (and a job with one metric) is a single.  Returns (rows [G, 8] int32, -1
+    padded; K [G] int64; singles int64)."""
+    rows, ks, singles = [], [], []
+    for idx in jobs:
+        for c0 in range(0, len(idx), MVN_MAX_K):
+            part = list(idx[c0:c0 + MVN_MAX_K])
+            if len(part) == 1:
+                singles.append(part[0])
+            else:
+                rows.append(part + [-1] * (MVN_MAX_K - len(part)))
+                ks.append(len(part))
+    return (torch.tensor(rows, dtype=torch.int32).reshape(-1, MVN_MAX_K), torch.tensor(ks, dtype=torch.int64),
+            torch.tensor(singles, dtype=torch.int64))
+
+
+def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None) -> RowDecision:
+    """All metrics of a job scored jointly (K12): every member row of a group
+    gets the group's decision, bounds in Mahalanobis units (upper = the cut
+    the group used, lower = 0).  ``groups`` = (rows [G, 8] int32, K [G],
+    singles) as :func:`mvn_groups` makes them; default: each service's M
+    consecutive rows.  Singles go through ``moving_average_all``.  ``thr`` is
+    the joint threshold in sigma units (default: the largest of the table);
+    a group is judged at ``thr * pair_factor`` when any member's canary
+    distribution differs."""
+    from ..ops import misc as MI
+    R, n = cur.shape
+    device = hist.device
+    if groups is None:
+        groups = mvn_groups([range(s * M, (s + 1) * M) for s in range(R // M)])
+    grows, gk, singles = (g.to(device) for g in groups)
+    NW = max(1, (n + 63) // 64)
+    flags_all = torch.zeros((R, NW), dtype=torch.int64, device=device)
+    count_all = torch.zeros((R,), dtype=torch.int32, device=device)
+    score_all = torch.zeros((R,), dtype=torch.float32, device=device)
+    up_all = torch.full((R, n), float("nan"), device=device)
+    lo_all = torch.full((R, n), float("nan"), device=device)
+    valid = _valid(hist, T, cur, tables.min_hist)
+    if hist.is_cuda and (hist.stride(0) % 4 or hist.data_ptr() % 16 or hist.stride(1) != 1):
+        hist = _aligned_rows(hist, torch.arange(R, device=device), T)
+    cur = cur.contiguous()
+    if grows.shape[0]:
+        if thr is None:
+            thr = float(tables.thr[0].item()) if tables.thr.numel() == 1 else float(tables.thr.max().item())
+        cuts = MI.mvn_cuts(thr, tables.pair_factor)
+        cuts_d = torch.from_numpy(cuts).to(device)
+        member = grows >= 0
+        safe = grows.clamp(min=0).long()
+        if diff is None:
+            lowered = torch.zeros((grows.shape[0],), dtype=torch.uint8, device=device)
+        else:
+            lowered = ((diff.to(device)[safe] != 0) & member).any(1).to(torch.uint8)
+        for K in sorted(set(gk.tolist())):
+            sel = (gk == K).nonzero().squeeze(1)
+            params, dist, flags, cnt, gvalid = MI.mvn(hist, T, cur, grows[sel].contiguous(), K, cuts, lowered[sel],
+                                                      tables.min_hist)
+            sc = torch.nan_to_num(dist, nan=0.0).amax(1)
+            used = cuts_d[lowered[sel].long(), params[:, 1].long()]
+            hist_ok = (gvalid & 1).to(torch.int32)
+            for j in range(K):
+                i = safe[sel, j]
+                flags_all[i] = flags
+                count_all[i] = cnt
+                score_all[i] = sc
+                up_all[i] = used[:, None].expand(-1, n)
+                lo_all[i] = 0.0
+                valid[i] = (valid[i] & 2) | hist_ok
+    if singles.numel():
+        S1 = int(singles.numel())
+        pick = lambda t: t[singles % t.numel()].contiguous()
+        sub = C.stats_decide(_aligned_rows(hist, singles, T), cur[singles].contiguous(), T, S1, pick(tables.thr),
+                             pick(tables.bound), pick(tables.minlb), None if diff is None else diff[singles].contiguous(),
+                             tables.pair_factor, tables.min_hist)
+        flags_all[singles], count_all[singles], score_all[singles] = sub.flags, sub.count, sub.score
+        up_all[singles] = sub.stats[:, 2:3].expand(-1, n)
+        lo_all[singles] = sub.stats[:, 3:4].expand(-1, n)
     return RowDecision(up_all, lo_all, flags_all, count_all, score_all, valid)
 
 

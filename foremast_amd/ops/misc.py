@@ -1,5 +1,5 @@
-"""K5 bivariate normal, K8 HPA score, K9 downstream impact
-(csrc/kernels/bivariate.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
+"""K5 bivariate normal, K12 multivariate normal, K8 HPA score, K9 downstream impact
+(csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -61,6 +61,137 @@ def ref_bivariate(ha, hb, ca, cb, threshold):
     words = np.packbits(padded.reshape(P, NW, 64), axis=2, bitorder="little").view(np.uint64).reshape(P, NW)
     params = np.stack([ma, mb, caa, cab, cbb], 1).astype(np.float32)
     return params, dist.astype(np.float32), words.view(np.int64), flag.sum(1).astype(np.int32)
+
+
+# --------------------------------------------------------------------------- K12
+MVN_MAX_K = 8
+MVN_RIDGE = 1e-6
+# Moment form of the kernel (csrc/kernels/mvn.hip): 0 = mean sweep then centred
+# sweep, 1 = shift from the row tails then one centred sweep.  Form 1 measured
+# 0.86 ms against 1.12 ms at the fleet shape with equal results (docs/PERF.md).
+MVN_FORM = 1
+
+
+def mvn_cuts(thr: float, factor: float = 1.0) -> np.ndarray:
+    """Flag cuts of the joint detector, [2, 9] fp32: row 0 for ``thr``, row 1
+    for ``thr * factor`` (groups with a differing canary), column k for k
+    live members.  The threshold stays in sigma units: the cut is the
+    Mahalanobis distance whose chi-square(k) upper tail equals the two-sided
+    normal tail of ``thr``, so ``cut(thr, 1) == thr``; column 0 is 0."""
+    from scipy.special import chdtri, erfc
+    out = np.zeros((2, MVN_MAX_K + 1), np.float64)
+    for r, t in enumerate((float(thr), float(thr) * float(factor))):
+        p = erfc(t / np.sqrt(2.0))
+        out[r, 1:] = np.sqrt(chdtri(np.arange(1, MVN_MAX_K + 1), p))
+        out[r, 1] = t
+    return out.astype(np.float32)
+
+
+def _pack_words(flag: np.ndarray) -> np.ndarray:
+    P, m = flag.shape
+    NW = max(1, (m + 63) // 64)
+    padded = np.zeros((P, NW * 64), bool)
+    padded[:, :m] = flag
+    return np.packbits(padded.reshape(P, NW, 64), axis=2, bitorder="little").view(np.uint64).reshape(P, NW).view(
+        np.int64)
+
+
+def ref_mvn(hist, cur, rows, K: int, cuts, lowered, min_n: int):
+    """fp64 oracle of the joint multivariate-normal detector over groups of
+    ``K`` rows (``rows`` [G, 8] row ids into ``hist`` [R, T] / ``cur`` [R, n]).
+    Returns (params [G, 2 + K + K(K+1)/2] = (N, k, mean, upper-triangular
+    covariance), dist [G, n], flags [G, NW] int64, count [G] int32,
+    valid [G] int32: bit 0 enough complete history, bit 1 a current point
+    present)."""
+    hist = np.asarray(hist, np.float32)
+    cur = np.asarray(cur, np.float32)
+    rows = np.asarray(rows)
+    cuts = np.asarray(cuts, np.float32)
+    G, n = rows.shape[0], cur.shape[1]
+    iu = np.triu_indices(K)
+    params = np.zeros((G, 2 + K + len(iu[0])), np.float32)
+    dist = np.full((G, n), np.nan, np.float32)
+    flag = np.zeros((G, n), bool)
+    valid = np.zeros(G, np.int32)
+    used = np.zeros(G, np.float32)
+    for g in range(G):
+        r = rows[g, :K].astype(np.int64)
+        h = hist[r].astype(np.float64)
+        x = cur[r].astype(np.float64)
+        h = h[:, np.isfinite(h).all(0)]                      # complete columns
+        N = h.shape[1]
+        mu = h.mean(1) if N else np.zeros(K)
+        d = h - mu[:, None]
+        C = d @ d.T / max(N - 1, 1)
+        live = np.diag(C) > 1e-12 * mu * mu + 1e-30
+        k = int(live.sum())
+        params[g, 0], params[g, 1], params[g, 2:2 + K], params[g, 2 + K:] = N, k, mu, C[iu]
+        used[g] = cuts[1 if lowered[g] else 0, k]
+        present = np.isfinite(x).all(0)
+        ok = N >= max(int(min_n), K + 2)
+        valid[g] = int(ok) | (int(present.any()) << 1)
+        if not ok:
+            continue
+        dg = np.zeros(n)
+        if k:
+            sd = np.sqrt(np.diag(C)[live])
+            Rm = C[np.ix_(live, live)] / np.outer(sd, sd)
+            np.fill_diagonal(Rm, 1.0)
+            L = np.linalg.cholesky(Rm + MVN_RIDGE * np.eye(k))
+            z = np.where(present, (x[live] - mu[live, None]) / sd[:, None], 0.0)
+            dg = np.sqrt((np.linalg.solve(L, z) ** 2).sum(0))
+        dead = ~live
+        if dead.any():
+            with np.errstate(invalid="ignore"):
+                moved = (np.abs(x[dead] - mu[dead, None]) > 1e-6 * np.abs(mu[dead, None]) + 1e-12).any(0)
+            dg = np.where(moved, np.inf, dg)
+        dist[g] = np.where(present, dg, np.nan)
+        with np.errstate(invalid="ignore"):
+            flag[g] = present & (dist[g] > used[g])
+    return params, dist, _pack_words(flag), flag.sum(1).astype(np.int32), valid
+
+
+def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts, lowered: torch.Tensor,
+        min_n: int):
+    """Joint multivariate-normal detector (K12) over groups of ``K`` member
+    rows: ``rows`` [G, 8] int32 row ids into ``hist`` [R, ld] (first ``T``
+    columns) and ``cur`` [R, n], -1 padded past ``K``; ``cuts`` from
+    :func:`mvn_cuts`; ``lowered`` [G] uint8 picks row 1 of ``cuts``.
+    Returns what :func:`ref_mvn` returns, which is also the CPU path."""
+    check(2 <= int(K) <= MVN_MAX_K, f"group size must be in [2, {MVN_MAX_K}]")
+    check(rows.dim() == 2 and rows.shape[1] == MVN_MAX_K and rows.dtype == torch.int32, "rows must be int32 [G, 8]")
+    check(hist.dtype == torch.float32 and cur.dtype == torch.float32 and hist.shape[0] == cur.shape[0]
+          and 0 < T <= hist.shape[1], "hist / cur must be fp32 with the same rows")
+    G, n = rows.shape[0], cur.shape[1]
+    check(lowered.numel() == G and lowered.dtype == torch.uint8, "lowered must be uint8 [G]")
+    cuts = np.asarray(cuts, np.float32)
+    check(cuts.shape == (2, MVN_MAX_K + 1), "cuts must be [2, 9]")
+    if G:
+        used = rows[:, :K]
+        check(int(used.min().item()) >= 0 and int(used.max().item()) < hist.shape[0], "row ids out of range")
+    if hist.is_cuda:
+        check(hist.stride(1) == 1 and hist.stride(0) % 4 == 0 and hist.data_ptr() % 16 == 0 and cur.stride(1) == 1,
+              "rows must be contiguous, 16-B aligned, with a row stride that is a multiple of 4")
+    NW = max(1, (n + 63) // 64)
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_mvn(hist.numpy()[:, :T], cur.numpy(), rows.numpy(), K, cuts,
+                                                          lowered.numpy(), min_n))
+    require_native(hist)
+    d = hist.device
+    NA = K + K * (K + 1) // 2
+    params = torch.empty((G, 2 + NA), dtype=torch.float32, device=d)
+    dist = torch.empty((G, n), dtype=torch.float32, device=d)
+    flags = torch.zeros((G, NW), dtype=torch.int64, device=d)
+    cnt = torch.empty((G,), dtype=torch.int32, device=d)
+    valid = torch.empty((G,), dtype=torch.int32, device=d)
+    if G == 0 or n == 0:
+        return params, dist, flags, cnt, valid
+    ct = torch.from_numpy(cuts).to(d)
+    rows = rows.contiguous()
+    LIB.call("fm_mvn", ptr(hist), hist.stride(0), int(T), hist.shape[0], ptr(cur), cur.stride(0), n, ptr(rows), G,
+             int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), MVN_FORM, ptr(params), ptr(dist), ptr(flags), NW,
+             ptr(cnt), ptr(valid), stream_of(hist))
+    return params, dist, flags, cnt, valid
 
 
 # --------------------------------------------------------------------------- K8
