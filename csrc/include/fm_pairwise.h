@@ -1,0 +1,544 @@
+// Pairwise rank tests (K4), the device code shared by every canary-scoring
+// unit that runs them: pairwise.hip (stand-alone kernels), canary_rows.hip
+// (fused row kernel) and tick_front.hip (role-split front kernel).
+// pw_compute with K = 16 needs the per-file flag
+// `-mllvm -pragma-unroll-threshold=1000000` (see pairwise.hip).
+//
+// Reference behaviour being rebuilt (foremast-brain is external; see
+// docs/BRAIN_SPEC.md): per (service, metric) the brain fits a historical model
+// (ML_ALGORITHM=moving_average_all, deploy/foremast/3_brain/foremast-brain.yaml:24-25),
+// compares canary vs baseline with pairwise tests (foremast-brain/README.md:32-38,
+// docs/guides/design.md:35) and flags current points outside the bounds
+// (design.md:43, fail fast).
+//
+// Layout: rows = services x metrics, row r -> metric r % M.  history [R, ld_h]
+// fp32 (NaN = missing sample), current [R, ld_c], baseline [R, ld_b].
+#pragma once
+#include "fm_common.h"
+
+using namespace fm;
+
+// ---------------------------------------------------------------------------
+// K4: pairwise tests. One wave per (service, metric) row, 4 rows per 256-thread
+// workgroup.  The pooled sample (n1 + n2 <= 64*K) is sorted in registers with a
+// bitonic network (in-register swaps for strides >= 64, __shfl_xor below),
+// average ranks with ties come from a max-scan / suffix-min-scan over tie runs.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr float kPad = INFINITY;
+
+// SPLIT (K == 2 only): register 0 holds sample 1 and register 1 sample 2
+// (each <= 64 values).  Every stage up to size 64 then stays inside one
+// register, so a value's sample is its register index and the tags need no
+// exchange; they are rebuilt (k, or -1 for pads) before the final 128-merge.
+// That drops the tag exchange and select from 21 of the 27 lane-exchange
+// steps.
+template <int K, bool SPLIT = false>
+__device__ __forceinline__ void bitonic_sort(float (&v)[K], int (&tag)[K]) {
+  // Branch-free compare-exchange (selects, no exec-mask branches): strides
+  // >= 64 swap registers inside the lane, smaller strides exchange with the
+  // partner lane through DPP / permlane (xor_lane_any).
+  static_assert(!SPLIT || K == 2, "split layout is two 64-lane registers");
+  const int lane = lane_id();
+#pragma unroll
+  for (int size = 2; size <= 64 * K; size <<= 1) {
+    const bool tags = !SPLIT || size > 64;
+    if (SPLIT && size == 128) {
+#pragma unroll
+      for (int k = 0; k < K; ++k) tag[k] = v[k] == kPad ? -1 : k;
+    }
+#pragma unroll
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (stride >= 64) {
+        const int ks = stride / 64;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int p = k ^ ks;
+          if (p > k) {
+            const int i = k * 64 + lane;
+            const bool asc = (i & size) == 0;
+            const float a = v[k], b = v[p];
+            const int ta = tag[k], tb = tag[p];
+            const bool alt = a < b;
+            const float mn = alt ? a : b, mx = alt ? b : a;
+            const int tmn = alt ? ta : tb, tmx = alt ? tb : ta;
+            v[k] = asc ? mn : mx; v[p] = asc ? mx : mn;
+            tag[k] = asc ? tmn : tmx; tag[p] = asc ? tmx : tmn;
+          }
+        }
+      } else {
+        float ov[K];
+        int ot[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          ov[k] = xor_lane_any(v[k], stride);
+          ot[k] = tags ? xor_lane_any(tag[k], stride) : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const int i = k * 64 + lane;
+          const bool asc = (i & size) == 0;
+          const bool lower = (lane & stride) == 0;
+          // keep the smaller value in the lower lane of an ascending pair
+          const bool keep_min = lower == asc;
+          // select min or max of the pair; the tag follows only when the value
+          // actually moved (equal values keep their own tags on both lanes)
+          const bool vlt = v[k] < ov[k];
+          const float mn = vlt ? v[k] : ov[k], mx = vlt ? ov[k] : v[k];
+          const float nv = keep_min ? mn : mx;
+          if (tags) tag[k] = nv != v[k] ? ot[k] : tag[k];
+          v[k] = nv;
+        }
+      }
+    }
+  }
+}
+
+// Average (1-based) ranks for a sorted register array whose first n entries are
+// real.  tie_term accumulates sum(t^3 - t) over tie runs; is_end marks the last
+// element of each run (where empirical CDFs are evaluated).
+template <int K>
+__device__ __forceinline__ void avg_ranks(const float (&v)[K], int n, int (&rank2)[K], bool (&is_end)[K],
+                                          int& tie_term) {
+  // rank2 = 2 x (1-based average rank) = start + end + 2: exact integers, so
+  // rank sums and the tie term sum(t^3 - t) (<= 1024^3 < 2^31) need no doubles.
+  const int lane = lane_id();
+  int start_idx[K];
+  int carry = 0;
+  float last_prev = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = k * 64 + lane;
+    const float prev = lane_prev(v[k], last_prev);
+    const bool st = (i == 0) || (v[k] != prev);
+    int s = st ? i : 0;
+    s = wave_incl_max(s, 0);
+    s = s > carry ? s : carry;
+    start_idx[k] = s;
+    carry = lane_bcast(s, 63);
+    last_prev = lane_bcast(v[k], 63);
+  }
+  int carry_e = 0x7fffffff;
+  float next_first = 0.f;
+  int tl = 0;
+#pragma unroll
+  for (int k = K - 1; k >= 0; --k) {
+    const int i = k * 64 + lane;
+    const float next = lane_next(v[k], next_first);
+    const bool en = (i < n) && ((i == n - 1) || (v[k] != next));
+    int e = en ? i : 0x7fffffff;
+    e = wave_incl_suffix_min(e, 0x7fffffff);
+    e = e < carry_e ? e : carry_e;
+    carry_e = lane_bcast(e, 0);
+    next_first = lane_bcast(v[k], 0);
+    is_end[k] = en;
+    rank2[k] = start_idx[k] + e + 2;
+    if (i < n && i == start_idx[k]) {
+      const int t = e - start_idx[k] + 1;
+      tl += t * t * t - t;
+    }
+  }
+  tie_term = wave_sum(tl);
+}
+
+}  // namespace
+
+enum { T_MW = 0, T_WIL = 1, T_KRU = 2, T_KS = 3, T_T = 4, T_FRI = 5, N_TESTS = 6 };
+constexpr int kSuff = 14;
+
+// Per-row pairwise inputs, split into a LOAD half (raw samples into
+// registers, no arithmetic that would wait on them) and a COMPUTE half, so a
+// fused kernel can put other loads in flight between the two.
+template <int K>
+struct PwIn {
+  static constexpr int KW = (K + 1) / 2;
+  float v[K];     // pooled sample slot i = k*64 + lane: cur[i] (i < n_cur) or base[i - n_cur]
+  float pc[KW];   // position-paired cur[j], base[j] (Wilcoxon / Friedman)
+  float pb[KW];
+};
+
+// SPLIT (K == 2, n_cur <= 64, n_base <= 64): v[0] = current, v[1] = baseline
+// instead of the pooled order (see bitonic_sort).
+template <int K, bool SPLIT = false>
+__device__ __forceinline__ void pw_load(const float* __restrict__ c, const float* __restrict__ b, int n_cur,
+                                        int n_base, PwIn<K>& in) {
+  const int lane = lane_id();
+  if constexpr (SPLIT) {
+    in.v[0] = lane < n_cur ? c[lane] : kPad;
+    in.v[1] = lane < n_base ? b[lane] : kPad;
+  } else {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = k * 64 + lane;
+      in.v[k] = i < n_cur ? c[i] : (i < n_cur + n_base ? b[i - n_cur] : kPad);
+    }
+  }
+  const int npair = n_cur < n_base ? n_cur : n_base;
+#pragma unroll
+  for (int k = 0; k < PwIn<K>::KW; ++k) {
+    const int j = k * 64 + lane;
+    in.pc[k] = j < npair ? c[j] : 0.f;
+    in.pb[k] = j < npair ? b[j] : 0.f;
+  }
+}
+
+template <int K, bool SPLIT = false>
+__device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o) {
+  // Everything exact is carried in integers (counts, doubled rank sums, tie
+  // terms, the KS numerator); only the Welch moments are floating point.
+  const int lane = lane_id();
+  float (&v)[K] = in.v;
+  int tag[K];
+  float s1 = 0.f, s2 = 0.f;
+  int c12 = 0;  // n1 | n2 << 16
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = k * 64 + lane;
+    int t = SPLIT ? (lane < (k == 0 ? n_cur : n_base) ? k : -1) : (i < n_cur ? 0 : (i < n_cur + n_base ? 1 : -1));
+    float x = v[k];
+    if (!isfinite(x)) { x = kPad; t = -1; }
+    v[k] = x; tag[k] = t;
+    if (t == 0) { s1 += x; c12 += 1; }
+    if (t == 1) { s2 += x; c12 += 1 << 16; }
+  }
+  c12 = wave_sum(c12);
+  const int n1 = c12 & 0xFFFF, n2 = c12 >> 16;
+  const int n = n1 + n2;
+  const float m1 = wave_sum(s1) / (float)(n1 > 0 ? n1 : 1), m2 = wave_sum(s2) / (float)(n2 > 0 ? n2 : 1);
+  float q1 = 0.f, q2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (tag[k] == 0) { const float d = v[k] - m1; q1 += d * d; }
+    if (tag[k] == 1) { const float d = v[k] - m2; q2 += d * d; }
+  }
+  q1 = wave_sum(q1); q2 = wave_sum(q2);
+
+  // ---- Wilcoxon signed-rank on position-paired differences (zero_method='wilcox')
+  constexpr int KW = PwIn<K>::KW;
+  float dv[KW];
+  int dt[KW];
+  const int npair = n_cur < n_base ? n_cur : n_base;
+  int cwz = 0;  // nonzero | positive << 10 | zero << 20 (each <= 512)
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    const int j = k * 64 + lane;
+    float d = kPad;
+    int t = -1;
+    if (j < npair) {
+      const float xc = in.pc[k], xb = in.pb[k];
+      if (isfinite(xc) && isfinite(xb)) {
+        const float dd = xc - xb;
+        if (dd != 0.f) { d = fabsf(dd); t = dd > 0.f ? 1 : 0; cwz += 1 + (t << 10); }
+        else cwz += 1 << 20;
+      }
+    }
+    dv[k] = d; dt[k] = t;
+  }
+  cwz = wave_sum(cwz);
+  const int nw = cwz & 0x3FF, npos = (cwz >> 10) & 0x3FF, nzero = cwz >> 20;
+
+  bitonic_sort<K, SPLIT>(v, tag);
+  int rk2[K];
+  bool en[K];
+  int tie = 0;
+  avg_ranks<K>(v, n, rk2, en, tie);
+
+  int r1x2 = 0;
+  int dnum = 0;   // max |a1 n2 - a2 n1| over tie-run ends = D n1 n2
+  int base12 = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (tag[k] == 0) r1x2 += rk2[k];
+    // KS: inclusive prefix counts of both samples along the sorted order, one packed scan
+    const int a12 = wave_incl_sum(tag[k] == 0 ? 1 : (tag[k] == 1 ? (1 << 16) : 0)) + base12;
+    base12 = lane_bcast(a12, 63);
+    if (en[k] && n1 > 0 && n2 > 0) {
+      const int a1 = a12 & 0xFFFF, a2 = a12 >> 16;
+      const int dd = abs(a1 * n2 - a2 * n1);
+      dnum = dd > dnum ? dd : dnum;
+    }
+  }
+  r1x2 = wave_sum(r1x2);
+  dnum = wave_max(dnum);
+
+  bitonic_sort<KW>(dv, dt);
+  int rw2[KW];
+  bool ew[KW];
+  int tiew = 0;
+  avg_ranks<KW>(dv, nw, rw2, ew, tiew);
+  int rplus2 = 0;
+#pragma unroll
+  for (int k = 0; k < KW; ++k)
+    if (dt[k] == 1) rplus2 += rw2[k];
+  rplus2 = wave_sum(rplus2);
+
+  // Per-row sufficient statistics; p-values are evaluated one row per THREAD
+  // by pvalue_kernel (the double-precision special functions would otherwise
+  // run on lane 0 with 63 lanes idle).
+  if (lane == 0) {
+    o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * r1x2; o[4] = tie;
+    o[5] = (n1 > 0 && n2 > 0) ? (double)dnum / ((double)n1 * n2) : 0.0;
+    o[6] = 0.5 * rplus2; o[7] = tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
+    o[12] = npos; o[13] = nzero;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Counting form of the same statistics (no sort).  Every average rank is
+// 2*rank = 2*#(v < x) + #(v == x) + 1, the KS empirical CDFs at x are the
+// "<=" counts per sample, the tie term is sum over samples of (t_i^2 - 1)
+// (t_i = size of x's tie run), and the Wilcoxon ranks are the same counts over
+// the non-zero |d|.  The row's values go to LDS once; each lane then sweeps
+// them with broadcast ds_read_b128 (4 values per instruction, one address for
+// the whole wave: conflict-free), so the work is ~n independent compare/adds
+// per owned value instead of the bitonic network's dependent exchange chain.
+// ---------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ void pw_compute_count(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o,
+                                                 float* __restrict__ lds /* >= 3*64*K + 12 floats */) {
+  constexpr int KW = PwIn<K>::KW;
+  const int lane = lane_id();
+  const int n = n_cur + n_base;
+  const int nc4 = (n_cur + 3) & ~3, nb4 = (n_base + 3) & ~3;
+  float* pc = lds;                      // current sample, +inf for missing / padding
+  float* pb = lds + 64 * K + 4;         // baseline sample
+  float* pd = lds + 128 * K + 8;        // |d| of non-zero pairs, +inf otherwise
+  float x[K];
+  int tag[K];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = k * 64 + lane;
+    int t = i < n_cur ? 0 : (i < n ? 1 : -1);
+    float v = in.v[k];
+    if (!isfinite(v)) { v = kPad; t = -1; }
+    x[k] = v; tag[k] = t;
+    if (t == 0) s1 += v;
+    if (t == 1) s2 += v;
+    if (i < n_cur) pc[i] = v;
+    else if (i < n) pb[i - n_cur] = v;
+  }
+  if (lane < 4) {
+    if (n_cur + lane < nc4) pc[n_cur + lane] = kPad;
+    if (n_base + lane < nb4) pb[n_base + lane] = kPad;
+  }
+  int n1 = 0, n2 = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    n1 += __popcll(__ballot(tag[k] == 0));
+    n2 += __popcll(__ballot(tag[k] == 1));
+  }
+  const float m1 = wave_sum(s1) / (float)(n1 > 0 ? n1 : 1), m2 = wave_sum(s2) / (float)(n2 > 0 ? n2 : 1);
+  float q1 = 0.f, q2 = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (tag[k] == 0) { const float d = x[k] - m1; q1 += d * d; }
+    if (tag[k] == 1) { const float d = x[k] - m2; q2 += d * d; }
+  }
+  q1 = wave_sum(q1); q2 = wave_sum(q2);
+
+  const int npair = n_cur < n_base ? n_cur : n_base;
+  const int npp4 = (npair + 3) & ~3;
+  float dabs[KW];
+  int dsgn[KW];   // 1 positive, 0 negative, -1 excluded
+  int npos = 0, nneg = 0, nzero = 0;
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    const int j = k * 64 + lane;
+    float d = kPad;
+    int t = -1;
+    bool zero = false;
+    if (j < npair) {
+      const float xc = in.pc[k], xb = in.pb[k];
+      if (isfinite(xc) && isfinite(xb)) {
+        const float dd = xc - xb;
+        if (dd != 0.f) { d = fabsf(dd); t = dd > 0.f ? 1 : 0; }
+        else zero = true;
+      }
+    }
+    dabs[k] = d; dsgn[k] = t;
+    npos += __popcll(__ballot(t == 1));
+    nneg += __popcll(__ballot(t == 0));
+    nzero += __popcll(__ballot(zero));
+    if (j < npp4) pd[j] = d;
+  }
+  const int nw = npos + nneg;
+  __builtin_amdgcn_wave_barrier();   // LDS stores of this wave visible to its own reads
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+
+  // pooled sample: per owned value, "<" and "==" counts against cur and base
+  int lt_c[K], eq_c[K], lt_b[K], eq_b[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) { lt_c[k] = 0; eq_c[k] = 0; lt_b[k] = 0; eq_b[k] = 0; }
+  for (int j = 0; j < nc4; j += 4) {
+    const float4 w = *reinterpret_cast<const float4*>(pc + j);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      lt_c[k] += (w.x < x[k]) + (w.y < x[k]) + (w.z < x[k]) + (w.w < x[k]),
+      eq_c[k] += (w.x == x[k]) + (w.y == x[k]) + (w.z == x[k]) + (w.w == x[k]);
+  }
+  for (int j = 0; j < nb4; j += 4) {
+    const float4 w = *reinterpret_cast<const float4*>(pb + j);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      lt_b[k] += (w.x < x[k]) + (w.y < x[k]) + (w.z < x[k]) + (w.w < x[k]),
+      eq_b[k] += (w.x == x[k]) + (w.y == x[k]) + (w.z == x[k]) + (w.w == x[k]);
+  }
+  int r1x2 = 0, tie = 0, dnum = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if (tag[k] >= 0) {
+      const int lt = lt_c[k] + lt_b[k], t = eq_c[k] + eq_b[k];
+      if (tag[k] == 0) r1x2 += 2 * lt + t + 1;
+      tie += t * t - 1;
+      if (n1 > 0 && n2 > 0) {
+        const int a1 = lt_c[k] + eq_c[k], a2 = lt_b[k] + eq_b[k];
+        const int dd = abs(a1 * n2 - a2 * n1);
+        dnum = dd > dnum ? dd : dnum;
+      }
+    }
+  }
+  r1x2 = wave_sum(r1x2);
+  tie = wave_sum(tie);
+  dnum = wave_max(dnum);
+
+  // Wilcoxon ranks among the non-zero |d|
+  int rp2 = 0, tiew = 0;
+  {
+    int ltw[KW], eqw[KW];
+#pragma unroll
+    for (int k = 0; k < KW; ++k) { ltw[k] = 0; eqw[k] = 0; }
+    for (int j = 0; j < npp4; j += 4) {
+      const float4 w = *reinterpret_cast<const float4*>(pd + j);
+      const float wv[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int k = 0; k < KW; ++k) ltw[k] += wv[u] < dabs[k], eqw[k] += wv[u] == dabs[k];
+    }
+#pragma unroll
+    for (int k = 0; k < KW; ++k) {
+      if (dsgn[k] >= 0) {
+        tiew += eqw[k] * eqw[k] - 1;
+        if (dsgn[k] == 1) rp2 += 2 * ltw[k] + eqw[k] + 1;
+      }
+    }
+  }
+  rp2 = wave_sum(rp2);
+  tiew = wave_sum(tiew);
+  __builtin_amdgcn_wave_barrier();   // the LDS slot is reused by the next row
+
+  if (lane == 0) {
+    o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * r1x2; o[4] = tie;
+    o[5] = (n1 > 0 && n2 > 0) ? (double)dnum / ((double)n1 * n2) : 0.0;
+    o[6] = 0.5 * rp2; o[7] = tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
+    o[12] = npos; o[13] = nzero;
+  }
+}
+
+// One row's sufficient statistics (sort form): the split layout when both
+// samples fit one register each (the usual 5 pods x 10 points per side).
+template <int K>
+__device__ __forceinline__ void pw_row(const float* __restrict__ c, const float* __restrict__ b, int n_cur,
+                                       int n_base, double* __restrict__ o) {
+  PwIn<K> in;
+  if constexpr (K == 2) {
+    if (n_cur <= 64 && n_base <= 64) {
+      pw_load<K, true>(c, b, n_cur, n_base, in);
+      pw_compute<K, true>(in, n_cur, n_base, o);
+      return;
+    }
+  }
+  pw_load<K>(c, b, n_cur, n_base, in);
+  pw_compute<K>(in, n_cur, n_base, o);
+}
+
+// p-value of ONE test for one row from its sufficient statistics (NaN when the
+// test is gated out).  t is uniform per workgroup (grid y), so the fp64
+// special-function code paths never diverge inside a wave.
+__device__ __forceinline__ void eval_test(int t, const double* __restrict__ o, int min_mw, int min_wil, int min_kru,
+                                          double& pv, double& sv) {
+  const int n1 = (int)o[0], n2 = (int)o[1], nw = (int)o[2];
+  const double r1 = o[3], tie = o[4], dmax = o[5], rplus = o[6], tiew = o[7];
+  const double m1 = o[8], m2 = o[9], q1 = o[10], q2 = o[11];
+  const int n = n1 + n2;
+  const double NaN = __builtin_nan("");
+  pv = NaN;
+  sv = NaN;
+  const double dn1 = n1, dn2 = n2, dn = n;
+  switch (t) {
+    case T_MW:
+      if (n1 >= min_mw && n2 >= min_mw && n1 > 0 && n2 > 0) {
+        const double u1 = r1 - dn1 * (dn1 + 1.0) / 2.0;
+        const double u2 = dn1 * dn2 - u1;
+        const double u = u1 > u2 ? u1 : u2;
+        const double mu = dn1 * dn2 / 2.0;
+        const double var = dn1 * dn2 / 12.0 * ((dn + 1.0) - tie / (dn * (dn - 1.0)));
+        sv = u1;
+        if (var > 0) {
+          const double z = (u - mu - 0.5) / sqrt(var);
+          double pp = 2.0 * norm_sf(z);
+          pv = pp > 1.0 ? 1.0 : pp;
+        } else {
+          pv = 1.0;
+        }
+      }
+      break;
+    case T_KRU:
+      if (n1 >= min_kru && n2 >= min_kru && n1 > 0 && n2 > 0) {
+        const double r2 = dn * (dn + 1.0) / 2.0 - r1;
+        double h = 12.0 / (dn * (dn + 1.0)) * (r1 * r1 / dn1 + r2 * r2 / dn2) - 3.0 * (dn + 1.0);
+        const double corr = 1.0 - tie / (dn * dn * dn - dn);
+        if (corr > 0) {
+          sv = h / corr;
+          pv = h / corr > 0 ? erfc(sqrt(0.5 * h / corr)) : 1.0;   // chi2(1) survival
+        }
+      }
+      break;
+    case T_KS:
+      if (n1 >= min_mw && n2 >= min_mw && n1 > 0 && n2 > 0) {
+        const double en_ = dn1 * dn2 / (dn1 + dn2);
+        sv = dmax;
+        pv = kolmogorov_sf(sqrt(en_) * dmax);
+      }
+      break;
+    case T_T:
+      if (n1 >= 2 && n2 >= 2 && n1 >= min_kru && n2 >= min_kru) {
+        const double v1 = q1 / (dn1 - 1.0), v2 = q2 / (dn2 - 1.0);
+        const double se2 = v1 / dn1 + v2 / dn2;
+        if (se2 > 0) {
+          const double tt = (m1 - m2) / sqrt(se2);
+          const double a = v1 / dn1, bb = v2 / dn2;
+          const double df = se2 * se2 / (a * a / (dn1 - 1.0) + bb * bb / (dn2 - 1.0));
+          sv = tt;
+          pv = student_t_2sided(tt, df);
+        }
+      }
+      break;
+    case T_WIL:
+      if (nw >= min_wil && nw > 0) {
+        const double dnw = nw;
+        const double tot = dnw * (dnw + 1.0) / 2.0;
+        const double rminus = tot - rplus;
+        const double T = rplus < rminus ? rplus : rminus;
+        const double mn = dnw * (dnw + 1.0) / 4.0;
+        const double se = sqrt(dnw * (dnw + 1.0) * (2.0 * dnw + 1.0) / 24.0 - tiew / 48.0);
+        sv = T;
+        if (se > 0) {
+          double pp = 2.0 * norm_sf(fabs((T - mn) / se));
+          pv = pp > 1.0 ? 1.0 : pp;
+        }
+      }
+      break;
+    default: {  // T_FRI: k = 2 treatments over paired blocks, (n+ - n-)^2 / (n+ + n-), chi2(1)
+      const int npos = (int)o[12], nzero = (int)o[13];
+      const int nneg = nw - npos, b = nw + nzero;
+      if (b >= min_wil && b > 0) {
+        const double q = nw > 0 ? (double)(npos - nneg) * (npos - nneg) / nw : 0.0;
+        sv = q;
+        pv = q > 0 ? erfc(sqrt(0.5 * q)) : 1.0;
+      }
+    }
+  }
+}

@@ -1,0 +1,124 @@
+// Register-resident statistics of one history row (K1), shared by
+// hist_stats.hip (stats_decide_kernel, hist_stats_kernel) and the history
+// role of tick_front.hip, plus the host-side choice of the NV instantiation.
+#pragma once
+#include <type_traits>
+
+#include "fm_common.h"
+
+using namespace fm;
+
+// Mean / population std / finite count of one history row, computed by a
+// 256-thread block with the row held in registers (NV float4 per thread).
+// Fast path for rows without missing samples (the common case): the plain
+// sum is computed with packed f32 adds (v_pk_add_f32, 2 elements per
+// instruction) and is finite iff every sample is; only a non-finite sum sends
+// the block to the masked per-element path.  Per element that is ~0.75 VALU
+// instructions instead of ~8, which leaves the CU's issue slots to the
+// pairwise kernel running concurrently on the side stream.
+// The row is read through a buffer resource (wave-uniform, in SGPRs) with the
+// thread's 16 B as the VGPR offset and the 4-KB step as a scalar offset: no
+// 64-bit VGPR address per load, and the range check returns zeros past the
+// row (no clamp).  109 -> 72 VGPRs for the history kernel; the front kernel
+// drops from 111 to 87 (the p-value call now bounds it): five waves per SIMD
+// instead of four, i.e. one pairwise + four history workgroups per CU.
+template <int NV>
+__device__ __forceinline__ void block_row_stats(const float* __restrict__ hrow, int T, double* red, int* redi,
+                                                float& mf, float& sd, int& n) {
+  typedef float f2 __attribute__((ext_vector_type(2)));
+  typedef float nt4 __attribute__((ext_vector_type(4)));
+  const int tid = threadIdx.x;
+  const int nq = (T + 3) >> 2;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)hrow, (short)0, nq * 16, 0x00020000);
+  nt4 q[NV];
+  f2 acc = {0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int qi = tid + j * 256;
+    nt4 v = __builtin_bit_cast(nt4, __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, j * 4096, 2 /* nt */));
+    if (qi == nq - 1) {
+      const int e0 = qi * 4;
+      if (e0 + 1 >= T) v.y = 0.f;
+      if (e0 + 2 >= T) v.z = 0.f;
+      if (e0 + 3 >= T) v.w = 0.f;
+    }
+    q[j] = v;
+    acc += v.xy;
+    acc += v.zw;
+  }
+  const double tot = block_sum<256>((double)acc.x + (double)acc.y, red);
+  if (isfinite(tot)) {
+    n = T;
+    mf = (float)(tot / T);
+    const f2 mm = {mf, mf};
+    f2 a2 = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int qi = tid + j * 256;
+      if (qi < nq - 1) {
+        const f2 d0 = q[j].xy - mm, d1 = q[j].zw - mm;
+        a2 += d0 * d0;
+        a2 += d1 * d1;
+      } else if (qi == nq - 1) {
+        const int e0 = qi * 4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (e0 + c < T) { const float d = q[j][c] - mf; a2.x += d * d; }
+      }
+    }
+    const double sst = block_sum<256>((double)a2.x + (double)a2.y, red);
+    sd = (float)sqrt(sst / n);
+    return;
+  }
+  f2 ms = {0.f, 0.f};
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int e0 = (tid + j * 256) * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float x = q[j][c];
+      const bool ok = e0 + c < T && isfinite(x);
+      cnt += ok ? 1 : 0;
+      ms[c & 1] += ok ? x : 0.f;
+    }
+  }
+  const double t2 = block_sum<256>((double)ms.x + (double)ms.y, red);
+  n = block_sum<256>(cnt, redi);
+  mf = n > 0 ? (float)(t2 / n) : 0.f;
+  f2 a2 = {0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int e0 = (tid + j * 256) * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float x = q[j][c];
+      const float d = (e0 + c < T && isfinite(x)) ? x - mf : 0.f;
+      a2[c & 1] += d * d;
+    }
+  }
+  const double sst = block_sum<256>((double)a2.x + (double)a2.y, red);
+  sd = n > 0 ? (float)sqrt(sst / n) : 0.f;
+}
+
+// History row of logical row `row`: identity, or a slot of the brain's
+// device-resident history store (engine/resident.py) when a row map is given.
+// The row index is wave-uniform, so the map read is one scalar load.
+__device__ __forceinline__ int64_t hist_row(const int* __restrict__ rowmap, int64_t row) {
+  return rowmap != nullptr ? (int64_t)rowmap[row] : row;
+}
+
+// Host side: the block_row_stats<NV> instantiation for a history row of nq
+// float4 (256 threads x NV float4 hold the row).  f is a generic lambda called
+// with std::integral_constant<int, NV>; hipErrorInvalidValue past 256 x 16.
+template <class F>
+inline int row_stats_dispatch_nv(int nq, F&& f) {
+  if (nq <= 256 * 2) f(std::integral_constant<int, 2>{});
+  else if (nq <= 256 * 4) f(std::integral_constant<int, 4>{});
+  else if (nq <= 256 * 8) f(std::integral_constant<int, 8>{});
+  else if (nq <= 256 * 10) f(std::integral_constant<int, 10>{});
+  else if (nq <= 256 * 12) f(std::integral_constant<int, 12>{});
+  else if (nq <= 256 * 16) f(std::integral_constant<int, 16>{});
+  else return (int)hipErrorInvalidValue;
+  return 0;
+}

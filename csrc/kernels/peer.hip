@@ -295,3 +295,11 @@ FM_API int fm_memcpy_sync(void* dst, const void* src, int64_t bytes) {
   if (bytes <= 0) return 0;
   return (int)hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDefault);
 }
+
+// Async device -> pinned-host copy of the fleet verdict, issued on the
+// caller's stream so it is captured into the tick's HIP graph as a memcpy
+// node (the whole step — tick, all-gather, host copy — is one graph launch).
+FM_API int fm_copy_d2h_async(void* dst, const void* src, int64_t bytes, hipStream_t stream) {
+  if (bytes <= 0) return 0;
+  return (int)hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToHost, stream);
+}

@@ -99,7 +99,7 @@ class CanaryScorer:
         if xcd_balance is None:
             xcd_balance = os.environ.get("FM_XCD_BALANCE", "1") != "0"
         if self._queue is not None and xcd_balance:
-            self._queue[8 * 32 + 31] = 1      # control block: XCD-balanced history ranges (canary.hip kXcdCtl)
+            self._queue[8 * 32 + 31] = 1      # control block: XCD-balanced history ranges (tick_front.hip kXcdCtl)
         self._cus = (torch.cuda.get_device_properties(self.device).multi_processor_count
                      if self.device.type == "cuda" else 0)
         rules = [self.cfg.rule_for(a) for a in aliases]

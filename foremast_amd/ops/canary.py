@@ -2,7 +2,9 @@
 anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
-GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/canary.hip``;
+GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
+(``pairwise.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+``decide.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
 numerics oracle for tests).

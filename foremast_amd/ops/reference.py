@@ -236,7 +236,7 @@ def compact_anomalies(flags, cur, count):
 
 
 # ---------------------------------------------------------------------------
-# synthetic fleet (must mirror synth_kernel in csrc/kernels/canary.hip)
+# synthetic fleet (must mirror synth_kernel in csrc/kernels/synth.hip)
 
 _U = np.uint32
 

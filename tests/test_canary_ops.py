@@ -356,7 +356,7 @@ def test_gpu_front_tick_generic_shapes(cuda, M, P, T):
 
 @pytest.mark.gpu
 def test_gpu_front_xcd_balanced_ranges_equal_serial(cuda):
-    """32,768 rows (the balancing threshold, canary.hip kXcdMinRows): after a
+    """32,768 rows (the balancing threshold, tick_front.hip kXcdMinRows): after a
     few ticks the control block holds a split (monotone 2^-24 fractions ending
     at 1) and the XCD-balanced history ranges still give serial's results."""
     from foremast_amd.engine.scorer import CanaryScorer
@@ -429,3 +429,17 @@ def test_gpu_split_tick_equals_score(cuda, S, M):
     for i in range(2):
         torch.testing.assert_close(packed[i], ref.packed, rtol=0, atol=0)
 
+
+
+def test_native_library_exports_every_declared_entry_point():
+    """``_Lib.load`` skips names the library lacks, so an entry point lost
+    when kernels move between files would only surface when a GPU path calls
+    it: every name in ``_SIGS`` must resolve in libforemast_hip.so."""
+    import ctypes
+
+    from foremast_amd.ops import _lib
+    if not _lib._LIB_PATH.exists():
+        pytest.skip("native library not built")
+    lib = ctypes.CDLL(str(_lib._LIB_PATH))
+    missing = [name for name in _lib._SIGS if not hasattr(lib, name)]
+    assert not missing, missing

@@ -2,7 +2,11 @@
 """Build the native libraries in-tree.
 
 * ``foremast_amd/_native/libforemast_hip.so`` — every ``csrc/kernels/*.hip``
-  compiled by ``hipcc --offload-arch=gfx950`` (CDNA4 only, no other targets).
+  compiled by ``hipcc --offload-arch=gfx950`` (CDNA4 only, no other targets),
+  one unit per kernel family (the canary tick: ``pairwise``, ``hist_stats``,
+  ``tick_front``, ``canary_rows``, ``decide``, ``synth``; device code shared
+  between units lives in ``csrc/include/*.h``, and every unit is rebuilt when
+  a header changes).
 * ``foremast_amd/_native/libforemast_rt.so`` — host-side C++ runtime
   (``csrc/runtime/*.cpp``: Prometheus/Wavefront response parsing, the series
   packer) compiled with g++.

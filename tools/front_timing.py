@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Per-workgroup start/end of the role-split front kernel (build with
--DFM_FRONT_TIMING, load through FOREMAST_HIP_LIB): which role ends the
+"""Per-workgroup start/end of the role-split front kernel (rebuild
+csrc/kernels/tick_front.hip with -DFM_FRONT_TIMING:
+``python tools/build_native.py --variant NAME:tick_front:-DFM_FRONT_TIMING``,
+load the variant through FOREMAST_HIP_LIB): which role ends the
 kernel at a given shard size, and when the late history workgroups start.
 Prints one JSON object per shape (times in us from the first start)."""
 from __future__ import annotations
