@@ -104,33 +104,88 @@ FM_API int fm_stats_decide(const float* hist, int64_t ld_h, int T, const float* 
 template <int NV>
 __global__ __launch_bounds__(256) void hist_stats_kernel(const float* __restrict__ hist, int64_t ld_h, int T,
                                                          int64_t R, float* __restrict__ out /*[R,3]*/,
-                                                         const int* __restrict__ rowmap) {
+                                                         const int* __restrict__ rowmap, float* __restrict__ cache,
+                                                         unsigned* __restrict__ valid) {
   __shared__ double red[4];
   __shared__ int redi[4];
   for (int64_t row = blockIdx.x; row < R; row += gridDim.x) {
     float mf, sd;
     int n;
-    block_row_stats<NV>(hist + hist_row(rowmap, row) * ld_h, T, red, redi, mf, sd, n);
+    const int64_t p = hist_row(rowmap, row);
+    block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
     if (threadIdx.x == 0) {
       out[row * 3 + 0] = mf;
       out[row * 3 + 1] = sd;
       out[row * 3 + 2] = (float)n;
+      // (row-statistics cache, fm_row_stats.h: this launch tests no word)
+      if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
     }
   }
 }
 
-FM_API int fm_hist_stats_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
-                            const int* rowmap, hipStream_t stream) {
+static int hist_stats_launch(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
+                             const int* rowmap, float* cache, unsigned* valid, hipStream_t stream) {
   if (R <= 0) return 0;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
   const int nq = (T + 3) / 4;
   const dim3 grid((unsigned)(max_blocks > 0 && R > max_blocks ? max_blocks : R)), block(256);
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    hipLaunchKernelGGL(hist_stats_kernel<decltype(nv)::value>, grid, block, 0, stream, hist, ld_h, T, R, out, rowmap);
+    hipLaunchKernelGGL(hist_stats_kernel<decltype(nv)::value>, grid, block, 0, stream, hist, ld_h, T, R, out, rowmap,
+                       cache, valid);
   });
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
   return 0;
+}
+
+FM_API int fm_hist_stats_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
+                            const int* rowmap, hipStream_t stream) {
+  return hist_stats_launch(hist, ld_h, T, R, out, max_blocks, rowmap, nullptr, nullptr, stream);
+}
+
+// The same with the row-statistics cache of the history tensor
+// (fm_row_stats.h): a row whose validity word carries this view's tag is
+// copied from the cache, any other is reduced and recorded.
+template <int NV>
+__global__ __launch_bounds__(256) void hist_stats_cached_kernel(const float* __restrict__ hist, int64_t ld_h, int T,
+                                                                int64_t R, float* __restrict__ out /*[R,3]*/,
+                                                                const int* __restrict__ rowmap,
+                                                                float* __restrict__ cache,
+                                                                unsigned* __restrict__ valid) {
+  __shared__ double red[4];
+  __shared__ int redi[4];
+  __shared__ int s_list[256];
+  __shared__ int s_cnt;
+  hist_scan_cached<NV>(hist, ld_h, T, R, out, rowmap, cache, valid, blockIdx.x, gridDim.x, red, redi, s_list, &s_cnt);
+}
+
+// expect_miss 1: every row is reduced and recorded without a look at its
+// word, one workgroup per row (capped by max_blocks) as fm_hist_stats_rm;
+// 0: one workgroup per 256 rows, a row per thread, which reduces what does
+// miss.  Null cache pointers: fm_hist_stats_rm.
+FM_API int fm_hist_stats_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
+                                const int* rowmap, float* cache, unsigned* valid, int expect_miss,
+                                hipStream_t stream) {
+  if (cache == nullptr || valid == nullptr || T <= 0) cache = nullptr, valid = nullptr;   // (tag 0 means invalid)
+  if (cache == nullptr || expect_miss != 0)
+    return hist_stats_launch(hist, ld_h, T, R, out, max_blocks, rowmap, cache, valid, stream);
+  if (R <= 0) return 0;
+  if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
+  const int nq = (T + 3) / 4;
+  const dim3 grid((unsigned)((R + 255) / 256)), block(256);
+  const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
+    hipLaunchKernelGGL(hist_stats_cached_kernel<decltype(nv)::value>, grid, block, 0, stream, hist, ld_h, T, R, out,
+                       rowmap, cache, valid);
+  });
+  if (rc != 0) return rc;
+  FM_LAUNCH_CHECK();
+  return 0;
+}
+
+// Invalidate the first n validity words (a writer that cannot name its rows).
+FM_API int fm_hist_cache_invalidate(unsigned* valid, int64_t n, hipStream_t stream) {
+  if (valid == nullptr || n <= 0) return 0;
+  return (int)hipMemsetAsync(valid, 0, (size_t)n * sizeof(unsigned), stream);
 }
 
 FM_API int fm_hist_stats_capped(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,

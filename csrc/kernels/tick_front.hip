@@ -45,9 +45,9 @@ __device__ unsigned long long g_front_t[2 * 8192];
       const float *__restrict__ cur, int64_t ld_c, int n_cur, const float *__restrict__ base, int64_t ld_b,    \
       int n_base, double *__restrict__ suff, int nP, int min_mw, int min_wil, int min_kru,                     \
       float *__restrict__ pvals, float *__restrict__ pstats, unsigned *__restrict__ queue,                    \
-      const int *__restrict__ rowmap
+      const int *__restrict__ rowmap, float *__restrict__ cache, unsigned *__restrict__ valid, int scan
 #define FM_FRONT_ARGS hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, min_mw, min_wil, \
-      min_kru, pvals, pstats, queue, rowmap
+      min_kru, pvals, pstats, queue, rowmap, cache, valid, scan
 
 // Control block of the front kernel's history queue (uint32 words from
 // queue[kXcdCtl]; the queue is 8 x 32 counters + this block, zeroed by the
@@ -152,15 +152,32 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
     return;
   }
   const int nH = (int)gridDim.x - nP;
+  // Row-statistics cache (fm_row_stats.h).  scan: the host expects (nearly)
+  // every row to hit -- the history workgroups test their rows one per
+  // thread, copy the hits and reduce only the misses.  Otherwise (first tick,
+  // after an invalidation, no cache) every row is taken as a miss without
+  // looking: today's queue, plus the cache entry of each row it computes.
+  // Either way the device decides what is computed; the host's expectation
+  // only picks the shape.
+  if (scan) {
+    __shared__ int s_list[256];
+    __shared__ int s_cnt;
+    hist_scan_cached<NV>(hist, ld_h, T, R, hs, rowmap, cache, valid, (int64_t)blockIdx.x - nP, nH, red, redi, s_list,
+                         &s_cnt);
+    FM_FT_MARK(1);
+    return;
+  }
   if (queue == nullptr) {
     for (int64_t row = (int64_t)blockIdx.x - nP; row < R; row += nH) {
       float mf, sd;
       int n;
-      block_row_stats<NV>(hist + hist_row(rowmap, row) * ld_h, T, red, redi, mf, sd, n);
+      const int64_t p = hist_row(rowmap, row);
+      block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
       if (threadIdx.x == 0) {
         hs[row * 3 + 0] = mf;
         hs[row * 3 + 1] = sd;
         hs[row * 3 + 2] = (float)n;
+        if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
       }
     }
     FM_FT_MARK(1);
@@ -216,11 +233,13 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
     for (int64_t row = r0; row < r1; ++row) {
       float mf, sd;
       int n;
-      block_row_stats<NV>(hist + hist_row(rowmap, row) * ld_h, T, red, redi, mf, sd, n);
+      const int64_t p = hist_row(rowmap, row);
+      block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
       if (threadIdx.x == 0) {
         hs[row * 3 + 0] = mf;
         hs[row * 3 + 1] = sd;
         hs[row * 3 + 2] = (float)n;
+        if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
       }
     }
     __syncthreads();               // everyone is done reading s_next
@@ -261,24 +280,38 @@ static unsigned front_lds() {
 // one history workgroup per row); queue: dynamic history rows (or nullptr):
 // 8 x 32 + 64 zero-initialised uint32 -- the per-XCD counters and the
 // XCD-balance control block (kXcdCtl; word kXcdCtl + kCtlOn = 1 enables it).
-FM_API int fm_tick_front_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
-                            int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
-                            int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
-                            unsigned* queue, const int* rowmap, hipStream_t stream) {
+//
+// cache / valid: the row-statistics cache of the history tensor (per physical
+// row: float[3] and the validity word, fm_row_stats.h), or both nullptr.
+// expect_miss: what the host believes about this tick -- 1: rows were written
+// since the last tick (or this is the first): the launch is shaped for
+// streaming, exactly as without a cache, and records every row it computes;
+// 0: every row should hit: the history workgroups scan the validity words
+// (computing whatever does miss), nP / nH are taken as given for that shape
+// (nH 0 = one workgroup per 256 rows) and no dynamic LDS caps the pairwise
+// workgroups per CU.  A wrong expectation costs time, never correctness.
+FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
+                                int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff,
+                                int nP, int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
+                                unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
+                                hipStream_t stream) {
   if (R <= 0) return 0;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
   const int n = n_cur + n_base;
   if (base == nullptr || n_base <= 0 || n > 256) return (int)hipErrorInvalidValue;
+  if (cache == nullptr || valid == nullptr || T <= 0) cache = nullptr, valid = nullptr;   // (tag 0 means invalid)
+  const int scan = cache != nullptr && expect_miss == 0 ? 1 : 0;
   const int64_t pmax = (R + 3) / 4;
   if (nP <= 0 || nP > pmax) nP = (int)pmax;
+  if (scan && nH <= 0) nH = (int)((R + 255) / 256);
   if (nH <= 0 || nH > R) nH = (int)R;
   // queue: 8 x 32 + 64 zero-initialised uints (the counters are kept zero
   // between launches by the kernel itself); needs at least one history
   // workgroup per XCD range
-  if (queue != nullptr && nH < 8) nH = 8;
+  if (!scan && queue != nullptr && nH < 8) nH = 8;
   const int nq = (T + 3) / 4;
   const dim3 grid((unsigned)(nP + nH)), block(256);
-  const unsigned lds = front_lds();
+  const unsigned lds = scan ? 0u : front_lds();
 #define FM_TF(KK) hipLaunchKernelGGL((tick_front_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS)
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
     constexpr int NV = decltype(nv)::value;
@@ -290,6 +323,14 @@ FM_API int fm_tick_front_rm(const float* hist, int64_t ld_h, int T, int64_t R, f
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
   return 0;
+}
+
+FM_API int fm_tick_front_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
+                            int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
+                            int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
+                            unsigned* queue, const int* rowmap, hipStream_t stream) {
+  return fm_tick_front_cached(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw,
+                              min_wil, min_kru, pvals, pstats, queue, rowmap, nullptr, nullptr, 1, stream);
 }
 
 FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,

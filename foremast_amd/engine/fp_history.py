@@ -224,6 +224,7 @@ def load_history(fp: "FastPath", t: dict, meta: dict, now: float, owns=None) -> 
             if hi > lo:
                 blk = v[:, lo - c0:hi - c0].contiguous().to(st.device)
                 st.buf[torch.as_tensor(rows, device=st.device), lo:hi] = blk
+                st.touch(rows)
             keep_t = np.where(np.isfinite(last_t) & (last_t <= st.t0 + (st.e - 1) * st.step), last_t, -np.inf)
             st.last_t[rows] = keep_t
             st.nfin[rows] = torch.isfinite(st.buf.index_select(0, torch.as_tensor(rows, device=st.device))
@@ -237,6 +238,7 @@ def load_history(fp: "FastPath", t: dict, meta: dict, now: float, owns=None) -> 
             else:
                 full = vd
             st.buf.index_copy_(0, torch.as_tensor(rows, device=st.device), full)
+            st.touch(rows)
             nlen = t[f"{name}.nlen"].numpy()[sel]
             st.nlen[rows] = np.minimum(nlen, st.width)
             st.nfin[rows] = torch.isfinite(vd).sum(1).cpu().numpy()

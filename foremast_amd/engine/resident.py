@@ -56,13 +56,74 @@ def _ceil4(x: int) -> int:
     return (x + 3) // 4 * 4
 
 
+class RowStatsCache:
+    """Per-row (mean, std, n) of a history tensor whose rows are written once
+    and scored many times, kept by the statistics kernels themselves
+    (csrc/include/fm_row_stats.h): ``stats[p]`` are the three floats the
+    kernel computed for physical row ``p``, ``valid[p]`` the view length they
+    were computed for (0 = invalid).  Whoever writes a row clears its word,
+    on the stream of the write (:meth:`touch` / :meth:`invalidate`); the next
+    tick recomputes exactly those rows.
+
+    ``dirty`` is the host's count of words cleared since the last tick.  It
+    only shapes that tick's launch (:meth:`expect_miss`); what is recomputed
+    is decided on the device, word by word."""
+
+    def __init__(self, rows: int, device):
+        self.device = torch.device(device)
+        self.stats = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        self.valid = torch.zeros((rows,), dtype=torch.int32, device=self.device)
+        self.dirty = rows
+        self.T = 0                                  # view length of the last tick
+
+    def __len__(self) -> int:
+        return self.valid.numel()
+
+    def grow(self, rows: int) -> None:
+        """More rows; the existing entries stay (the row data is copied)."""
+        n = len(self)
+        if rows <= n:
+            return
+        stats = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        valid = torch.zeros((rows,), dtype=torch.int32, device=self.device)
+        stats[:n].copy_(self.stats)
+        valid[:n].copy_(self.valid)
+        self.stats, self.valid = stats, valid
+
+    def touch(self, idx: torch.Tensor) -> None:
+        """Rows ``idx`` (int64, on the device) were written on the current stream."""
+        self.valid.index_fill_(0, idx, 0)
+        self.dirty += int(idx.numel())
+
+    def invalidate(self, stream: int | None = None) -> None:
+        """Every row, on ``stream`` (a raw stream handle; default: the current
+        torch stream)."""
+        if self.valid.is_cuda:
+            from ..ops._lib import LIB, ptr, stream_of
+            LIB.call("fm_hist_cache_invalidate", ptr(self.valid), len(self),
+                     stream_of(self.valid) if stream is None else stream)
+        else:
+            self.valid.zero_()
+        self.dirty = max(self.dirty, len(self))
+
+    def expect_miss(self, T: int, rows: int) -> bool:
+        """Whether the tick over ``rows`` rows of a view of length ``T`` should
+        be shaped for streaming history (many misses) rather than for hits."""
+        return self.T != T or self.dirty * 16 > rows
+
+    def ticked(self, T: int) -> None:
+        self.T, self.dirty = T, 0
+
+
 @dataclass
 class HistView:
     """What a scoring launch needs: the buffer view (16-B aligned rows), its
-    leading dimension, the logical history length and the row map."""
+    leading dimension, the logical history length and the row map; for a
+    static store also the row-statistics cache of the buffer."""
     hist: torch.Tensor        # [rows, >= T] view into the resident buffer
     ld: int
     T: int
+    cache: RowStatsCache | None = None
 
 
 class ResidentHistory:
@@ -76,6 +137,9 @@ class ResidentHistory:
         # sliding rows: the window may start up to 3 columns early (aligned view)
         self.width = _ceil4(self.T) if not sliding else _ceil4(self.T + 3) + _ceil4(max(4, slack))
         self.buf = torch.empty((0, self.width), dtype=torch.float32, device=self.device)
+        # static rows are written once and re-scored every cycle: their
+        # statistics are cached per row; a sliding window moves every cycle
+        self.cache = None if sliding else RowStatsCache(0, self.device)
         self.slot: dict = {}
         self.free: list[int] = []
         self.last_t = np.zeros(0, np.float64)       # time of each row's newest sample (-inf: none)
@@ -118,6 +182,8 @@ class ResidentHistory:
         if cap:
             nb[:cap].copy_(self.buf)
         self.buf = nb
+        if self.cache is not None:
+            self.cache.grow(new_cap)
         self.free.extend(range(new_cap - 1, cap - 1, -1))
         self.last_t = np.concatenate([self.last_t, np.full(new_cap - cap, -np.inf)])
         self.nlen = np.concatenate([self.nlen, np.zeros(new_cap - cap, np.int64)])
@@ -199,6 +265,7 @@ class ResidentHistory:
         if rows:
             idx = torch.as_tensor(rows, dtype=torch.int64, device=self.device)
             self.buf.index_fill_(0, idx, float("nan"))
+            self.touch(idx)
             for r in rows:
                 self.keys[r] = None
                 self.kjson[r] = self.ojson[r] = None
@@ -230,15 +297,25 @@ class ResidentHistory:
         src = torch.from_numpy(packed)
         if self.device.type == "cuda":
             src = src.pin_memory().to(self.device, non_blocking=True)
-        self.buf.index_copy_(0, torch.as_tensor(rows, dtype=torch.int64).to(self.device), src)
+        idx = torch.as_tensor(rows, dtype=torch.int64).to(self.device)
+        self.buf.index_copy_(0, idx, src)
+        self.touch(idx)
         self.last_t[rows] = t_last
         self.nlen[rows] = [min(len(v), self.width) for v in values]
         self.nfin[rows] = [int(np.isfinite(np.asarray(v[:self.width], np.float32)).sum()) for v in values]
         self.bytes_in += packed.nbytes
 
+    def touch(self, rows) -> None:
+        """Rows whose data was just written on the current stream: their
+        cached statistics are stale.  Every writer of a static ``buf`` row
+        calls this (write_static, release, the checkpoint restore)."""
+        if self.cache is not None and len(rows):
+            idx = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows), dtype=torch.int64)
+            self.cache.touch(idx.to(self.device))
+
     def view(self) -> HistView:
         if not self.sliding:
-            return HistView(self.buf, self.width, max(1, self.max_len))
+            return HistView(self.buf, self.width, max(1, self.max_len), self.cache)
         vs = max(0, self.ws // 4 * 4)
         return HistView(self.buf[:, vs:], self.width, self.e - vs)
 

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import weakref
 from dataclasses import dataclass
 
 import torch
@@ -40,6 +41,33 @@ class CanaryOutputs:
 MODES = ("front", "fused", "overlap", "serial")
 
 
+class _BoundHist:
+    """A history tensor bound to a launcher for the launcher's life: the strong
+    reference (its address cannot be handed to another tensor while statistics
+    of its rows are cached), the row-statistics cache, and the tensor version
+    the cache was filled under."""
+
+    def __init__(self, hist: torch.Tensor):
+        from .resident import RowStatsCache
+        self.hist = hist
+        self.cache = RowStatsCache(hist.shape[0], hist.device)
+        self.version = hist._version
+
+    def expect_miss(self, T: int, rows: int, stream: int | None) -> bool:
+        """Called before every launch (``stream``: where it goes; None = the
+        current torch stream): a write torch knows of invalidates everything."""
+        v = self.hist._version
+        if v != self.version:
+            self.version = v
+            if rows == len(self.cache):
+                # the streaming launch this forces looks at no word and
+                # rewrites every one of them: nothing to clear ahead of it
+                self.cache.dirty = rows
+            else:
+                self.cache.invalidate(stream)
+        return self.cache.expect_miss(T, rows)
+
+
 class CanaryScorer:
     """``mode`` (GPU only):
 
@@ -60,7 +88,15 @@ class CanaryScorer:
     def __init__(self, aliases: list[str], cfg: BrainConfig | None = None, device="cpu", overlap: bool = True,
                  mode: str | None = None, hist_blocks: int = 0, pw_blocks: int = 0, pw_cap_rows: int = 32,
                  front_wgs: tuple[float, float] | None = None, front_queue: bool = True,
-                 xcd_balance: bool | None = None):
+                 xcd_balance: bool | None = None, hist_cache: bool = True,
+                 front_hot_wgs: tuple[float, float] | None = None):
+        """``hist_cache`` (and env ``FM_HIST_CACHE``, ``0`` = off): keep each
+        history row's (mean, std, n) across ticks where the history has an
+        owner that reports its writes -- a static ``ResidentHistory``
+        (``score_resident``) or the tensor bound by ``split_launchers`` /
+        ``capture_front``.  A tick then reads only the rows written since the
+        previous one; results are the same floats.  See
+        :meth:`invalidate_history` for writers the owner cannot see."""
         self.mode = mode or ("front" if overlap else "serial")
         if self.mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
@@ -89,7 +125,16 @@ class CanaryScorer:
                 self.hist_blocks = 8 * cus
         # front mode: (pairwise, history) workgroups per CU, 0 = one per 4 rows /
         # one per row (tools/tick_breakdown.py SWEEP_FRONT)
+        # (front_wgs shapes the ticks that stream history; a tick whose rows
+        # are all expected in the row-statistics cache has no history stream
+        # to make room for: front_hot_wgs, workgroups per CU again)
         self.front_wgs = front_wgs or (1.0, 4.0)
+        if front_hot_wgs is None:
+            front_hot_wgs = tuple(float(x) for x in os.environ.get("FM_FRONT_HOT_WGS", "5:0.25").split(":"))
+        self.front_hot_wgs = front_hot_wgs
+        self.hist_cache = hist_cache and os.environ.get("FM_HIST_CACHE", "1") != "0"
+        self._bound: dict[int, _BoundHist] = {}            # id(history tensor) -> its cache
+        self._store_caches = weakref.WeakSet()             # caches of resident stores this scorer has ticked
         # dynamic history-row queue (8 per-XCD counters, kept zero between
         # launches by the kernel itself) + the XCD-balance control block
         self._queue = (torch.zeros(8 * 32 + 64, dtype=torch.int32, device=self.device)
@@ -199,7 +244,10 @@ class CanaryScorer:
         ``hview.hist`` in place.  GPU: one role-split front launch when the
         pairwise windows fit a wave-sorted 256 (n_cur + n_base <= 256),
         otherwise history stats || pairwise (<= C.PAIRWISE_MAX on the GPU,
-        wider on the CPU oracle) — then the decision kernel.  Rows are services x M."""
+        wider on the CPU oracle) — then the decision kernel.  Rows are services x M.
+        A view that carries a row-statistics cache (a static store's) has only
+        the rows written since their last tick reduced again; a hand-made
+        ``HistView`` without one streams every row, as does ``hist_cache=False``."""
         R = cur.shape[0]
         has_base = base is not None and base.shape[1] > 0
         if not cur.is_cuda:
@@ -212,16 +260,22 @@ class CanaryScorer:
         o = self._alloc(R, cur.shape[1], slot)
         st = stream_of(cur)
         n = cur.shape[1] + (base.shape[1] if has_base else 0)
+        # a static store's rows keep their statistics between its writes
+        cache = getattr(hview, "cache", None) if self.hist_cache else None
+        miss = True
+        if cache is not None:
+            self._store_caches.add(cache)
+            miss = cache.expect_miss(hview.T, R)
+        c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
         if has_base and n <= 256:
-            fp, fh = self.front_wgs
-            n_p = int(fp * self._cus) if fp > 0 else 0
-            n_h = int(fh * self._cus) if fh > 0 else 0
-            LIB.call("fm_tick_front_rm", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), ptr(cur), cur.stride(0),
-                     cur.shape[1], ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h,
+            n_p, n_h = self._front_grid(miss)
+            LIB.call("fm_tick_front_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), ptr(cur),
+                     cur.stride(0), cur.shape[1], ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h,
                      self.pcfg.min_mann_white, self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals),
-                     ptr(o.pstats), ptr(self._queue), ptr(rowmap), st)
+                     ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid, int(miss), st)
         else:
-            LIB.call("fm_hist_stats_rm", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), 0, ptr(rowmap), st)
+            LIB.call("fm_hist_stats_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), 0, ptr(rowmap),
+                     c_stats, c_valid, int(miss), st)
             if has_base and n <= C.PAIRWISE_MAX:
                 self._pairwise_into(cur, base, o, combine=False)
             elif has_base:
@@ -231,8 +285,47 @@ class CanaryScorer:
                 p, s_, _ = C.pairwise_tests(cur, base, self.pcfg)
                 o.pvals.copy_(p)
                 o.pstats.copy_(s_)
+        if cache is not None:
+            cache.ticked(hview.T)
         self._decide_services(cur, o, has_base)
         return o
+
+    def _front_grid(self, miss: bool) -> tuple[int, int]:
+        """(pairwise, history) workgroups of a front launch: ``front_wgs`` per
+        CU when the tick streams history rows, ``front_hot_wgs`` when every row
+        is expected in the row-statistics cache."""
+        fp, fh = self.front_wgs if miss else self.front_hot_wgs
+        n_p = int(fp * self._cus) if fp > 0 else 0
+        n_h = int(fh * self._cus) if fh > 0 else 0
+        return n_p, (n_h if miss or fh <= 0 else max(1, n_h))
+
+    def _bind(self, hist: torch.Tensor) -> _BoundHist | None:
+        """The row-statistics cache of a history tensor bound to a launcher
+        (one per tensor, shared by the launchers of every slot)."""
+        if not self.hist_cache:
+            return None
+        bh = self._bound.get(id(hist))
+        if bh is None or bh.hist is not hist:
+            bh = self._bound[id(hist)] = _BoundHist(hist)
+        return bh
+
+    def invalidate_history(self) -> None:
+        """Drop every cached row statistic this scorer can reach: the caches of
+        the tensors bound by ``split_launchers`` / ``capture_front`` and of the
+        resident stores it has ticked.  The next tick of each recomputes all
+        rows.
+
+        The caches see a write in two ways only: a ``ResidentHistory`` clears
+        the rows it writes itself, and a bound tensor is watched through
+        torch's version counter.  A write that passes neither -- a raw kernel
+        or a copy through the tensor's pointer, another process through IPC,
+        ``tensor.data`` tricks that do not bump the version -- is a blind
+        spot: whoever does that calls this afterwards, on the stream of the
+        write or after synchronising with it."""
+        for bh in self._bound.values():
+            bh.version = -1                        # invalidated by the next launch, on its own stream
+        for cache in self._store_caches:
+            cache.invalidate()
 
     # -- split tick: front kernel and decision on different streams ----------
     def front_only(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0) -> CanaryOutputs:
@@ -258,17 +351,41 @@ class CanaryScorer:
         return o
 
     def capture_front(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0):
-        """Graph of ``front_only`` for one buffer slot; returns (replay, outputs)."""
+        """Graph of ``front_only`` for one buffer slot; returns (replay, outputs).
+
+        ``hist`` is bound for the life of the replay callable (it holds a
+        reference) and its row statistics are cached: two graphs are captured,
+        one that streams every history row and records it, one that expects
+        every row cached; ``replay`` picks per call.  A change of
+        ``hist._version`` (any torch write) makes the next replay invalidate
+        the cache, with a launch of its own ahead of the graph, and stream the
+        rows again; for writes torch does not see, :meth:`invalidate_history`."""
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)   # warm / allocate
         torch.cuda.synchronize(cur.device)
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(cur.device)
-        s.wait_stream(torch.cuda.current_stream(cur.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self.front_only(hist, base, cur, n_hist, packed_out, slot)
-        torch.cuda.current_stream(cur.device).wait_stream(s)
-        return g.replay, o
+        bh = self._bind(hist)
+        T = hist.shape[1] if n_hist is None else int(n_hist)
+        R = cur.shape[0]
+
+        def capture(body):
+            g = torch.cuda.CUDAGraph()
+            s = torch.cuda.Stream(cur.device)
+            s.wait_stream(torch.cuda.current_stream(cur.device))
+            with torch.cuda.stream(s):
+                with torch.cuda.graph(g, stream=s):
+                    body()
+            torch.cuda.current_stream(cur.device).wait_stream(s)
+            return g
+        if bh is None:
+            return capture(lambda: self.front_only(hist, base, cur, n_hist, packed_out, slot)).replay, o
+        from ..ops._lib import LIB, stream_of
+        graphs = {miss: capture(lambda miss=miss: LIB.call(
+            "fm_tick_front_cached", *self._front_cached_args(bh, base, cur, T, o, miss), stream_of(cur)))
+            for miss in (True, False)}
+
+        def replay() -> None:
+            graphs[bh.expect_miss(T, R, None)].replay()
+            bh.cache.ticked(T)
+        return replay, o
 
     def _decide_services(self, cur, o: CanaryOutputs, has_base: bool) -> None:
         """p-value combine + window decision + service reduce, one launch
@@ -304,6 +421,17 @@ class CanaryScorer:
                 ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white,
                 self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue))
 
+    def _front_cached_args(self, bh: _BoundHist, base, cur, T: int, o: CanaryOutputs, miss: bool) -> tuple:
+        """Arguments of fm_tick_front_cached (all but the stream) over a bound
+        history tensor, for a tick expected to miss / to hit."""
+        from ..ops._lib import ptr
+        hist = bh.hist
+        n_p, n_h = self._front_grid(miss)
+        return (ptr(hist), hist.stride(0), T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1],
+                ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white,
+                self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue), None,
+                ptr(bh.cache.stats), ptr(bh.cache.valid), int(miss))
+
     def split_launchers(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0,
                         front_stream=None, decide_stream=None):
         """Pre-bound launchers of a split tick for one buffer slot: returns
@@ -311,7 +439,14 @@ class CanaryScorer:
         every argument resolved up front (no tensor inspection per tick), on
         the stream given here (default: the current stream at creation).  A
         single-kernel HIP graph buys nothing here: at the 1,250-service shard
-        the graph launch cost 6 % of the step."""
+        the graph launch cost 6 % of the step.
+
+        ``hist`` is bound for the life of the launcher (it holds a reference)
+        and its row statistics are cached: the first launch streams and
+        records every row, later ones read the 12 bytes per row.  A change of
+        ``hist._version`` (any torch write) makes the next launch invalidate
+        the cache on the front stream and stream the rows again; for writes
+        torch does not see, :meth:`invalidate_history`."""
         from ..ops._lib import LIB
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)    # validate / allocate / warm
         torch.cuda.synchronize(cur.device)
@@ -328,6 +463,18 @@ class CanaryScorer:
             rc = f_fn(*f_args)
             if rc:
                 raise RuntimeError(f"fm_tick_front failed with hipError {rc}")
+
+        bh = self._bind(hist)
+        if bh is not None:
+            c_fn, R = lib.fm_tick_front_cached, cur.shape[0]
+            c_args = {miss: self._front_cached_args(bh, base, cur, T, o, miss) + (fs,) for miss in (True, False)}
+            expect, ticked = bh.expect_miss, bh.cache.ticked
+
+            def front() -> None:   # noqa: F811 - the cached form replaces the plain one
+                rc = c_fn(*c_args[expect(T, R, fs)])
+                if rc:
+                    raise RuntimeError(f"fm_tick_front_cached failed with hipError {rc}")
+                ticked(T)
 
         def decide() -> None:
             rc = d_fn(*d_args)

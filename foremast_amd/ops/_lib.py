@@ -116,7 +116,14 @@ _SIGS: dict[str, list] = {
     "fm_tick_front_rm": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                          c_void_p],
+    # fm_tick_front_rm + cache valid expect_miss
+    "fm_tick_front_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
+                             c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_int, c_void_p],
     "fm_hist_stats_rm": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p],
+    "fm_hist_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                             c_void_p],
+    "fm_hist_cache_invalidate": [c_void_p, c_i64, c_void_p],
     "fm_copy_d2h_async": [c_void_p, c_void_p, c_i64, c_void_p],
     "fm_memcpy_sync": [c_void_p, c_void_p, c_i64],
     "fm_board_copy": [c_void_p, c_void_p, c_i64],
