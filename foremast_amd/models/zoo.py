@@ -18,6 +18,8 @@ prophet                         trend+hinges+daily/weekly Fourier LSQ   K10 (f32
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
 multivariate_normal             joint Mahalanobis over all metrics      K12
+robust_moving_average_all       median / MAD over the whole history     K13 + band decide
+robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -42,7 +44,8 @@ from ..ops import lsq as LQ
 from ..ops import smoothing as SM
 
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
-              "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal")
+              "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
+              "robust_moving_average_all", "robust_moving_average")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -52,7 +55,10 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "holt_winters_multiplicative": "holt_winters_multiplicative", "hw_mul": "holt_winters_multiplicative",
            "prophet": "prophet", "lstm": "lstm", "bivariate_normal": "bivariate_normal", "bivariate": "bivariate_normal",
            "multivariate_normal": "multivariate_normal", "multivariate": "multivariate_normal",
-           "mvn": "multivariate_normal"}
+           "mvn": "multivariate_normal",
+           "robust_moving_average_all": "robust_moving_average_all", "median_mad": "robust_moving_average_all",
+           "mad": "robust_moving_average_all", "robust": "robust_moving_average_all",
+           "robust_moving_average": "robust_moving_average", "robust_ma": "robust_moving_average"}
 
 
 def canonical(name: str) -> str:
@@ -135,6 +141,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         dec = C.stats_decide(view, cur, T - start, M, tables.thr, tables.bound, tables.minlb, diff,
                              tables.pair_factor, tables.min_hist)
         return _expand_stats(dec, n)
+    if algo in ROBUST:
+        return _robust(hist, T, robust_start(algo, T, window), cur, horizon, M, tables, diff)
     if algo == "bivariate_normal":
         return _bivariate(hist, T, cur, M, tables, pairs)
     if algo == "multivariate_normal":
@@ -172,6 +180,28 @@ def band(fc: torch.Tensor, sigma: torch.Tensor, horizon: torch.Tensor, cur: torc
     cnt = torch.where(has, cnt, torch.zeros_like(cnt))
     flags = torch.where(has[:, None], flags, torch.zeros_like(flags))
     return RowDecision(up, lo, flags, cnt, sc, valid, center)
+
+
+ROBUST = ("robust_moving_average_all", "robust_moving_average")
+
+
+def robust_start(algo: str, T: int, window: int = 60) -> int:
+    """First history column the robust model ``algo`` reads: 0, or the start
+    of the last ``window`` points (any column: K13 takes unaligned views)."""
+    return 0 if algo == "robust_moving_average_all" else T - min(T, max(1, int(window)))
+
+
+def _robust(hist, T, start, cur, horizon, M, tables, diff) -> RowDecision:
+    """Hampel band: centre = median, sigma = 1.4826 MAD (or its mean-deviation
+    fallback) of the finite history samples in columns [start, T), K13; the
+    existing band decision then applies the per-metric thresholds, bounds and
+    canary factor in those sigma units.  The history gate is the kernel's
+    finite count, not a second pass over the history."""
+    from ..ops import misc as MI
+    center, sigma, nfin = MI.robust_stats(hist[:, start:T], T - start)
+    has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+    valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+    return band(center[:, None], sigma, horizon, cur, M, tables, diff, valid)
 
 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,

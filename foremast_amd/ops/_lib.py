@@ -83,6 +83,8 @@ _SIGS: dict[str, list] = {
     # hist ld T R cur ld_c n rows G K cuts lowered min_n form params dist flags NW count valid stream
     "fm_mvn": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # hist ld T R out stream
+    "fm_robust_stats": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p],
     "fm_hpa_score": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.c_double, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p],

@@ -1,5 +1,6 @@
-"""K5 bivariate normal, K12 multivariate normal, K8 HPA score, K9 downstream impact
-(csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
+"""K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K8 HPA score,
+K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip,
+csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -192,6 +193,66 @@ def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: in
              int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), MVN_FORM, ptr(params), ptr(dist), ptr(flags), NW,
              ptr(cnt), ptr(valid), stream_of(hist))
     return params, dist, flags, cnt, valid
+
+
+# --------------------------------------------------------------------------- K13
+# Longest row the kernel selects in LDS (csrc/kernels/robust_stats.hip
+# kRobustLdsKeys); longer rows take its global-memory path.
+ROBUST_LDS_KEYS = 13312
+
+
+def ref_robust_stats(hist, T: int):
+    """Median / MAD statistics of the finite samples of ``hist[r, :T]`` ->
+    (center [R] f32, sigma [R] f32, n [R] int32), all arithmetic in fp32.
+    With ``s`` the sorted finite samples, ``center = 0.5 s[(n-1)//2] +
+    0.5 s[n//2]``; ``mad`` is the same middle of the sorted ``|x - center|``;
+    ``sigma = 1.4826 mad`` when ``mad > 0``, else ``1.2533 * mean|x - center|``
+    (the mean summed and divided in fp64, rounded once to fp32), which is 0
+    for a constant row only.  ``n == 0`` gives NaN, NaN.  The selection is
+    exact, so the GPU kernel reproduces ``center`` and ``mad`` bit for bit."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    fin = np.isfinite(x)
+    n = fin.sum(1).astype(np.int32)
+    center = np.full(R, np.nan, np.float32)
+    sigma = np.full(R, np.nan, np.float32)
+    if x.shape[1] == 0 or not n.any():
+        return center, sigma, n
+    half = np.float32(0.5)
+    lo = (np.maximum(n, 1) - 1) // 2
+    up = np.maximum(n, 1) // 2
+
+    def middle(v):                                  # missing samples sort last as +inf
+        s = np.sort(np.where(fin, v, np.float32(np.inf)), axis=1)
+        return half * np.take_along_axis(s, lo[:, None], 1)[:, 0] + half * np.take_along_axis(s, up[:, None], 1)[:, 0]
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = middle(x)
+        d = np.abs(x - c[:, None])
+        mad = middle(d)
+        mean_d = (np.where(fin, d, 0).astype(np.float64).sum(1) / np.maximum(n, 1)).astype(np.float32)
+        sg = np.where(mad > 0, np.float32(1.4826) * mad, np.float32(1.2533) * mean_d).astype(np.float32)
+    ok = n > 0
+    center[ok], sigma[ok] = c[ok], sg[ok]
+    return center, sigma, n
+
+
+def robust_stats(hist: torch.Tensor, T: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """K13: per-row (center, sigma, n) of :func:`ref_robust_stats` over
+    ``hist[:, :T]``, by exact selection on the GPU.  ``hist`` may be any
+    column view with unit column stride: rows need 4-byte alignment only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    if not hist.is_cuda:
+        c, s, n = ref_robust_stats(hist.numpy(), T)
+        return torch.from_numpy(c), torch.from_numpy(s), torch.from_numpy(n)
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    out = torch.empty((R, 3), dtype=torch.float32, device=hist.device)
+    if R:
+        LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), int(T), R, ptr(out), stream_of(hist))
+    return out[:, 0], out[:, 1], out[:, 2].to(torch.int32)
 
 
 # --------------------------------------------------------------------------- K8

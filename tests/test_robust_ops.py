@@ -1,0 +1,261 @@
+"""K13 robust statistics (median / MAD by exact selection) and the two zoo
+models built on them: the numpy contract, the contaminated-history case the
+models exist for, and the kernel against the contract on every row type and
+length that takes another path through it."""
+import numpy as np
+import pytest
+import torch
+
+from foremast_amd.config import BrainConfig
+from foremast_amd.models import zoo
+from foremast_amd.ops import canary as C
+from foremast_amd.ops import misc as MI
+
+
+def _ulp(v):
+    return np.spacing(np.abs(np.asarray(v, np.float32))).astype(np.float64)
+
+
+# ------------------------------------------------------------------ contract
+def test_ref_matches_numpy_median_within_2_ulp():
+    """``center`` against the fp64 median of the finite samples and ``mad``
+    against the fp64 median of |x - med|, both within 2 fp32 ulp of the
+    compared value.  With ``med`` the fp64 median that holds where the fp32
+    centre is exact or tiny against the spread (odd n: the centre is a
+    sample; even n about zero): an even-n centre far from zero is rounded by
+    up to half an ulp OF THE CENTRE, many ulp of a small MAD, so those rows
+    take ``med`` = the fp32 centre (the contract's own definition of d)."""
+    rng = np.random.default_rng(3)
+    for loc, scale, T, odd_n, own_center in ((0.0, 1.0, 500, False, False), (0.0, 1.0, 501, False, False),
+                                             (100.0, 5.0, 777, True, False), (100.0, 5.0, 778, False, True),
+                                             (-3e4, 40.0, 64, False, True)):
+        x = (rng.standard_normal((6, T)) * scale + loc).astype(np.float32)
+        x[rng.random(x.shape) < 0.02] = np.nan
+        for r in range(x.shape[0]):
+            if odd_n and np.isfinite(x[r]).sum() % 2 == 0:
+                x[r, np.nonzero(np.isfinite(x[r]))[0][0]] = np.nan
+        c, s, n = MI.ref_robust_stats(x, T)
+        for r in range(x.shape[0]):
+            f = x[r][np.isfinite(x[r])].astype(np.float64)
+            assert n[r] == f.size and (not odd_n or f.size % 2 == 1)
+            med = np.median(f)
+            assert abs(float(c[r]) - med) <= 2 * _ulp(med), (loc, T, r)
+            mad = np.median(np.abs(f - (float(c[r]) if own_center else med)))
+            assert mad > 0
+            want = float(np.float32(1.4826)) * mad            # sigma = 1.4826f * mad, compared in sigma's ulp
+            assert abs(float(s[r]) - want) <= 2 * _ulp(want), (loc, T, r)
+
+
+def test_ref_contract_cases():
+    nan, inf = np.nan, np.inf
+    x = np.full((6, 10), nan, np.float32)
+    x[1, 4] = 7.5                                             # n = 1
+    x[2] = 3.25                                               # constant
+    x[3] = [0, 0, 0, 0, 0, 0, 0, 2, 4, 6]                     # 70 % zeros
+    x[4] = [1, 2, 3, inf, -inf, nan, 4, 5, nan, inf]          # +-inf ignored: 1..5
+    x[5] = [-2, -1, 1, 2, nan, nan, nan, nan, nan, nan]       # even n
+    c, s, n = MI.ref_robust_stats(x, 10)
+    assert c.dtype == np.float32 and s.dtype == np.float32 and n.dtype == np.int32
+    assert n.tolist() == [0, 1, 10, 10, 5, 4]
+    assert np.isnan(c[0]) and np.isnan(s[0])
+    assert c[1] == 7.5 and s[1] == 0
+    assert c[2] == 3.25 and s[2] == 0
+    assert c[3] == 0 and s[3] == np.float32(1.2533) * np.float32(12 / 10) and s[3] > 0
+    assert c[4] == 3 and s[4] == np.float32(1.4826) * np.float32(1)
+    assert c[5] == 0 and s[5] == np.float32(1.4826) * np.float32(1.5)
+    # only the first T columns count
+    c2, s2, n2 = MI.ref_robust_stats(x, 7)
+    assert n2.tolist() == [0, 1, 7, 7, 4, 4] and c2[4] == 2.5 and s2[3] == 0
+    # the op on CPU tensors is the contract
+    tc, ts_, tn = MI.robust_stats(torch.from_numpy(x), 10)
+    assert np.array_equal(tc.numpy(), c, equal_nan=True) and np.array_equal(ts_.numpy(), s, equal_nan=True)
+    assert tn.dtype == torch.int32 and tn.tolist() == n.tolist()
+
+
+# ---------------------------------------------------------------------- zoo
+T_FIX, N_CUR = 2000, 10
+
+
+def _fixture():
+    """8 rows x 2000: N(100, 5); rows 0-5 carry earlier incidents (every 20th
+    sample, 5 %, at 1000), rows 6-7 are clean.  The current window sits inside
+    100 +- 4 except, on the contaminated rows, 160 at point 3 and 130 at
+    point 7."""
+    rng = np.random.default_rng(7)
+    hist = (rng.standard_normal((8, T_FIX)) * 5 + 100).astype(np.float32)
+    hist[:6, 7::20] = 1000.0
+    cur = np.tile(100 + np.linspace(-4, 4, N_CUR, dtype=np.float32), (8, 1))
+    cur[:6, 3] = 160.0
+    cur[:6, 7] = 130.0
+    return hist, cur
+
+
+def _decide(algo, device, hist, cur):
+    cfg = BrainConfig()
+    cfg.threshold = 3.0
+    tables = zoo.make_tables(["requests"] * hist.shape[0], cfg, device)
+    h = torch.from_numpy(hist).to(device)
+    c = torch.from_numpy(cur).to(device)
+    hor = torch.ones(cur.shape, dtype=torch.int64, device=device)
+    dec = zoo.decide(algo, h, hist.shape[1], c, hor, hist.shape[0], tables)
+    return dec, C.unpack_flags(dec.flags, cur.shape[1])
+
+
+def test_contaminated_history_hides_from_mean_std_but_not_from_median_mad():
+    hist, cur = _fixture()
+    dec, flags = _decide("moving_average_all", "cpu", hist, cur)
+    assert not flags.any() and int(dec.count.sum()) == 0
+    assert float(dec.upper[0, 0]) > 600                       # the band the incidents inflated
+    dec, flags = _decide("robust_moving_average_all", "cpu", hist, cur)
+    center, sigma, n = MI.ref_robust_stats(hist, T_FIX)
+    upper = center + np.float32(3.0) * sigma
+    assert np.all(n == T_FIX) and np.all(np.abs(center - 100) < 1) and np.all((sigma > 4) & (sigma < 7))
+    np.testing.assert_allclose(dec.upper.numpy(), np.broadcast_to(upper[:, None], cur.shape), rtol=1e-6)
+    assert np.array_equal(flags, cur > upper[:, None])        # exactly the points above the band
+    want = np.zeros(cur.shape, bool)
+    want[:6, 3] = want[:6, 7] = True
+    assert np.array_equal(flags, want)                        # 160 and 130 on the dirty rows, nothing on the clean
+    assert dec.count.tolist() == [2] * 6 + [0] * 2 and dec.valid.tolist() == [3] * 8
+
+
+def test_robust_window_and_history_gate():
+    hist, cur = _fixture()
+    dec, flags = _decide("robust_moving_average", "cpu", hist, cur)
+    center, sigma, n = MI.ref_robust_stats(hist[:, -60:], 60)
+    np.testing.assert_allclose(dec.upper.numpy()[:, 0], center + np.float32(3.0) * sigma, rtol=1e-6)
+    assert flags[:6, 3].all() and not flags[6:].any()
+    # fewer finite samples than MIN_HISTORICAL_DATA_POINT_TO_MEASURE: no verdict, bit 0 clear
+    hist[1, 5:] = np.nan
+    dec, flags = _decide("robust_moving_average_all", "cpu", hist, cur)
+    assert dec.valid.tolist() == [3, 2] + [3] * 6 and not flags[1].any() and int(dec.count[1]) == 0
+
+
+def test_aliases_and_config():
+    for a in ("robust_moving_average_all", "median_mad", "mad", "robust", " Robust "):
+        assert zoo.canonical(a) == "robust_moving_average_all"
+    for a in ("robust_moving_average", "robust_ma"):
+        assert zoo.canonical(a) == "robust_moving_average"
+    assert {"robust_moving_average_all", "robust_moving_average"} <= set(zoo.ALGORITHMS)
+    with pytest.raises(ValueError):
+        zoo.canonical("robust_median")
+    cfg = BrainConfig.from_env({"ML_ALGORITHM": "robust_moving_average_all", "metric_type_threshold_count": "1",
+                                "metric_type0": "latency", "threshold0": "4", "ml_algorithm0": "robust_ma"})
+    assert zoo.canonical(cfg.algorithm_for("cpu")) == "robust_moving_average_all"
+    assert zoo.canonical(cfg.algorithm_for("latency")) == "robust_moving_average"
+
+
+# ---------------------------------------------------------------------- GPU
+NTYPES = 12
+
+
+def _row(kind, T, rng):
+    """One history row of length T of the given type (see the list in
+    ``test_gpu_robust_stats_matches_oracle``)."""
+    nan, inf = np.nan, np.inf
+    x = np.full(T, nan, np.float32)
+    if kind == 0:                                             # all missing
+        return x
+    if kind == 1:                                             # one finite sample
+        x[rng.integers(T)] = -12.5
+        return x
+    if kind == 2:                                             # constant
+        x[:] = 42.0
+        return x
+    if kind == 3:                                             # > 50 % zeros: the MAD = 0 fallback
+        x[:] = np.where(rng.random(T) < 0.7, 0.0, rng.exponential(3.0, T))
+        return x
+    if kind == 4:                                             # heavy ties
+        return rng.integers(0, 4, T).astype(np.float32)
+    if kind == 5:                                             # all negative
+        return (-np.abs(rng.standard_normal(T)) * 50 - 1).astype(np.float32)
+    if kind == 6:                                             # mixed sign
+        return (rng.standard_normal(T) * 3).astype(np.float32)
+    if kind == 7:                                             # -0.0 next to +0.0 around the middle
+        x[:] = np.where(rng.random(T) < 0.5, -0.0, 0.0)
+        k = T // 5
+        x[:k], x[T - k:] = -1.5, 2.5
+        return rng.permutation(x)
+    if kind == 8:                                             # missing values of every kind, also at both ends
+        x[:] = rng.standard_normal(T) * 5 + 100
+        x[rng.random(T) < 0.2] = nan
+        x[rng.random(T) < 0.05] = inf
+        x[rng.random(T) < 0.05] = -inf
+        x[0], x[-1] = nan, -inf
+        return x
+    if kind == 9:                                             # 1e30 and 1e-30 in one row
+        x[:] = np.where(rng.random(T) < 0.5, 1e30, 1e-30) * rng.choice([-1.0, 1.0], T) * rng.uniform(1, 2, T)
+        return x
+    if kind == 10:                                            # differ in the last mantissa bits only
+        return (np.float32(1.0).view(np.uint32) + rng.integers(0, 4, T).astype(np.uint32)).view(np.float32)
+    # even n whose two middle samples differ in the top byte of the key: half below zero, half above
+    v = np.concatenate([-(1 + rng.random(T // 2)), 1 + rng.random(T // 2)]).astype(np.float32)
+    x[:v.size] = v                                            # an odd T leaves one missing sample
+    return rng.permutation(x)
+
+
+def _batch(R, T, seed):
+    rng = np.random.default_rng(seed)
+    off = 6 if R == 1 else 0
+    return np.stack([_row((r + off) % NTYPES, T, rng) for r in range(R)])
+
+
+def _mad(x, c):
+    """fp32 MAD of one row about the fp32 centre c (which branch sigma took)."""
+    f = x[np.isfinite(x)]
+    if f.size == 0:
+        return np.float32(np.nan)
+    d = np.sort(np.abs(f - np.float32(c)))
+    return np.float32(0.5) * d[(f.size - 1) // 2] + np.float32(0.5) * d[f.size // 2]
+
+
+def _check(got, x, T, what):
+    c, s, n = (t.cpu().numpy() for t in got)
+    rc, rs, rn = MI.ref_robust_stats(x, T)
+    assert np.array_equal(n, rn), what
+    assert np.array_equal(c, rc, equal_nan=True), (what, np.nonzero(~((c == rc) | (np.isnan(c) & np.isnan(rc))))[0])
+    with np.errstate(invalid="ignore"):
+        exact = np.array([_mad(x[r, :T], rc[r]) > 0 for r in range(x.shape[0])])
+    assert np.array_equal(s[exact], rs[exact]), (what, np.nonzero(exact & (s != rs))[0])
+    rest = ~exact & (rn > 0)
+    np.testing.assert_allclose(s[rest], rs[rest], rtol=1e-6, atol=0, err_msg=str(what))
+    assert np.isnan(s[rn == 0]).all(), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,R", [(1, 37), (2, 37), (3, 37), (63, 37), (64, 37), (65, 37), (255, 37), (256, 37),
+                                 (257, 37), (1000, 37), (4099, 37), (10080, 37), (MI.ROBUST_LDS_KEYS + 3, 5),
+                                 (1000, 1), (257, 700)])
+def test_gpu_robust_stats_matches_oracle(cuda, T, R):
+    """Kernel == contract: centre and n equal as floats (-0 == +0), sigma equal
+    where MAD > 0 and within rtol 1e-6 on the fp64-mean fallback.  Rows cycle
+    through: all-NaN, single finite, constant, > 50 % zeros, integers 0..3,
+    all-negative, mixed sign, -0.0 / +0.0, NaN and +-inf scattered (first and
+    last position too), 1e30 with 1e-30, last-mantissa-bit differences, and an
+    even-n row whose middles differ in the key's top byte.  Each batch also
+    runs with ld > T and 1e9 past column T, and on a view that starts at
+    column 1 of an odd-stride buffer (4-byte alignment only, every peel)."""
+    x = _batch(R, T, 100 + T)
+    _check(MI.robust_stats(torch.from_numpy(x).to(cuda), T), x, T, ("dense", T, R))
+    wide = np.full((R, T + 5), 1e9, np.float32)
+    wide[:, :T] = x
+    _check(MI.robust_stats(torch.from_numpy(wide).to(cuda), T), x, T, ("ld > T", T, R))
+    ld = T + 2 + (T + 1) % 2                                    # odd stride: row starts at every 4-byte phase
+    buf = np.full((R, ld), 1e9, np.float32)
+    buf[:, 1:1 + T] = x
+    view = torch.from_numpy(buf).to(cuda)[:, 1:]
+    assert view.data_ptr() % 16 == 4 and view.stride(0) % 2 == 1
+    _check(MI.robust_stats(view, T), x, T, ("view", T, R))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("algo", ["robust_moving_average_all", "robust_moving_average"])
+def test_gpu_robust_zoo_equals_cpu_zoo(cuda, algo):
+    hist, cur = _fixture()
+    hist[7, 40:] = np.nan                                     # a short row: 40 samples in all, none in the window
+    a, fa = _decide(algo, "cpu", hist, cur)
+    b, fb = _decide(algo, cuda, hist, cur)
+    assert fa[:6, 3].all()
+    assert np.array_equal(fa, fb)
+    for k in ("upper", "lower"):
+        np.testing.assert_allclose(getattr(b, k).cpu().numpy(), getattr(a, k).numpy(), rtol=1e-6, err_msg=k)
+    assert b.count.cpu().tolist() == a.count.tolist() and b.valid.cpu().tolist() == a.valid.tolist()
