@@ -10,159 +10,22 @@
 // LDS does not matter to a selection: the aligned body is stored first and
 // the peeled head / tail elements behind it.
 //
-// Selection: the block's min and max key give the leading bits every finite
-// key shares; below them, passes of up to 11 bits histogram the matching keys
-// into 2,048 LDS bins (atomics; the lanes of a wave that share its first
-// digit make one add), wave 0 scans the bins to the one holding rank k, and
-// the prefix grows until all 32 bits are known.  For even n the upper middle is the same
-// value when the last bin still holds rank k + 1, else the smallest key above.
-// Phase two overwrites the keys with the bits of |x - centre| (non-negative
-// floats are monotone as they are), sums them in fp64 and selects again.
+// The keys and the selection (MSB-first radix passes of up to 11 bits over
+// 2,048 LDS bins) are fm_radix_select.h, shared with K14.  Phase two
+// overwrites the keys with the bits of |x - centre| (non-negative floats are
+// monotone as they are), sums them in fp64 and selects again.
 //
 // Rows longer than the LDS capacity run the same passes re-reading global
 // memory (no limit on T; not a fast path).  The contract is
 // foremast_amd/ops/misc.py ref_robust_stats; centre and MAD are exact.
 #include "fm_common.h"
+#include "fm_radix_select.h"
 
 using namespace fm;
 
 namespace {
 
 constexpr int kRobustThreads = 512;
-constexpr int kDigitBits = 11;                 // bits settled per pass: three passes cover a key
-constexpr int kBins = 1 << kDigitBits;
-constexpr int kBinsPerLane = kBins / FM_WAVE;  // wave 0 scans the bins, a run of them per lane
-static_assert(kBinsPerLane % 4 == 0, "a lane's bins are read as uint4");
-// The fast path's longest row: 52 KiB of keys, so that a workgroup's LDS (keys,
-// 8 KiB of bins, reduction scratch) stays under the 64 KiB a launch gets
-// without a raised limit.  foremast_amd/ops/misc.py ROBUST_LDS_KEYS mirrors it.
-constexpr int kRobustLdsKeys = 13312;
-constexpr unsigned kMissing = 0xFFFFFFFFu;
-
-__device__ __forceinline__ unsigned enc_key(float x) {
-  const unsigned b = __float_as_uint(x);
-  if ((b & 0x7F800000u) == 0x7F800000u) return kMissing;   // NaN, +-inf
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_key(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-// key of the deviation |x - c| of the sample with key k
-__device__ __forceinline__ unsigned dev_key(unsigned k, float c) {
-  return k == kMissing ? kMissing : __float_as_uint(fabsf(dec_key(k) - c));
-}
-
-template <int NT>
-__device__ __forceinline__ unsigned block_min_u32(unsigned v, unsigned* scratch) {
-  v = wave_min(v);
-  if (lane_id() == 0) scratch[wave_id()] = v;
-  __syncthreads();
-  unsigned r = scratch[0];
-#pragma unroll
-  for (int w = 1; w < NT / FM_WAVE; ++w) r = r < scratch[w] ? r : scratch[w];
-  __syncthreads();
-  return r;
-}
-
-// The keys of one row: the LDS copy (LDS) or the row in global memory, encoded
-// on the way (phase two: as deviations from the centre c).
-template <int NT, bool LDS>
-struct RowKeys {
-  const float* p;
-  int T;
-  uint4* k4;
-  int nq;
-  bool dev;
-  float c;
-  template <class F>
-  __device__ __forceinline__ void sweep(F f) const {
-    if constexpr (LDS) {
-      for (int q = threadIdx.x; q < nq; q += NT) {
-        const uint4 v = k4[q];
-        f(v.x); f(v.y); f(v.z); f(v.w);
-      }
-    } else {
-      for (int i = threadIdx.x; i < T; i += NT) {
-        unsigned k = enc_key(p[i]);
-        if (dev) k = dev_key(k, c);
-        f(k);
-      }
-    }
-  }
-};
-
-// Key of rank k (0-based) among the n finite keys, all within [kmin, kmax].
-// cnt = how many keys equal it, resid = rank k inside that run.  bins[kBins]
-// is zero on entry and on return.
-template <int NT, bool LDS>
-__device__ __forceinline__ unsigned radix_select(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned k,
-                                                 unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
-                                                 unsigned& cnt) {
-  int hi = kmin == kmax ? 32 : __clz(kmin ^ kmax);            // leading bits shared by every finite key
-  unsigned pref = hi == 0 ? 0u : (hi == 32 ? kmin : (kmin & (~0u << (32 - hi))));
-  cnt = n;
-  while (hi < 32) {
-    const int w = 32 - hi < kDigitBits ? 32 - hi : kDigitBits, shift = 32 - hi - w;
-    const unsigned mask = hi == 0 ? 0u : (~0u << (32 - hi)), dm = (1u << w) - 1u;
-    rk.sweep([&](unsigned key) {
-      const bool m = ((key ^ pref) & mask) == 0u;
-      const unsigned d = (key >> shift) & dm;
-      const unsigned long long act = __ballot(m);
-      if (act == 0ull) return;
-      // the lanes that share the first matching lane's digit make one add (a
-      // row of ties would serialise 64 adds on one bin); the rest add singly
-      const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
-      const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, leader);
-      const bool same = m && d == d0;
-      const unsigned long long grp = __ballot(same);
-      if (lane_id() == leader) atomicAdd(&bins[d0], (unsigned)__popcll(grp));
-      else if (m && !same) atomicAdd(&bins[d], 1u);
-    });
-    __syncthreads();
-    if (wave_id() == 0) {
-      const int l = lane_id();
-      unsigned* mine = bins + l * kBinsPerLane;
-      unsigned s = 0u;
-#pragma unroll
-      for (int j = 0; j < kBinsPerLane / 4; ++j) {
-        const uint4 c = reinterpret_cast<const uint4*>(mine)[j];
-        s += c.x + c.y + c.z + c.w;
-      }
-      const unsigned inc = wave_incl_sum(s), exc = inc - s;
-      if (exc <= k && k < inc) {                               // one lane: the missing keys sort last
-        unsigned r = k - exc, b = 0u, cc = mine[0];
-        while (r >= cc) { r -= cc; ++b; cc = mine[b]; }
-        sel[0] = pref | (((unsigned)(l * kBinsPerLane) + b) << shift);
-        sel[1] = r;
-        sel[2] = cc;
-      }
-#pragma unroll
-      for (int j = 0; j < kBinsPerLane / 4; ++j) reinterpret_cast<uint4*>(mine)[j] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __syncthreads();
-    pref = sel[0];
-    k = sel[1];
-    cnt = sel[2];
-    hi += w;
-  }
-  resid = k;
-  return pref;
-}
-
-// Lower and upper middle keys of the n finite keys.
-template <int NT, bool LDS>
-__device__ __forceinline__ void select_middles(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned n,
-                                               unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
-                                               unsigned& up) {
-  unsigned resid, cnt;
-  lo = radix_select<NT, LDS>(rk, kmin, kmax, (n - 1u) >> 1, n, bins, sel, resid, cnt);
-  up = lo;
-  if ((n & 1u) == 0u && resid + 1u >= cnt) {                   // the run of lo ends at the lower middle
-    unsigned above = kMissing;
-    rk.sweep([&](unsigned key) { if (key > lo && key < above) above = key; });
-    up = block_min_u32<NT>(above, redu);
-  }
-}
 
 template <int NT, bool LDS>
 __global__ __launch_bounds__(NT) void robust_stats_kernel(const float* __restrict__ hist, int64_t ld, int T, int64_t R,

@@ -67,6 +67,10 @@ class BrainConfig:
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
+    # seasonal_robust: period in samples (0 = one day at the brain's step, < 0 = detect from the history)
+    # and the half width of the profile's smoothing window in phases
+    seasonal_period: int = 0                 # SEASONAL_PERIOD
+    seasonal_smooth: int = 5                 # SEASONAL_SMOOTH
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -133,6 +137,14 @@ class BrainConfig:
                 return r
         return MetricRule(self.threshold, self.bound, self.min_lower_bound)
 
+    def seasonal_period_for(self, step: float) -> int | None:
+        """Period of ``seasonal_robust`` in samples of spacing ``step`` seconds:
+        ``SEASONAL_PERIOD`` when positive, one day when 0, None (detect it from
+        the history) when negative."""
+        if self.seasonal_period > 0:
+            return self.seasonal_period
+        return None if self.seasonal_period < 0 else max(1, int(round(86400.0 / step)))
+
     def mvn_threshold(self) -> float:
         return self.threshold if self.multivariate_threshold is None else self.multivariate_threshold
 
@@ -170,6 +182,8 @@ class BrainConfig:
         c.pairwise_threshold_factor = _f(env, "ML_PAIRWISE_THRESHOLD_FACTOR", c.pairwise_threshold_factor)
         if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
+        c.seasonal_period = _i(env, "SEASONAL_PERIOD", c.seasonal_period)
+        c.seasonal_smooth = _i(env, "SEASONAL_SMOOTH", c.seasonal_smooth)
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

@@ -274,7 +274,7 @@ class Brain(BrainStateMixin):
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
                              pairs=pairs, cache=self._cache_ctx(rows, algo),
                              groups=self._groups(rows) if algo == "multivariate_normal" else None,
-                             mvn_threshold=self.cfg.mvn_threshold())
+                             mvn_threshold=self.cfg.mvn_threshold(), **self._seasonal_args(algo))
             out = {k: getattr(dec, k).detach().cpu().numpy() for k in keys}
             flags = dec.flags
         else:
@@ -290,7 +290,7 @@ class Brain(BrainStateMixin):
                                  lstm_model=self._lstm_for(sub) if algo == "lstm" else self.lstm_model,
                                  pairs=pairs, cache=self._cache_ctx(sub, algo),
                                  groups=self._groups(sub) if algo == "multivariate_normal" else None,
-                                 mvn_threshold=self.cfg.mvn_threshold())
+                                 mvn_threshold=self.cfg.mvn_threshold(), **self._seasonal_args(algo))
                 for k in keys:
                     v = getattr(dec, k).detach()
                     if k not in out:
@@ -306,6 +306,14 @@ class Brain(BrainStateMixin):
         out["flags"] = C.unpack_flags(flags, cur.shape[1])
         out["diff"] = None if diff is None else diff.cpu().numpy()
         return out
+
+    def _seasonal_args(self, algorithm: str) -> dict:
+        """``period`` / ``smooth`` of a zoo call: SEASONAL_PERIOD and
+        SEASONAL_SMOOTH for ``seasonal_robust``, nothing for any other model
+        (Holt-Winters keeps detecting its period)."""
+        if zoo.canonical(algorithm) != "seasonal_robust":
+            return {}
+        return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -836,7 +844,8 @@ class Brain(BrainStateMixin):
         try:
             fc, _ = zoo.forecast(self.cfg.hpa_forecast_algorithm, h, T, max(1, self.cfg.hpa_forecast_steps),
                                  lstm_model=self.lstm_model,
-                                 cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm))
+                                 cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm),
+                                 **self._seasonal_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

@@ -613,6 +613,10 @@ class ModelsMixin:
                                       sub.T, H)
         elif algo == "lstm":
             hist = lazy.materialize(sub.T - min(lstm.L, sub.T))
+        elif algo == "seasonal_robust":
+            # only the span of whole cycles is gathered: the model reads no column before it
+            kw = b._seasonal_args(algo)
+            return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
         else:
             hist = lazy.materialize(0)
         return zoo.forecast(algo, hist, sub.T, H, lstm_model=lstm, cache=ctx)

@@ -20,6 +20,7 @@ bivariate_normal                Mahalanobis over metric pairs           K5
 multivariate_normal             joint Mahalanobis over all metrics      K12
 robust_moving_average_all       median / MAD over the whole history     K13 + band decide
 robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
+seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -45,7 +46,7 @@ from ..ops import smoothing as SM
 
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
-              "robust_moving_average_all", "robust_moving_average")
+              "robust_moving_average_all", "robust_moving_average", "seasonal_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -58,7 +59,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "mvn": "multivariate_normal",
            "robust_moving_average_all": "robust_moving_average_all", "median_mad": "robust_moving_average_all",
            "mad": "robust_moving_average_all", "robust": "robust_moving_average_all",
-           "robust_moving_average": "robust_moving_average", "robust_ma": "robust_moving_average"}
+           "robust_moving_average": "robust_moving_average", "robust_ma": "robust_moving_average",
+           "seasonal_robust": "seasonal_robust", "seasonal_median": "seasonal_robust",
+           "seasonal_mad": "seasonal_robust", "robust_seasonal": "seasonal_robust"}
 
 
 def canonical(name: str) -> str:
@@ -122,7 +125,7 @@ def _valid(hist: torch.Tensor, T: int, cur: torch.Tensor, min_hist: int) -> torc
 def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizon: torch.Tensor, M: int,
            tables: Tables, diff: torch.Tensor | None = None, window: int = 60, period: int | None = None,
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
-           groups=None, mvn_threshold: float | None = None) -> RowDecision:
+           groups=None, mvn_threshold: float | None = None, smooth: int = 5) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -162,7 +165,13 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (fit.nfin.to(cur.device) >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fit.forecast, fit.sigma, horizon, cur, M, tables, diff, valid)
-    fc, sigma = forecast(algo, hist, T, H, period=period, lstm_model=lstm_model, cache=cache)
+    if algo == "seasonal_robust":
+        # the kernel counts the finite samples it models: no separate history pass
+        fc, sigma, nfin = _seasonal_robust(hist, T, H, period, smooth)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    fc, sigma = forecast(algo, hist, T, H, period=period, lstm_model=lstm_model, cache=cache, smooth=smooth)
     return band(fc, sigma, horizon, cur, M, tables, diff, _valid(hist, T, cur, tables.min_hist))
 
 
@@ -206,11 +215,36 @@ def _robust(hist, T, start, cur, horizon, M, tables, diff) -> RowDecision:
 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
-FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm")
+FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust")
+
+
+def seasonal_start(T: int, period: int | None) -> int:
+    """First history column ``seasonal_robust`` reads when ``period`` is given:
+    the start of its span of whole cycles, or 0 when it falls back to the
+    whole-history median (and when the period is still to be detected)."""
+    from ..ops import misc as MI
+    J = MI.seasonal_cycles(T, period) if period else 0
+    return T - J * int(period) if J >= 2 else 0
+
+
+def _seasonal_robust(hist, T, H, period, smooth):
+    """Per-phase median profile over the last whole cycles of the history and
+    the MAD-sigma of the residuals about it, K14 -> (forecast [R, H], sigma
+    [R], finite count [R]).  ``period`` None: detected from the history.  A
+    history shorter than two periods, or a period too long for the kernel's
+    budget, falls back to a constant forecast of the whole-history median with
+    K13's sigma (as Holt-Winters falls back to Holt)."""
+    from ..ops import misc as MI
+    m = int(period or _detect_period(hist, T))
+    if MI.seasonal_cycles(T, m) >= 2:
+        return MI.seasonal_robust(hist, T, m, H, smooth)
+    center, sigma, nfin = MI.robust_stats(hist, T)
+    return center[:, None].expand(-1, H), sigma, nfin
 
 
 def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | None = None,
-             lstm_model=None, cache: CacheContext | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+             lstm_model=None, cache: CacheContext | None = None,
+             smooth: int = 5) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]).  Used by the
     band decision and, for HPA jobs, to publish the load forecast a cluster
@@ -237,6 +271,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
             from .lstm import LSTMForecaster
             lstm_model = LSTMForecaster.default(device=hist.device)
         return lstm_model.forecast(hist, T, H)
+    if algo == "seasonal_robust":
+        return _seasonal_robust(hist, T, H, period, smooth)[:2]
     raise ValueError(f"{algorithm!r} is not a forecasting model ({', '.join(FORECASTERS)})")
 
 

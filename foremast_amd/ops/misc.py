@@ -1,6 +1,7 @@
-"""K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K8 HPA score,
-K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip,
-csrc/kernels/hpa_graph.hip) with numpy references."""
+"""K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K14 seasonal robust
+model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
+csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip, csrc/kernels/hpa_graph.hip) with numpy
+references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -253,6 +254,107 @@ def robust_stats(hist: torch.Tensor, T: int) -> tuple[torch.Tensor, torch.Tensor
     if R:
         LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), int(T), R, ptr(out), stream_of(hist))
     return out[:, 0], out[:, 1], out[:, 2].to(torch.int32)
+
+
+# --------------------------------------------------------------------------- K14
+# Most cycles the seasonal model reads (csrc/kernels/seasonal_robust.hip kMaxCycles).
+SEASONAL_MAX_CYCLES = 16
+
+
+def seasonal_cycles(T: int, m: int) -> int:
+    """Whole cycles J of period ``m`` the seasonal robust model reads from a
+    history of ``T`` samples: its span is the last ``J * m`` columns.  At most
+    16 cycles, and the span plus two ``m``-word profile buffers fit K13's LDS
+    budget.  The model is seasonal when ``J >= 2``."""
+    T, m = int(T), int(m)
+    if m < 1:
+        return 0
+    return max(0, min(T // m, SEASONAL_MAX_CYCLES, ROBUST_LDS_KEYS // m - 2))
+
+
+def seasonal_halfwidth(m: int, smooth: int = 5) -> int:
+    """Half width k of the smoothing window: ``smooth`` phases each side, but
+    the window stays about a twelfth of the period (``m // 24`` each side)."""
+    return max(0, min(int(smooth), int(m) // 24))
+
+
+def ref_seasonal_robust(hist, T: int, m: int, H: int, smooth: int = 5):
+    """Per-phase median / MAD model of ``hist[r, :T]`` with period ``m`` ->
+    (forecast [R, H] f32, sigma [R] f32, n [R] int32, profile [R, m] f32).
+
+    The span is the last ``J * m`` columns (:func:`seasonal_cycles`); span
+    index ``i`` has phase ``i % m``.  ``raw[p]`` is K13's median rule over the
+    finite samples of phase ``p`` (NaN when it has none); ``profile[p]`` the
+    mean of the finite ``raw[(p + d) % m]``, ``d = -k..k``
+    (:func:`seasonal_halfwidth`), summed in that order and divided in fp64,
+    rounded once to fp32.  ``mad`` is K13's middle of the sorted residuals
+    ``|x - profile[phase]|`` of the ``n`` finite samples, with no re-centring;
+    ``sigma = 1.4826 mad`` when ``mad > 0``, else ``1.2533 * mean residual``
+    (fp64, rounded once); ``n == 0`` gives NaN.  ``forecast[:, h - 1] =
+    profile[(h - 1) % m]``: the phase after the last sample is phase 0."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    m, H = int(m), int(H)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    k = seasonal_halfwidth(m, smooth)
+    span = x[:, T - J * m:T]
+    fin = np.isfinite(span)
+    n = fin.sum(1).astype(np.int32)
+    half, inf = np.float32(0.5), np.float32(np.inf)
+
+    def middle(v, ok, cnt, axis):                   # missing samples sort last as +inf
+        s = np.sort(np.where(ok, v, inf), axis=axis)
+        lo = np.expand_dims((np.maximum(cnt, 1) - 1) // 2, axis)
+        up = np.expand_dims(np.maximum(cnt, 1) // 2, axis)
+        return (half * np.take_along_axis(s, lo, axis) + half * np.take_along_axis(s, up, axis)).squeeze(axis)
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        fin3 = fin.reshape(R, J, m)
+        c = fin3.sum(1)
+        raw = np.where(c > 0, middle(span.reshape(R, J, m), fin3, c, 1), np.float32(np.nan)).astype(np.float32)
+        tot = np.zeros((R, m), np.float64)
+        cnt = np.zeros((R, m), np.int64)
+        for d in range(-k, k + 1):
+            nb = np.roll(raw, -d, axis=1)           # nb[:, p] = raw[:, (p + d) % m]
+            ok = np.isfinite(nb)
+            tot += np.where(ok, nb, 0).astype(np.float64)
+            cnt += ok
+        profile = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan).astype(np.float32)
+        r = np.abs(span - np.tile(profile, (1, J)))
+        mad = middle(r, fin, n, 1)
+        mean_r = (np.where(fin, r, 0).astype(np.float64).sum(1) / np.maximum(n, 1)).astype(np.float32)
+        sigma = np.where(mad > 0, np.float32(1.4826) * mad, np.float32(1.2533) * mean_r).astype(np.float32)
+    sigma[n == 0] = np.nan
+    forecast = np.ascontiguousarray(profile[:, np.arange(H) % m])
+    return forecast, sigma, n, profile
+
+
+def seasonal_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: int = 5, want_profile: bool = False):
+    """K14: (forecast [R, H], sigma [R], n [R] int32) of :func:`ref_seasonal_robust`
+    over ``hist[:, :T]``, and the profile [R, m] behind them when
+    ``want_profile``.  ``hist`` may be any column view with unit column
+    stride: rows need 4-byte alignment only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, m, H = int(T), int(m), int(H)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    check(H >= 0, "H must be >= 0")
+    if not hist.is_cuda:
+        out = tuple(torch.from_numpy(a) for a in ref_seasonal_robust(hist.numpy(), T, m, H, smooth))
+        return out if want_profile else out[:3]
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    fc = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    stats = torch.empty((R, 2), dtype=torch.float32, device=hist.device)
+    prof = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    if R:
+        LIB.call("fm_seasonal_robust", ptr(hist), hist.stride(0), T, R, m, J, seasonal_halfwidth(m, smooth), H,
+                 ptr(fc), max(H, 1), ptr(stats), ptr(prof), stream_of(hist))
+    out = (fc, stats[:, 0], stats[:, 1].to(torch.int32))
+    return out + (prof,) if want_profile else out
 
 
 # --------------------------------------------------------------------------- K8
