@@ -1,7 +1,8 @@
 // Exact order statistics of one row held by a workgroup: order-preserving
 // uint32 keys and an MSB-first radix selection over them.  Shared by K13
-// (robust_stats.hip: median and MAD of a row) and K14 (seasonal_robust.hip:
-// MAD of the residuals about a per-phase median profile).
+// (robust_stats.hip: median and MAD of a row), K14 (seasonal_robust.hip: MAD
+// of the residuals about a per-phase median profile) and K15 (level_shift.hip:
+// medians of the blocks of a row and of the segment behind a level shift).
 //
 // Keys: negatives have all bits flipped, non-negatives get the sign bit set.
 // NaN / +-inf become the key 0xFFFFFFFF, which no finite value maps to and
@@ -82,13 +83,43 @@ struct RowKeys {
   }
 };
 
+// A run of keys in LDS with key i at word i: the words [lo, hi) of kw, any
+// bounds (K15: the row sits at its global alignment, and a block of it or the
+// segment behind a level shift starts at any word).  The sweep reads whole
+// quads and masks the words outside the run as missing, so every lane of a
+// wave stays in it together.  dev: the keys are taken as deviations from c
+// on the fly, which leaves the raw keys in place for a later selection.
+template <int NT>
+struct SpanKeys {
+  const unsigned* kw;
+  int lo, hi;
+  bool dev;
+  float c;
+  template <class F>
+  __device__ __forceinline__ void sweep(F f) const {
+    const uint4* k4 = reinterpret_cast<const uint4*>(kw);
+    for (int q = (lo >> 2) + (int)threadIdx.x, qe = (hi + 3) >> 2; q < qe; q += NT) {
+      const uint4 v = k4[q];
+      const unsigned e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int w = 4 * q + j;
+        unsigned k = (w >= lo && w < hi) ? e[j] : kMissing;
+        if (dev) k = dev_key(k, c);
+        f(k);
+      }
+    }
+  }
+};
+
 // Key of rank k (0-based) among the n finite keys, all within [kmin, kmax].
 // cnt = how many keys equal it, resid = rank k inside that run.  bins[kBins]
-// is zero on entry and on return.
-template <int NT, bool LDS>
-__device__ __forceinline__ unsigned radix_select(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned k,
-                                                 unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
-                                                 unsigned& cnt) {
+// is zero on entry and on return.  Keys is any source with a sweep(f) that
+// hands every key to f, the lanes of a wave together.
+template <int NT, class Keys>
+__device__ __forceinline__ unsigned radix_select_keys(const Keys& rk, unsigned kmin, unsigned kmax, unsigned k,
+                                                      unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
+                                                      unsigned& cnt) {
   int hi = kmin == kmax ? 32 : __clz(kmin ^ kmax);            // leading bits shared by every finite key
   unsigned pref = hi == 0 ? 0u : (hi == 32 ? kmin : (kmin & (~0u << (32 - hi))));
   cnt = n;
@@ -140,19 +171,32 @@ __device__ __forceinline__ unsigned radix_select(const RowKeys<NT, LDS>& rk, uns
   return pref;
 }
 
-// Lower and upper middle keys of the n finite keys.
 template <int NT, bool LDS>
-__device__ __forceinline__ void select_middles(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned n,
-                                               unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
-                                               unsigned& up) {
+__device__ __forceinline__ unsigned radix_select(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned k,
+                                                 unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
+                                                 unsigned& cnt) {
+  return radix_select_keys<NT>(rk, kmin, kmax, k, n, bins, sel, resid, cnt);
+}
+
+// Lower and upper middle keys of the n finite keys.
+template <int NT, class Keys>
+__device__ __forceinline__ void select_middles_keys(const Keys& rk, unsigned kmin, unsigned kmax, unsigned n,
+                                                    unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
+                                                    unsigned& up) {
   unsigned resid, cnt;
-  lo = radix_select<NT, LDS>(rk, kmin, kmax, (n - 1u) >> 1, n, bins, sel, resid, cnt);
+  lo = radix_select_keys<NT>(rk, kmin, kmax, (n - 1u) >> 1, n, bins, sel, resid, cnt);
   up = lo;
   if ((n & 1u) == 0u && resid + 1u >= cnt) {                   // the run of lo ends at the lower middle
     unsigned above = kMissing;
     rk.sweep([&](unsigned key) { if (key > lo && key < above) above = key; });
     up = block_min_u32<NT>(above, redu);
   }
+}
+template <int NT, bool LDS>
+__device__ __forceinline__ void select_middles(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned n,
+                                               unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
+                                               unsigned& up) {
+  select_middles_keys<NT>(rk, kmin, kmax, n, bins, sel, redu, lo, up);
 }
 
 }  // namespace fm

@@ -71,6 +71,11 @@ class BrainConfig:
     # and the half width of the profile's smoothing window in phases
     seasonal_period: int = 0                 # SEASONAL_PERIOD
     seasonal_smooth: int = 5                 # SEASONAL_SMOOTH
+    # shift_robust: samples per block (0 = one day at the brain's step), the score a level shift must
+    # exceed (sigma-like units) and the whole blocks a new level must have held to count as normal
+    shift_block: int = 0                     # SHIFT_BLOCK
+    shift_threshold: float = 4.0             # SHIFT_THRESHOLD
+    shift_min_blocks: int = 2                # SHIFT_MIN_BLOCKS
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -145,6 +150,11 @@ class BrainConfig:
             return self.seasonal_period
         return None if self.seasonal_period < 0 else max(1, int(round(86400.0 / step)))
 
+    def shift_block_for(self, step: float) -> int:
+        """Block length of ``shift_robust`` in samples of spacing ``step``
+        seconds: ``SHIFT_BLOCK`` when positive, else one day."""
+        return self.shift_block if self.shift_block > 0 else max(1, int(round(86400.0 / step)))
+
     def mvn_threshold(self) -> float:
         return self.threshold if self.multivariate_threshold is None else self.multivariate_threshold
 
@@ -184,6 +194,9 @@ class BrainConfig:
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
         c.seasonal_period = _i(env, "SEASONAL_PERIOD", c.seasonal_period)
         c.seasonal_smooth = _i(env, "SEASONAL_SMOOTH", c.seasonal_smooth)
+        c.shift_block = _i(env, "SHIFT_BLOCK", c.shift_block)
+        c.shift_threshold = _f(env, "SHIFT_THRESHOLD", c.shift_threshold)
+        c.shift_min_blocks = max(1, _i(env, "SHIFT_MIN_BLOCKS", c.shift_min_blocks))
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

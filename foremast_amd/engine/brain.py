@@ -274,7 +274,7 @@ class Brain(BrainStateMixin):
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
                              pairs=pairs, cache=self._cache_ctx(rows, algo),
                              groups=self._groups(rows) if algo == "multivariate_normal" else None,
-                             mvn_threshold=self.cfg.mvn_threshold(), **self._seasonal_args(algo))
+                             mvn_threshold=self.cfg.mvn_threshold(), **self._model_args(algo))
             out = {k: getattr(dec, k).detach().cpu().numpy() for k in keys}
             flags = dec.flags
         else:
@@ -290,7 +290,7 @@ class Brain(BrainStateMixin):
                                  lstm_model=self._lstm_for(sub) if algo == "lstm" else self.lstm_model,
                                  pairs=pairs, cache=self._cache_ctx(sub, algo),
                                  groups=self._groups(sub) if algo == "multivariate_normal" else None,
-                                 mvn_threshold=self.cfg.mvn_threshold(), **self._seasonal_args(algo))
+                                 mvn_threshold=self.cfg.mvn_threshold(), **self._model_args(algo))
                 for k in keys:
                     v = getattr(dec, k).detach()
                     if k not in out:
@@ -314,6 +314,19 @@ class Brain(BrainStateMixin):
         if zoo.canonical(algorithm) != "seasonal_robust":
             return {}
         return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth}
+
+    def _shift_args(self, algorithm: str) -> dict:
+        """``block`` / ``shift_threshold`` / ``min_blocks`` of a zoo decision:
+        SHIFT_BLOCK, SHIFT_THRESHOLD and SHIFT_MIN_BLOCKS for ``shift_robust``,
+        nothing for any other model."""
+        if zoo.canonical(algorithm) != "shift_robust":
+            return {}
+        return {"block": self.cfg.shift_block_for(self.step), "shift_threshold": self.cfg.shift_threshold,
+                "min_blocks": self.cfg.shift_min_blocks}
+
+    def _model_args(self, algorithm: str) -> dict:
+        """The configured parameters of a zoo decision by ``algorithm``."""
+        return {**self._seasonal_args(algorithm), **self._shift_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),

@@ -21,6 +21,7 @@ multivariate_normal             joint Mahalanobis over all metrics      K12
 robust_moving_average_all       median / MAD over the whole history     K13 + band decide
 robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
 seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
+shift_robust                    median / MAD behind the last shift      K15 + band decide
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -46,7 +47,7 @@ from ..ops import smoothing as SM
 
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
-              "robust_moving_average_all", "robust_moving_average", "seasonal_robust")
+              "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -61,7 +62,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "mad": "robust_moving_average_all", "robust": "robust_moving_average_all",
            "robust_moving_average": "robust_moving_average", "robust_ma": "robust_moving_average",
            "seasonal_robust": "seasonal_robust", "seasonal_median": "seasonal_robust",
-           "seasonal_mad": "seasonal_robust", "robust_seasonal": "seasonal_robust"}
+           "seasonal_mad": "seasonal_robust", "robust_seasonal": "seasonal_robust",
+           "shift_robust": "shift_robust", "level_shift": "shift_robust", "robust_shift": "shift_robust",
+           "shift_mad": "shift_robust"}
 
 
 def canonical(name: str) -> str:
@@ -125,12 +128,16 @@ def _valid(hist: torch.Tensor, T: int, cur: torch.Tensor, min_hist: int) -> torc
 def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizon: torch.Tensor, M: int,
            tables: Tables, diff: torch.Tensor | None = None, window: int = 60, period: int | None = None,
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
-           groups=None, mvn_threshold: float | None = None, smooth: int = 5) -> RowDecision:
+           groups=None, mvn_threshold: float | None = None, smooth: int = 5, block: int | None = None,
+           shift_threshold: float = 4.0, min_blocks: int = 2) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
     point (1 = the next sample), used by forecasting models; ``H`` its
-    maximum when the caller knows it (saves a device sync)."""
+    maximum when the caller knows it (saves a device sync).  ``block``,
+    ``shift_threshold`` and ``min_blocks`` are ``shift_robust``'s block length
+    in samples (default 1,440: a day at 60 s), score threshold and the blocks
+    a new level must have held."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -146,6 +153,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         return _expand_stats(dec, n)
     if algo in ROBUST:
         return _robust(hist, T, robust_start(algo, T, window), cur, horizon, M, tables, diff)
+    if algo == "shift_robust":
+        return _shift_robust(hist, T, cur, horizon, M, tables, diff, block or 1440, shift_threshold, min_blocks)
     if algo == "bivariate_normal":
         return _bivariate(hist, T, cur, M, tables, pairs)
     if algo == "multivariate_normal":
@@ -210,6 +219,30 @@ def _robust(hist, T, start, cur, horizon, M, tables, diff) -> RowDecision:
     center, sigma, nfin = MI.robust_stats(hist[:, start:T], T - start)
     has_cur = torch.isfinite(cur).any(1).to(torch.int32)
     valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+    return band(center[:, None], sigma, horizon, cur, M, tables, diff, valid)
+
+
+def shift_start(T: int) -> int:
+    """First history column ``shift_robust`` reads: 0, or the start of the
+    last ``ROBUST_LDS_KEYS`` columns of a longer history (K15 holds the row in
+    LDS and has no global-memory path)."""
+    from ..ops import misc as MI
+    return max(0, int(T) - MI.ROBUST_LDS_KEYS)
+
+
+def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) -> RowDecision:
+    """Hampel band on the history behind the latest persistent level shift
+    (K15): the blocks of ``block`` samples are scanned for the most recent
+    change of level that has held for ``min_blocks`` blocks, and centre and
+    sigma are the median and 1.4826 MAD of the samples from there on; a row
+    without a shift gets ``robust_moving_average_all``'s band.  The history
+    gate is the finite count of the segment modelled, so a segment shorter
+    than MIN_HISTORICAL_DATA is not judged rather than misjudged."""
+    from ..ops import misc as MI
+    s0 = shift_start(T)
+    center, sigma, nseg, _, _, _ = MI.shift_robust(hist[:, s0:T], T - s0, int(block), float(k), int(min_blocks))
+    has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+    valid = (nseg >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
     return band(center[:, None], sigma, horizon, cur, M, tables, diff, valid)
 
 

@@ -88,6 +88,8 @@ _SIGS: dict[str, list] = {
     # hist ld T R m J k H forecast ldf stats profile stream
     "fm_seasonal_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p,
                            c_void_p, c_void_p],
+    # hist ld T R L J k min_blocks out stream
+    "fm_shift_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
     "fm_hpa_score": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.c_double, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p],

@@ -1,7 +1,7 @@
 """K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K14 seasonal robust
-model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
-csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip, csrc/kernels/hpa_graph.hip) with numpy
-references."""
+model, K15 level-shift robust model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip,
+csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
+csrc/kernels/level_shift.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -355,6 +355,154 @@ def seasonal_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: int = 5,
                  ptr(fc), max(H, 1), ptr(stats), ptr(prof), stream_of(hist))
     out = (fc, stats[:, 0], stats[:, 1].to(torch.int32))
     return out + (prof,) if want_profile else out
+
+
+# --------------------------------------------------------------------------- K15
+# Most blocks the level-shift model cuts a history into (csrc/kernels/level_shift.hip kMaxBlocks).
+SHIFT_MAX_BLOCKS = 16
+
+
+def shift_blocks(T: int, L: int) -> int:
+    """Whole blocks J of ``L`` samples the level-shift model cuts from a
+    history of ``T`` samples: the last ``J * L`` columns, block 0 the oldest,
+    at most 16.  A shift can be found when ``J >= 3 + min_blocks``."""
+    T, L = int(T), int(L)
+    if L < 1:
+        return 0
+    return max(0, min(T // L, SHIFT_MAX_BLOCKS))
+
+
+def _middle(v, ok, cnt):
+    """K13's median rule along axis 1 over the entries of ``v`` where ``ok``
+    (``cnt`` of them; rows with none give a value to be masked)."""
+    s = np.sort(np.where(ok, v, np.float32(np.inf)), axis=1)
+    lo = (np.maximum(cnt, 1) - 1) // 2
+    up = np.maximum(cnt, 1) // 2
+    half = np.float32(0.5)
+    return half * np.take_along_axis(s, lo[:, None], 1)[:, 0] + half * np.take_along_axis(s, up[:, None], 1)[:, 0]
+
+
+def shift_candidates(hist, T: int, L: int, min_blocks: int = 2):
+    """The candidate table behind :func:`ref_shift_robust` -> (valid
+    [R, J + 1] bool, score, d, den, edge [R, J + 1] f32, b [R, J] f32):
+    column ``j`` is candidate ``j`` (a shift that ends with transition block
+    ``j - 1``), ``edge = |b[j - 1] - p1|`` (NaN for an empty transition
+    block), ``b`` the block medians.  Columns of invalid candidates hold 0."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    T, L, mb = int(T), int(L), int(min_blocks)
+    check(mb >= 1, "min_blocks must be >= 1")
+    J = shift_blocks(T, L)
+    valid = np.zeros((R, J + 1), bool)
+    score, dd, den, edge = (np.zeros((R, J + 1), np.float32) for _ in range(4))
+    b = np.full((R, J), np.nan, np.float32)
+    if J == 0 or R == 0:
+        return valid, score, dd, den, edge, b
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        blk = x[:, T - J * L:T].reshape(R, J, L)
+        fin = np.isfinite(blk)
+        c = fin.sum(2)
+        for j in range(J):
+            b[:, j] = np.where(c[:, j] >= max(1, L // 4), _middle(blk[:, j], fin[:, j], c[:, j]), np.float32(np.nan))
+        s_all = ref_robust_stats(x, T)[1]
+        se = (np.float32(1.2533) * s_all / np.sqrt(np.float32(L))).astype(np.float32)
+        bok = np.isfinite(b)
+        for j in range(J - mb, 2, -1):
+            pre, post = b[:, :j - 1], b[:, j:]
+            npre, npost = bok[:, :j - 1].sum(1), bok[:, j:].sum(1)
+            ok = (npre >= 2) & (npost >= mb)
+            p0, p1 = _middle(pre, bok[:, :j - 1], npre), _middle(post, bok[:, j:], npost)
+            d = (p1 - p0).astype(np.float32)
+            dev = np.maximum(np.where(bok[:, :j - 1], np.abs(pre - p0[:, None]), 0).max(1),
+                             np.where(bok[:, j:], np.abs(post - p1[:, None]), 0).max(1)).astype(np.float32)
+            dn = np.where(se > dev, se, dev).astype(np.float32)
+            sc = np.where(dn > 0, np.abs(d) / dn, np.where(d != 0, np.float32(np.inf), np.float32(0))).astype(np.float32)
+            valid[:, j] = ok
+            score[:, j] = np.where(ok, sc, 0)
+            dd[:, j] = np.where(ok, d, 0)
+            den[:, j] = np.where(ok, dn, 0)
+            edge[:, j] = np.where(ok, np.abs(b[:, j - 1] - p1), 0)
+    return valid, score, dd, den, edge, b
+
+
+def ref_shift_robust(hist, T: int, L: int, k: float = 4.0, min_blocks: int = 2):
+    """Median / MAD model of ``hist[r, :T]`` that restarts after the latest
+    level shift -> (center [R] f32, sigma [R] f32, n [R] int32, start [R]
+    int32, delta [R] f32, score [R] f32), all arithmetic in fp32.
+
+    The last ``J * L`` columns (:func:`shift_blocks`) are cut into J blocks of
+    L samples, block 0 the oldest.  ``b[j]`` is K13's median rule over the
+    finite samples of block ``j``, NaN (empty) when it has fewer than
+    ``max(1, L // 4)``.  ``se = 1.2533 s_all / sqrt(L)`` with ``s_all`` the
+    sigma of :func:`ref_robust_stats` over the whole row: the standard error
+    of a median of L independent samples, which floors the spread.
+
+    Candidate ``j`` (``J - min_blocks`` down to 3): ``pre`` = the non-empty
+    ``b[0..j-2]``, ``post`` = the non-empty ``b[j..J-1]``; block ``j - 1`` is
+    the transition block and belongs to neither side.  It is valid with at
+    least 2 ``pre`` and ``min_blocks`` ``post`` blocks; then ``p0``, ``p1`` =
+    the median rule over each side, ``d = p1 - p0``, ``den = max(largest
+    |b[i] - own side's median|, se)`` and ``score_j = |d| / den`` (``den ==
+    0``: inf when ``d != 0``, else 0).
+
+    The shift is the largest ``j`` with ``score_j > k``; its start block is
+    ``j - 1`` when ``b[j-1]`` is finite and ``|b[j-1] - p1| <= den`` (the
+    shift fell on a block boundary), else ``j``; ``start = T - (J -
+    startblock) L``, ``delta = d``, ``score = score_j``.  Without a shift
+    ``start = 0``, ``delta = 0`` and ``score`` is the largest score seen (0
+    without a candidate).  ``(center, sigma, n)`` are
+    :func:`ref_robust_stats` over columns ``[start, T)``."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    T, L = int(T), int(L)
+    J = shift_blocks(T, L)
+    valid, sc, dd, den, edge, _ = shift_candidates(x, T, L, min_blocks)
+    start = np.zeros(R, np.int32)
+    delta = np.zeros(R, np.float32)
+    score = np.zeros(R, np.float32)
+    found = np.zeros(R, bool)
+    kf = np.float32(k)
+    with np.errstate(invalid="ignore"):
+        for j in range(J - int(min_blocks), 2, -1):
+            live = valid[:, j] & ~found
+            hit = live & (sc[:, j] > kf)
+            sb = np.where(edge[:, j] <= den[:, j], j - 1, j)       # (a NaN edge compares false)
+            start[hit] = (T - (J - sb) * L)[hit]
+            delta[hit] = dd[hit, j]
+            score[hit] = sc[hit, j]
+            found |= hit
+            seen = live & ~hit & (sc[:, j] > score)
+            score[seen] = sc[seen, j]
+    center = np.full(R, np.nan, np.float32)
+    sigma = np.full(R, np.nan, np.float32)
+    n = np.zeros(R, np.int32)
+    for s0 in np.unique(start):
+        rows = np.nonzero(start == s0)[0]
+        center[rows], sigma[rows], n[rows] = ref_robust_stats(x[rows, s0:], T - int(s0))
+    return center, sigma, n, start, delta, score
+
+
+def shift_robust(hist: torch.Tensor, T: int, L: int, k: float = 4.0, min_blocks: int = 2):
+    """K15: (center [R], sigma [R], n [R] int32, start [R] int32, delta [R],
+    score [R]) of :func:`ref_shift_robust` over ``hist[:, :T]``.  ``hist`` may
+    be any column view with unit column stride: rows need 4-byte alignment
+    only.  The row lives in LDS, so ``T <= ROBUST_LDS_KEYS``."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, L, mb = int(T), int(L), int(min_blocks)
+    check(T <= ROBUST_LDS_KEYS, f"shift_robust holds the row in LDS: T = {T} > {ROBUST_LDS_KEYS}")
+    check(L >= 1 and mb >= 1, "L and min_blocks must be >= 1")
+    if not hist.is_cuda:
+        c, s, n, st, dl, sc = ref_shift_robust(hist.numpy(), T, L, k, mb)
+        return tuple(torch.from_numpy(a) for a in (c, s, n, st, dl, sc))
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    out = torch.empty((R, 6), dtype=torch.float32, device=hist.device)
+    if R:
+        LIB.call("fm_shift_robust", ptr(hist), hist.stride(0), T, R, L, shift_blocks(T, L), float(k), mb, ptr(out),
+                 stream_of(hist))
+    return out[:, 0], out[:, 1], out[:, 2].to(torch.int32), out[:, 3].to(torch.int32), out[:, 4], out[:, 5]
 
 
 # --------------------------------------------------------------------------- K8
