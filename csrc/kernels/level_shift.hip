@@ -4,10 +4,10 @@
 //
 // The row is read from HBM once into LDS as the order-preserving keys of
 // fm_radix_select.h, key i at word a + i with a = (address / 4) & 3 of the
-// row's first sample (K14's loader: a 16-B global load and its 16-B LDS store
-// are aligned together whatever the row's alignment, and a block of the row
-// is a run of words).  The words before and behind the row in its first and
-// last quad hold the missing key.
+// row's first sample (load_row_keys: a 16-B global load and its 16-B LDS
+// store are aligned together whatever the row's alignment, and a block of the
+// row is a run of words).  The words before and behind the row in its first
+// and last quad hold the missing key.
 //
 // Per row: the whole-row median; the finite count of each of the J blocks
 // (the last J * L samples, block 0 the oldest) and the median of every
@@ -33,50 +33,6 @@ namespace {
 constexpr int kShiftThreads = 512;
 constexpr int kMaxBlocks = 16;                   // foremast_amd/ops/misc.py SHIFT_MAX_BLOCKS mirrors it
 
-// K13's median rule over v[0..c), sorted in place (one lane; c <= 16)
-__device__ __forceinline__ float small_median(float* v, int c) {
-  for (int i = 1; i < c; ++i) {
-    const float x = v[i];
-    int j = i - 1;
-    while (j >= 0 && v[j] > x) {
-      v[j + 1] = v[j];
-      --j;
-    }
-    v[j + 1] = x;
-  }
-  return 0.5f * v[(c - 1) >> 1] + 0.5f * v[c >> 1];
-}
-
-// Median and sigma (1.4826 MAD, or the mean-deviation fallback) of the n >= 1
-// finite keys in words [lo, hi) of kw, all within [kmin, kmax].
-template <int NT>
-__device__ __forceinline__ void span_stats(const unsigned* kw, int lo, int hi, unsigned n, unsigned kmin, unsigned kmax,
-                                           unsigned* bins, unsigned* sel, unsigned* redu, double* redd, float& center,
-                                           float& sigma) {
-  SpanKeys<NT> sk{kw, lo, hi, false, 0.f};
-  unsigned klo, kup;
-  select_middles_keys<NT>(sk, kmin, kmax, n, bins, sel, redu, klo, kup);
-  center = 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
-  sk.dev = true;
-  sk.c = center;
-  double sum = 0.0;
-  unsigned dmin = kMissing, dmax = 0u;
-  sk.sweep([&](unsigned d) {
-    if (d != kMissing) {
-      sum += (double)__uint_as_float(d);
-      dmin = d < dmin ? d : dmin;
-      dmax = d > dmax ? d : dmax;
-    }
-  });
-  sum = block_sum<NT>(sum, redd);
-  dmin = block_min_u32<NT>(dmin, redu);
-  dmax = ~block_min_u32<NT>(~dmax, redu);
-  unsigned dlo, dup;
-  select_middles_keys<NT>(sk, dmin, dmax, n, bins, sel, redu, dlo, dup);
-  const float mad = 0.5f * __uint_as_float(dlo) + 0.5f * __uint_as_float(dup);
-  sigma = mad > 0.f ? 1.4826f * mad : 1.2533f * (float)(sum / (double)n);
-}
-
 template <int NT>
 __global__ __launch_bounds__(NT) void shift_robust_kernel(const float* __restrict__ hist, int64_t ld, int T, int L,
                                                           int J, float sqrt_l, float kthr, int min_blocks,
@@ -96,7 +52,6 @@ __global__ __launch_bounds__(NT) void shift_robust_kernel(const float* __restric
   const int64_t row = blockIdx.x;
   const float* p = hist + row * ld;
   const int a = (int)(((uintptr_t)p >> 2) & 3u);             // LDS word of key 0
-  const int nq = (a + T + 3) >> 2;
   unsigned* kw = reinterpret_cast<unsigned*>(s_keys);
   const float qnan = __uint_as_float(0x7FC00000u);
   for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
@@ -105,38 +60,7 @@ __global__ __launch_bounds__(NT) void shift_robust_kernel(const float* __restric
   // ---- the row -> keys in place; finite count and key range
   int n = 0;
   unsigned kmin = kMissing, kmax = 0u;
-  auto track = [&](unsigned k) {
-    if (k != kMissing) {
-      ++n;
-      kmin = k < kmin ? k : kmin;
-      kmax = k > kmax ? k : kmax;
-    }
-  };
-  {
-    int head = (4 - a) & 3;                                  // samples before the 16-B boundary
-    if (head > T) head = T;
-    const int nb = (T - head) >> 2;
-    const float4* b4 = reinterpret_cast<const float4*>(p + head);
-    uint4* d4 = s_keys + ((a + head) >> 2);
-    for (int q = tid; q < nb; q += NT) {
-      const float4 x = b4[q];
-      const uint4 key = make_uint4(enc_key(x.x), enc_key(x.y), enc_key(x.z), enc_key(x.w));
-      track(key.x); track(key.y); track(key.z); track(key.w);
-      d4[q] = key;
-    }
-    // every word the body leaves out lies in the first or the last quad: a
-    // head / tail sample, or padding in front of / behind the row
-    if (tid < (nq > 1 ? 8 : 4)) {
-      const int w = tid < 4 ? tid : 4 * (nq - 1) + (tid - 4);
-      const int i = w - a;
-      if (i < head || i >= head + 4 * nb) {
-        unsigned key = kMissing;
-        if (i >= 0 && i < T) key = enc_key(p[i]);
-        track(key);
-        kw[w] = key;
-      }
-    }
-  }
+  load_row_keys<NT>(p, T, a, s_keys, n, kmin, kmax);
   n = block_sum<NT>(n, s_redi);                              // (barriers: keys, bins and counts visible)
   if (n == 0) {
     if (tid == 0) {
@@ -152,38 +76,9 @@ __global__ __launch_bounds__(NT) void shift_robust_kernel(const float* __restric
   kmin = block_min_u32<NT>(kmin, s_redu);
   kmax = ~block_min_u32<NT>(~kmax, s_redu);
 
-  // ---- finite count of each block: a thread walks its quads with the block
-  // and the position in it carried along, and adds a run's count when the
-  // block changes
+  // ---- finite count of each block
   const int off = T - J * L;                                 // columns in front of the blocks
-  if (J > 0) {
-    for (int q = tid; q < nq; q += NT) {
-      const int u = 4 * q - a - off;                         // position of the quad's word 0 among the blocks
-      if (u < -3) continue;
-      int blk, pos;
-      if (u >= 0) {
-        blk = u / L;
-        pos = u - blk * L;
-      } else {
-        blk = -1;                                            // reaches block 0, position 0 after -u words
-        pos = L + u;
-      }
-      const uint4 v = s_keys[q];
-      const unsigned e[4] = {v.x, v.y, v.z, v.w};
-      int run = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        run += (blk >= 0 && e[j] != kMissing) ? 1 : 0;
-        if (++pos == L) {
-          if (run != 0) atomicAdd(&s_cnt[blk], run);         // (behind the row the words are missing: blk < J)
-          run = 0;
-          pos = 0;
-          ++blk;
-        }
-      }
-      if (run != 0) atomicAdd(&s_cnt[blk], run);
-    }
-  }
+  if (J > 0) count_block_keys<NT>(kw, a + off, L, J, s_cnt);
   __syncthreads();
 
   // ---- whole-row median and sigma

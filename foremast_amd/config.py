@@ -76,6 +76,9 @@ class BrainConfig:
     shift_block: int = 0                     # SHIFT_BLOCK
     shift_threshold: float = 4.0             # SHIFT_THRESHOLD
     shift_min_blocks: int = 2                # SHIFT_MIN_BLOCKS
+    # trend_robust: samples per block (0 = one day at the brain's step) and the non-empty blocks a slope needs
+    trend_block: int = 0                     # TREND_BLOCK
+    trend_min_blocks: int = 3                # TREND_MIN_BLOCKS
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -155,6 +158,11 @@ class BrainConfig:
         seconds: ``SHIFT_BLOCK`` when positive, else one day."""
         return self.shift_block if self.shift_block > 0 else max(1, int(round(86400.0 / step)))
 
+    def trend_block_for(self, step: float) -> int:
+        """Block length of ``trend_robust`` in samples of spacing ``step``
+        seconds: ``TREND_BLOCK`` when positive, else one day."""
+        return self.trend_block if self.trend_block > 0 else max(1, int(round(86400.0 / step)))
+
     def mvn_threshold(self) -> float:
         return self.threshold if self.multivariate_threshold is None else self.multivariate_threshold
 
@@ -197,6 +205,8 @@ class BrainConfig:
         c.shift_block = _i(env, "SHIFT_BLOCK", c.shift_block)
         c.shift_threshold = _f(env, "SHIFT_THRESHOLD", c.shift_threshold)
         c.shift_min_blocks = max(1, _i(env, "SHIFT_MIN_BLOCKS", c.shift_min_blocks))
+        c.trend_block = _i(env, "TREND_BLOCK", c.trend_block)
+        c.trend_min_blocks = max(2, _i(env, "TREND_MIN_BLOCKS", c.trend_min_blocks))
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

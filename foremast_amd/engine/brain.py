@@ -324,9 +324,16 @@ class Brain(BrainStateMixin):
         return {"block": self.cfg.shift_block_for(self.step), "shift_threshold": self.cfg.shift_threshold,
                 "min_blocks": self.cfg.shift_min_blocks}
 
+    def _trend_args(self, algorithm: str) -> dict:
+        """``block`` / ``trend_min_blocks`` of a zoo call: TREND_BLOCK and
+        TREND_MIN_BLOCKS for ``trend_robust``, nothing for any other model."""
+        if zoo.canonical(algorithm) != "trend_robust":
+            return {}
+        return {"block": self.cfg.trend_block_for(self.step), "trend_min_blocks": self.cfg.trend_min_blocks}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
-        return {**self._seasonal_args(algorithm), **self._shift_args(algorithm)}
+        return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -858,7 +865,8 @@ class Brain(BrainStateMixin):
             fc, _ = zoo.forecast(self.cfg.hpa_forecast_algorithm, h, T, max(1, self.cfg.hpa_forecast_steps),
                                  lstm_model=self.lstm_model,
                                  cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm),
-                                 **self._seasonal_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._seasonal_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._trend_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

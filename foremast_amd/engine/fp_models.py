@@ -620,6 +620,9 @@ class ModelsMixin:
             # only the span of whole cycles is gathered: the model reads no column before it
             kw = b._seasonal_args(algo)
             return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
+        elif algo == "trend_robust":
+            # only the columns the kernel holds are gathered
+            return zoo.forecast(algo, lazy.materialize(zoo.trend_start(sub.T)), sub.T, H, **b._trend_args(algo))
         else:
             hist = lazy.materialize(0)
         return zoo.forecast(algo, hist, sub.T, H, lstm_model=lstm, cache=ctx)

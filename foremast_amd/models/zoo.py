@@ -22,6 +22,7 @@ robust_moving_average_all       median / MAD over the whole history     K13 + ba
 robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
 seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
 shift_robust                    median / MAD behind the last shift      K15 + band decide
+trend_robust                    repeated-median line + residual MAD     K16 + band decide
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -47,7 +48,8 @@ from ..ops import smoothing as SM
 
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
-              "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust")
+              "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
+              "trend_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -64,7 +66,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "seasonal_robust": "seasonal_robust", "seasonal_median": "seasonal_robust",
            "seasonal_mad": "seasonal_robust", "robust_seasonal": "seasonal_robust",
            "shift_robust": "shift_robust", "level_shift": "shift_robust", "robust_shift": "shift_robust",
-           "shift_mad": "shift_robust"}
+           "shift_mad": "shift_robust",
+           "trend_robust": "trend_robust", "robust_trend": "trend_robust", "trend_median": "trend_robust",
+           "repeated_median": "trend_robust"}
 
 
 def canonical(name: str) -> str:
@@ -129,7 +133,7 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            tables: Tables, diff: torch.Tensor | None = None, window: int = 60, period: int | None = None,
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
            groups=None, mvn_threshold: float | None = None, smooth: int = 5, block: int | None = None,
-           shift_threshold: float = 4.0, min_blocks: int = 2) -> RowDecision:
+           shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -137,7 +141,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     maximum when the caller knows it (saves a device sync).  ``block``,
     ``shift_threshold`` and ``min_blocks`` are ``shift_robust``'s block length
     in samples (default 1,440: a day at 60 s), score threshold and the blocks
-    a new level must have held."""
+    a new level must have held; ``trend_robust`` cuts its blocks by ``block``
+    too and fits a slope from ``trend_min_blocks`` non-empty ones."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -177,6 +182,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     if algo == "seasonal_robust":
         # the kernel counts the finite samples it models: no separate history pass
         fc, sigma, nfin = _seasonal_robust(hist, T, H, period, smooth)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "trend_robust":
+        # gated on the finite count of the residuals the kernel modelled
+        fc, sigma, nfin = _trend_robust(hist, T, H, block or 1440, trend_min_blocks)
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
@@ -248,7 +259,7 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
-FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust")
+FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust")
 
 
 def seasonal_start(T: int, period: int | None) -> int:
@@ -275,9 +286,31 @@ def _seasonal_robust(hist, T, H, period, smooth):
     return center[:, None].expand(-1, H), sigma, nfin
 
 
+def trend_start(T: int) -> int:
+    """First history column ``trend_robust`` reads: as :func:`shift_start`,
+    the last ``ROBUST_LDS_KEYS`` columns of a longer history (K16 holds the
+    row in LDS and has no global-memory path)."""
+    return shift_start(T)
+
+
+def _trend_robust(hist, T, H, block, min_blocks):
+    """Straight line through the history by the repeated median of the pair
+    slopes of its block medians, and the median / MAD-sigma of the residuals
+    about it, K16 -> (forecast [R, H], sigma [R], finite count [R]).  The
+    centre is the level at the last history sample, so the forecast at
+    horizon ``h`` is ``center + slope * h`` (a product and a sum, each rounded
+    to fp32)."""
+    from ..ops import misc as MI
+    s0 = trend_start(T)
+    center, sigma, nfin, slope = MI.trend_robust(hist[:, s0:T], T - s0, int(block), int(min_blocks))
+    h = torch.arange(1, int(H) + 1, dtype=torch.float32, device=center.device)
+    return center[:, None] + slope[:, None] * h[None, :], sigma, nfin
+
+
 def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | None = None,
              lstm_model=None, cache: CacheContext | None = None,
-             smooth: int = 5) -> tuple[torch.Tensor, torch.Tensor]:
+             smooth: int = 5, block: int | None = None,
+             trend_min_blocks: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]).  Used by the
     band decision and, for HPA jobs, to publish the load forecast a cluster
@@ -306,6 +339,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return lstm_model.forecast(hist, T, H)
     if algo == "seasonal_robust":
         return _seasonal_robust(hist, T, H, period, smooth)[:2]
+    if algo == "trend_robust":
+        return _trend_robust(hist, T, H, block or 1440, trend_min_blocks)[:2]
     raise ValueError(f"{algorithm!r} is not a forecasting model ({', '.join(FORECASTERS)})")
 
 

@@ -1,7 +1,8 @@
 """K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K14 seasonal robust
-model, K15 level-shift robust model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip,
-csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
-csrc/kernels/level_shift.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
+model, K15 level-shift robust model, K16 trend robust model, K8 HPA score, K9 downstream impact
+(csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip,
+csrc/kernels/seasonal_robust.hip, csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip,
+csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -503,6 +504,84 @@ def shift_robust(hist: torch.Tensor, T: int, L: int, k: float = 4.0, min_blocks:
         LIB.call("fm_shift_robust", ptr(hist), hist.stride(0), T, R, L, shift_blocks(T, L), float(k), mb, ptr(out),
                  stream_of(hist))
     return out[:, 0], out[:, 1], out[:, 2].to(torch.int32), out[:, 3].to(torch.int32), out[:, 4], out[:, 5]
+
+
+# --------------------------------------------------------------------------- K16
+def ref_trend_robust(hist, T: int, L: int, min_blocks: int = 3):
+    """Median / MAD model of ``hist[r, :T]`` about a robustly fitted straight
+    line -> (center [R] f32, sigma [R] f32, n [R] int32, slope [R] f32,
+    nblocks [R] int32), all arithmetic in fp32.
+
+    The last ``J * L`` columns (:func:`shift_blocks`) are cut into J blocks of
+    L samples, block 0 the oldest.  ``b[j]`` is K13's median rule over the
+    finite samples of block ``j``; a block with fewer than ``max(1, L // 4)``
+    is empty, and ``nblocks`` counts the others, at indices ``q_0 < ... <
+    q_{B-1}``.  With ``B >= min_blocks`` the slope is Siegel's repeated median
+    of the block medians: ``s_i`` = the median rule over ``j != i`` of
+    ``(b[q_j] - b[q_i]) / float((q_j - q_i) L)`` (one subtraction, one
+    correctly rounded division), ``slope`` = the median rule over the ``s_i``.
+    With fewer blocks, or a non-finite result, ``slope = 0``.
+
+    The line is anchored at the last history sample: ``r_i = x_i - (slope *
+    float(i - (T - 1)))``, the product rounded to fp32 and then the difference
+    (no fused multiply-add).  ``(center, sigma, n)`` are
+    :func:`ref_robust_stats` of ``r``, so the centre is the level at the end of
+    the history and the forecast at horizon ``h`` (1 = the next sample) is
+    ``center + slope * float(h)``.  A row with ``slope == 0`` gets
+    :func:`ref_robust_stats` of the row itself."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    T, L, mb = int(T), int(L), int(min_blocks)
+    check(mb >= 2, "min_blocks must be >= 2")
+    J = shift_blocks(T, L)
+    slope = np.zeros(R, np.float32)
+    nblocks = np.zeros(R, np.int32)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if J > 0 and R > 0:
+            blk = x[:, T - J * L:T].reshape(R, J, L)
+            fin = np.isfinite(blk)
+            c = fin.sum(2)
+            b = np.full((R, J), np.nan, np.float32)
+            for j in range(J):
+                b[:, j] = _middle(blk[:, j], fin[:, j], c[:, j])
+            ok = c >= max(1, L // 4)
+            nblocks = ok.sum(1).astype(np.int32)
+            # pair[r, i, j] = (b_j - b_i) / ((j - i) L); the diagonal and the empty blocks are masked out
+            q = np.arange(J, dtype=np.int64)
+            dist = ((q[None, :] - q[:, None]) * L).astype(np.float32)
+            pair = ((b[:, None, :] - b[:, :, None]).astype(np.float32) / dist[None]).astype(np.float32)
+            pok = ok[:, None, :] & ok[:, :, None] & (q[None, :] != q[:, None])[None]
+            si = np.zeros((R, J), np.float32)
+            for i in range(J):
+                si[:, i] = _middle(pair[:, i], pok[:, i], pok[:, i].sum(1))
+            sl = _middle(si, ok, nblocks)
+            slope = np.where((nblocks >= mb) & np.isfinite(sl), sl, np.float32(0)).astype(np.float32)
+        t = (np.arange(T, dtype=np.int64) - (T - 1)).astype(np.float32)
+        r = x - (slope[:, None] * t[None, :]).astype(np.float32)
+    center, sigma, n = ref_robust_stats(r, T)
+    return center, sigma, n, slope, nblocks
+
+
+def trend_robust(hist: torch.Tensor, T: int, L: int, min_blocks: int = 3):
+    """K16: (center [R], sigma [R], n [R] int32, slope [R]) of
+    :func:`ref_trend_robust` over ``hist[:, :T]``.  ``hist`` may be any column
+    view with unit column stride: rows need 4-byte alignment only.  The row
+    lives in LDS, so ``T <= ROBUST_LDS_KEYS``."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, L, mb = int(T), int(L), int(min_blocks)
+    check(T <= ROBUST_LDS_KEYS, f"trend_robust holds the row in LDS: T = {T} > {ROBUST_LDS_KEYS}")
+    check(L >= 1 and mb >= 2, "L must be >= 1 and min_blocks >= 2")
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_trend_robust(hist.numpy(), T, L, mb)[:4])
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    out = torch.empty((R, 4), dtype=torch.float32, device=hist.device)
+    if R:
+        LIB.call("fm_trend_robust", ptr(hist), hist.stride(0), T, R, L, shift_blocks(T, L), mb, ptr(out),
+                 stream_of(hist))
+    return out[:, 0], out[:, 1], out[:, 2].to(torch.int32), out[:, 3]
 
 
 # --------------------------------------------------------------------------- K8
