@@ -32,30 +32,11 @@
 // The kernel is bandwidth-bound (about 5.5 FMA per loaded float at K = 8):
 // plain VALU FMAs, no MFMA.
 #include "fm_common.h"
+#include "fm_mvn.h"
 
 using namespace fm;
 
 namespace {
-
-constexpr double MVN_RIDGE = 1e-6;
-
-// acc[0..NA) and cnt summed over the 256 threads in fp64 -> tot[0..NA], the
-// count last.  sh holds 4 * (NA + 1) doubles.
-template <int NA>
-__device__ __forceinline__ void block_sum_arr(const float (&acc)[NA], int cnt, double* sh, double* tot) {
-  const int w = wave_id();
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const double v = wave_sum((double)acc[i]);
-    if (lane_id() == 0) sh[w * (NA + 1) + i] = v;
-  }
-  const int c = wave_sum(cnt);
-  if (lane_id() == 0) sh[w * (NA + 1) + NA] = (double)c;
-  __syncthreads();
-  const int t = threadIdx.x;
-  if (t <= NA) tot[t] = (sh[t] + sh[(NA + 1) + t]) + (sh[2 * (NA + 1) + t] + sh[3 * (NA + 1) + t]);
-  __syncthreads();
-}
 
 // One float4 of every member row: sums of the complete columns.
 template <int K>
@@ -90,13 +71,10 @@ __global__ __launch_bounds__(256) void mvn_kernel(const float* __restrict__ hist
                                                   float* __restrict__ dist /*[G,n]*/,
                                                   unsigned long long* __restrict__ flags, int NW,
                                                   int* __restrict__ count, int* __restrict__ valid) {
-  constexpr int NP = K * (K + 1) / 2, NA = K + NP;
-  __shared__ double sh[4 * (NA + 1)];
-  __shared__ double tot[NA + 1];
-  __shared__ double s_mu[K], s_isd[K], s_C[K * K], s_L[K * K];
-  __shared__ float s_cut;
-  __shared__ int s_ok;
-  __shared__ int redi[4];
+  constexpr int NA = MvnShared<K>::NA;
+  __shared__ MvnShared<K> S;
+  double* const sh = S.sh;
+  double* const tot = S.tot;
   const int64_t g = blockIdx.x;
   const int tid = threadIdx.x;
 
@@ -172,98 +150,8 @@ __global__ __launch_bounds__(256) void mvn_kernel(const float* __restrict__ hist
   }
   block_sum_arr<NA>(acc, cnt, sh, tot);
 
-  // ---- moments, degeneracy, correlation + ridge, Cholesky (fp64, one thread, through LDS)
-  if (tid == 0) {
-    const double N = tot[NA];
-    const int Ni = (int)N;
-    const int need = min_n > K + 2 ? min_n : K + 2;
-    const bool okg = Ni >= need;
-    const double inv_n = N > 0.0 ? 1.0 / N : 0.0, den = N > 1.0 ? N - 1.0 : 1.0;
-    float* pr = params + g * (2 + NA);
-    int k = 0;
-    int idx = K;
-#pragma unroll
-    for (int a = 0; a < K; ++a) {
-      const double mu = (double)s[a] + tot[a] * inv_n;
-      s_mu[a] = mu;
-      pr[2 + a] = (float)mu;
-#pragma unroll
-      for (int b = a; b < K; ++b) {
-        const double c = (tot[idx] - tot[a] * tot[b] * inv_n) / den;
-        s_C[a * K + b] = c;
-        s_C[b * K + a] = c;
-        pr[2 + idx] = (float)c;
-        ++idx;
-      }
-      const double caa = s_C[a * K + a];
-      const bool live = caa > 1e-12 * mu * mu + 1e-30;
-      s_isd[a] = live ? 1.0 / sqrt(caa) : 0.0;
-      k += live;
-    }
-    pr[0] = (float)Ni;
-    pr[1] = (float)k;
-    // a constant member keeps a unit diagonal and zero couplings: it adds
-    // nothing to the distance, which equals the one over the live members alone
-#pragma unroll 1
-    for (int a = 0; a < K; ++a) {
-#pragma unroll 1
-      for (int b = 0; b <= a; ++b) {
-        double v = a == b ? 1.0 + MVN_RIDGE : s_C[a * K + b] * s_isd[a] * s_isd[b];
-#pragma unroll 1
-        for (int c = 0; c < b; ++c) v -= s_L[a * K + c] * s_L[b * K + c];
-        s_L[a * K + b] = a == b ? sqrt(v > 1e-12 ? v : 1e-12) : v / s_L[b * K + b];
-      }
-    }
-    s_cut = cuts[(lowered[g] ? 9 : 0) + k];
-    s_ok = okg ? 1 : 0;
-  }
-  __syncthreads();
-
-  // ---- current points, one per thread
-  const bool okg = s_ok != 0;
-  const float cut = s_cut;
-  int nflag = 0, npres = 0;
-  for (int i0 = 0; i0 < n; i0 += 256) {
-    const int i = i0 + tid;
-    bool f = false;
-    if (i < n) {
-      float d = NAN;
-      if (rows_ok) {
-        bool present = true, moved = false;
-        double y[K];
-#pragma unroll
-        for (int a = 0; a < K; ++a) {
-          const float x = cur[rid[a] * ld_c + i];
-          present = present && isfinite(x);
-          const double mu = s_mu[a], isd = s_isd[a], dx = (double)x - mu;
-          moved = moved || (isd == 0.0 && fabs(dx) > 1e-6 * fabs(mu) + 1e-12);
-          double z = dx * isd;
-#pragma unroll
-          for (int b = 0; b < a; ++b) z -= s_L[a * K + b] * y[b];
-          y[a] = z / s_L[a * K + a];
-        }
-        npres += present;
-        if (present && okg) {
-          double q = 0.0;
-#pragma unroll
-          for (int a = 0; a < K; ++a) q += y[a] * y[a];
-          d = moved ? INFINITY : (float)sqrt(q);
-          f = d > cut;
-          nflag += f;
-        }
-      }
-      dist[g * n + i] = d;
-    }
-    const unsigned long long bal = __ballot(f);
-    const int w = i0 / 64 + wave_id();
-    if (lane_id() == 0 && w < NW) flags[g * NW + w] = bal;
-  }
-  nflag = block_sum<256>(nflag, redi);
-  npres = block_sum<256>(npres, redi);
-  if (tid == 0) {
-    count[g] = nflag;
-    valid[g] = (okg ? 1 : 0) | (npres > 0 ? 2 : 0);
-  }
+  // ---- moments ... flags: the back half shared with K17 (fm_mvn.h)
+  mvn_finish<K>(S, s, rid, rows_ok, g, cur, ld_c, n, cuts, lowered, min_n, params, dist, flags, NW, count, valid);
 }
 
 template <int K>

@@ -67,6 +67,9 @@ class BrainConfig:
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
+    # ML_MULTIVARIATE_REJECT: robust_multivariate sets aside the history columns where a member lies more than
+    # this many of its MAD-sigmas from its median (<= 0: nothing is rejected, the model is multivariate_normal)
+    multivariate_reject: float = 3.5
     # seasonal_robust: period in samples (0 = one day at the brain's step, < 0 = detect from the history)
     # and the half width of the profile's smoothing window in phases
     seasonal_period: int = 0                 # SEASONAL_PERIOD
@@ -200,6 +203,7 @@ class BrainConfig:
         c.pairwise_threshold_factor = _f(env, "ML_PAIRWISE_THRESHOLD_FACTOR", c.pairwise_threshold_factor)
         if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
+        c.multivariate_reject = _f(env, "ML_MULTIVARIATE_REJECT", c.multivariate_reject)
         c.seasonal_period = _i(env, "SEASONAL_PERIOD", c.seasonal_period)
         c.seasonal_smooth = _i(env, "SEASONAL_SMOOTH", c.seasonal_smooth)
         c.shift_block = _i(env, "SHIFT_BLOCK", c.shift_block)

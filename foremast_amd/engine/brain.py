@@ -273,8 +273,9 @@ class Brain(BrainStateMixin):
             dec = zoo.decide(algo, hist, T, cur, hor, R, tables, diff,
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
                              pairs=pairs, cache=self._cache_ctx(rows, algo),
-                             groups=self._groups(rows) if algo == "multivariate_normal" else None,
-                             mvn_threshold=self.cfg.mvn_threshold(), **self._model_args(algo))
+                             groups=self._groups(rows) if algo in zoo.MVN_MODELS else None,
+                             mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
+                             **self._model_args(algo))
             out = {k: getattr(dec, k).detach().cpu().numpy() for k in keys}
             flags = dec.flags
         else:
@@ -289,8 +290,9 @@ class Brain(BrainStateMixin):
                                  None if diff is None else diff.index_select(0, it),
                                  lstm_model=self._lstm_for(sub) if algo == "lstm" else self.lstm_model,
                                  pairs=pairs, cache=self._cache_ctx(sub, algo),
-                                 groups=self._groups(sub) if algo == "multivariate_normal" else None,
-                                 mvn_threshold=self.cfg.mvn_threshold(), **self._model_args(algo))
+                                 groups=self._groups(sub) if algo in zoo.MVN_MODELS else None,
+                                 mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
+                                 **self._model_args(algo))
                 for k in keys:
                     v = getattr(dec, k).detach()
                     if k not in out:

@@ -301,7 +301,7 @@ class ModelsMixin:
             dsub = diff if sub.idx is None else dsub
             lazy = LazyHist(store.buf, sub.rm, *sub.shift_lim(), sub.T)
             algo = sub.algo
-            if algo in ("moving_average_all", "bivariate_normal", "multivariate_normal", "moving_average", *zoo.ROBUST,
+            if algo in ("moving_average_all", "bivariate_normal", *zoo.MVN_MODELS, "moving_average", *zoo.ROBUST,
                         "shift_robust"):
                 lo_col = 0
                 if algo == "moving_average":
@@ -312,7 +312,8 @@ class ModelsMixin:
                 elif algo == "shift_robust":
                     lo_col = zoo.shift_start(sub.T)
                 dec = zoo.decide(algo, lazy.materialize(lo_col), sub.T, cur, sub.hor, sub.M, sub.tables, dsub,
-                                 mvn_threshold=cfg.mvn_threshold(), **b._shift_args(algo))
+                                 mvn_threshold=cfg.mvn_threshold(), mvn_reject=cfg.multivariate_reject,
+                                 **b._shift_args(algo))
             else:
                 H = sub.H
                 if hpa_algo == algo:

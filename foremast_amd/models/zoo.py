@@ -18,6 +18,7 @@ prophet                         trend+hinges+daily/weekly Fourier LSQ   K10 (f32
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
 multivariate_normal             joint Mahalanobis over all metrics      K12
+robust_multivariate             the same, past incident columns aside   K13 + K17
 robust_moving_average_all       median / MAD over the whole history     K13 + band decide
 robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
 seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
@@ -32,7 +33,9 @@ advanced over their new samples instead of re-fitting the grid.
 Thresholds are in sigma units per metric (``BrainConfig.rule_for``), lowered
 by ``pairwise_threshold_factor`` on rows whose canary distribution differs.
 ``multivariate_normal`` takes one joint threshold (``mvn_threshold``), turned
-into a cut on the Mahalanobis distance per number of live members.
+into a cut on the Mahalanobis distance per number of live members;
+``robust_multivariate`` shares it and sets aside the history columns where a
+member lies more than ``mvn_reject`` MAD-sigmas from its median.
 """
 from __future__ import annotations
 
@@ -49,7 +52,7 @@ from ..ops import smoothing as SM
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
-              "trend_robust")
+              "trend_robust", "robust_multivariate")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -68,7 +71,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "shift_robust": "shift_robust", "level_shift": "shift_robust", "robust_shift": "shift_robust",
            "shift_mad": "shift_robust",
            "trend_robust": "trend_robust", "robust_trend": "trend_robust", "trend_median": "trend_robust",
-           "repeated_median": "trend_robust"}
+           "repeated_median": "trend_robust",
+           "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
+           "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
 
 def canonical(name: str) -> str:
@@ -133,7 +138,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            tables: Tables, diff: torch.Tensor | None = None, window: int = 60, period: int | None = None,
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
            groups=None, mvn_threshold: float | None = None, smooth: int = 5, block: int | None = None,
-           shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3) -> RowDecision:
+           shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
+           mvn_reject: float = 3.5) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -142,7 +148,9 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     ``shift_threshold`` and ``min_blocks`` are ``shift_robust``'s block length
     in samples (default 1,440: a day at 60 s), score threshold and the blocks
     a new level must have held; ``trend_robust`` cuts its blocks by ``block``
-    too and fits a slope from ``trend_min_blocks`` non-empty ones."""
+    too and fits a slope from ``trend_min_blocks`` non-empty ones.
+    ``mvn_reject`` is ``robust_multivariate``'s rejection limit in MAD-sigmas
+    (<= 0: nothing is rejected)."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -164,6 +172,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         return _bivariate(hist, T, cur, M, tables, pairs)
     if algo == "multivariate_normal":
         return _multivariate(hist, T, cur, M, tables, diff, groups, mvn_threshold)
+    if algo == "robust_multivariate":
+        return _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups, mvn_threshold, mvn_reject)
     if H is None:
         H = int(horizon.max().item()) if horizon.numel() else 1
     H = max(int(H), 1)
@@ -440,7 +450,19 @@ def mvn_groups(jobs) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
             torch.tensor(singles, dtype=torch.int64))
 
 
-def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None) -> RowDecision:
+MVN_MODELS = ("multivariate_normal", "robust_multivariate")
+
+
+def _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups=None, thr=None, reject=3.5) -> RowDecision:
+    """``_multivariate`` with the moments taken past the incident columns of
+    the history (K13 + K17, ``ops/misc.py:ref_mvn_robust``): a complete
+    column where any member lies more than ``reject`` of its MAD-sigmas from
+    its median is set aside, unless that would set aside more than half.
+    Singles go through ``robust_moving_average_all``."""
+    return _multivariate(hist, T, cur, M, tables, diff, groups, thr, reject=float(reject), horizon=horizon)
+
+
+def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=None, horizon=None) -> RowDecision:
     """All metrics of a job scored jointly (K12): every member row of a group
     gets the group's decision, bounds in Mahalanobis units (upper = the cut
     the group used, lower = 0).  ``groups`` = (rows [G, 8] int32, K [G],
@@ -448,7 +470,9 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None) -> RowDe
     consecutive rows.  Singles go through ``moving_average_all``.  ``thr`` is
     the joint threshold in sigma units (default: the largest of the table);
     a group is judged at ``thr * pair_factor`` when any member's canary
-    distribution differs."""
+    distribution differs.  ``reject`` not None: the robust model (K17) with
+    that rejection limit, and singles through ``_robust`` (which needs their
+    ``horizon``)."""
     from ..ops import misc as MI
     R, n = cur.shape
     device = hist.device
@@ -478,8 +502,12 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None) -> RowDe
             lowered = ((diff.to(device)[safe] != 0) & member).any(1).to(torch.uint8)
         for K in sorted(set(gk.tolist())):
             sel = (gk == K).nonzero().squeeze(1)
-            params, dist, flags, cnt, gvalid = MI.mvn(hist, T, cur, grows[sel].contiguous(), K, cuts, lowered[sel],
-                                                      tables.min_hist)
+            if reject is None:
+                params, dist, flags, cnt, gvalid = MI.mvn(hist, T, cur, grows[sel].contiguous(), K, cuts,
+                                                          lowered[sel], tables.min_hist)
+            else:
+                params, dist, flags, cnt, gvalid, _ = MI.mvn_robust(hist, T, cur, grows[sel].contiguous(), K, cuts,
+                                                                    lowered[sel], tables.min_hist, reject)
             sc = torch.nan_to_num(dist, nan=0.0).amax(1)
             used = cuts_d[lowered[sel].long(), params[:, 1].long()]
             hist_ok = (gvalid & 1).to(torch.int32)
@@ -494,12 +522,18 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None) -> RowDe
     if singles.numel():
         S1 = int(singles.numel())
         pick = lambda t: t[singles % t.numel()].contiguous()
-        sub = C.stats_decide(_aligned_rows(hist, singles, T), cur[singles].contiguous(), T, S1, pick(tables.thr),
-                             pick(tables.bound), pick(tables.minlb), None if diff is None else diff[singles].contiguous(),
-                             tables.pair_factor, tables.min_hist)
+        sdiff = None if diff is None else diff[singles].contiguous()
+        if reject is None:
+            sub = C.stats_decide(_aligned_rows(hist, singles, T), cur[singles].contiguous(), T, S1, pick(tables.thr),
+                                 pick(tables.bound), pick(tables.minlb), sdiff, tables.pair_factor, tables.min_hist)
+            up_all[singles] = sub.stats[:, 2:3].expand(-1, n)
+            lo_all[singles] = sub.stats[:, 3:4].expand(-1, n)
+        else:
+            sub = _robust(hist[singles], T, 0, cur[singles].contiguous(), horizon.to(device)[singles], S1,
+                          Tables(pick(tables.thr), pick(tables.bound), pick(tables.minlb), tables.pair_factor,
+                                 tables.min_hist), sdiff)
+            up_all[singles], lo_all[singles], valid[singles] = sub.upper, sub.lower, sub.valid
         flags_all[singles], count_all[singles], score_all[singles] = sub.flags, sub.count, sub.score
-        up_all[singles] = sub.stats[:, 2:3].expand(-1, n)
-        lo_all[singles] = sub.stats[:, 3:4].expand(-1, n)
     return RowDecision(up_all, lo_all, flags_all, count_all, score_all, valid)
 
 

@@ -83,6 +83,10 @@ _SIGS: dict[str, list] = {
     # hist ld T R cur ld_c n rows G K cuts lowered min_n form params dist flags NW count valid stream
     "fm_mvn": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # hist ld T R cur ld_c n rows G K cuts lowered min_n stats reject params dist flags NW count valid rejected stream
+    "fm_mvn_robust": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p,
+                      c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                      c_void_p],
     # hist ld T R out stream
     "fm_robust_stats": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p],
     # hist ld T R m J k H forecast ldf stats profile stream

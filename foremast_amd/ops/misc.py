@@ -1,8 +1,8 @@
-"""K5 bivariate normal, K12 multivariate normal, K13 robust (median / MAD) statistics, K14 seasonal robust
-model, K15 level-shift robust model, K16 trend robust model, K8 HPA score, K9 downstream impact
-(csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/robust_stats.hip,
-csrc/kernels/seasonal_robust.hip, csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip,
-csrc/kernels/hpa_graph.hip) with numpy references."""
+"""K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
+K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K8 HPA score, K9 downstream
+impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/mvn_robust.hip,
+csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip, csrc/kernels/level_shift.hip,
+csrc/kernels/trend_robust.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -154,18 +154,14 @@ def ref_mvn(hist, cur, rows, K: int, cuts, lowered, min_n: int):
     return params, dist, _pack_words(flag), flag.sum(1).astype(np.int32), valid
 
 
-def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts, lowered: torch.Tensor,
-        min_n: int):
-    """Joint multivariate-normal detector (K12) over groups of ``K`` member
-    rows: ``rows`` [G, 8] int32 row ids into ``hist`` [R, ld] (first ``T``
-    columns) and ``cur`` [R, n], -1 padded past ``K``; ``cuts`` from
-    :func:`mvn_cuts`; ``lowered`` [G] uint8 picks row 1 of ``cuts``.
-    Returns what :func:`ref_mvn` returns, which is also the CPU path."""
+def _mvn_args(hist, T, cur, rows, K, cuts, lowered) -> np.ndarray:
+    """The argument checks of the joint detectors' wrappers (nothing is
+    launched when one fails) -> ``cuts`` as fp32 [2, 9]."""
     check(2 <= int(K) <= MVN_MAX_K, f"group size must be in [2, {MVN_MAX_K}]")
     check(rows.dim() == 2 and rows.shape[1] == MVN_MAX_K and rows.dtype == torch.int32, "rows must be int32 [G, 8]")
     check(hist.dtype == torch.float32 and cur.dtype == torch.float32 and hist.shape[0] == cur.shape[0]
           and 0 < T <= hist.shape[1], "hist / cur must be fp32 with the same rows")
-    G, n = rows.shape[0], cur.shape[1]
+    G = rows.shape[0]
     check(lowered.numel() == G and lowered.dtype == torch.uint8, "lowered must be uint8 [G]")
     cuts = np.asarray(cuts, np.float32)
     check(cuts.shape == (2, MVN_MAX_K + 1), "cuts must be [2, 9]")
@@ -175,26 +171,131 @@ def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: in
     if hist.is_cuda:
         check(hist.stride(1) == 1 and hist.stride(0) % 4 == 0 and hist.data_ptr() % 16 == 0 and cur.stride(1) == 1,
               "rows must be contiguous, 16-B aligned, with a row stride that is a multiple of 4")
-    NW = max(1, (n + 63) // 64)
+    return cuts
+
+
+def _mvn_outputs(G: int, n: int, K: int, d):
+    NA, NW = K + K * (K + 1) // 2, max(1, (n + 63) // 64)
+    return (torch.empty((G, 2 + NA), dtype=torch.float32, device=d), torch.empty((G, n), dtype=torch.float32, device=d),
+            torch.zeros((G, NW), dtype=torch.int64, device=d), torch.empty((G,), dtype=torch.int32, device=d),
+            torch.empty((G,), dtype=torch.int32, device=d))
+
+
+def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts, lowered: torch.Tensor,
+        min_n: int):
+    """Joint multivariate-normal detector (K12) over groups of ``K`` member
+    rows: ``rows`` [G, 8] int32 row ids into ``hist`` [R, ld] (first ``T``
+    columns) and ``cur`` [R, n], -1 padded past ``K``; ``cuts`` from
+    :func:`mvn_cuts`; ``lowered`` [G] uint8 picks row 1 of ``cuts``.
+    Returns what :func:`ref_mvn` returns, which is also the CPU path."""
+    cuts = _mvn_args(hist, T, cur, rows, K, cuts, lowered)
+    G, n = rows.shape[0], cur.shape[1]
     if not hist.is_cuda:
         return tuple(torch.from_numpy(a) for a in ref_mvn(hist.numpy()[:, :T], cur.numpy(), rows.numpy(), K, cuts,
                                                           lowered.numpy(), min_n))
     require_native(hist)
     d = hist.device
-    NA = K + K * (K + 1) // 2
-    params = torch.empty((G, 2 + NA), dtype=torch.float32, device=d)
-    dist = torch.empty((G, n), dtype=torch.float32, device=d)
-    flags = torch.zeros((G, NW), dtype=torch.int64, device=d)
-    cnt = torch.empty((G,), dtype=torch.int32, device=d)
-    valid = torch.empty((G,), dtype=torch.int32, device=d)
+    params, dist, flags, cnt, valid = _mvn_outputs(G, n, K, d)
     if G == 0 or n == 0:
         return params, dist, flags, cnt, valid
     ct = torch.from_numpy(cuts).to(d)
     rows = rows.contiguous()
     LIB.call("fm_mvn", ptr(hist), hist.stride(0), int(T), hist.shape[0], ptr(cur), cur.stride(0), n, ptr(rows), G,
-             int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), MVN_FORM, ptr(params), ptr(dist), ptr(flags), NW,
-             ptr(cnt), ptr(valid), stream_of(hist))
+             int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), MVN_FORM, ptr(params), ptr(dist), ptr(flags),
+             flags.shape[1], ptr(cnt), ptr(valid), stream_of(hist))
     return params, dist, flags, cnt, valid
+
+
+# --------------------------------------------------------------------------- K17
+# Incident columns are those with a member further than this many of its own MAD-sigmas from its median.
+MVN_REJECT = 3.5
+
+
+def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: float = MVN_REJECT):
+    """Oracle of the robust joint detector: :func:`ref_mvn` over the history
+    columns that are not incident columns -> its five arrays and ``rejected``
+    [G] int32, the columns set aside.
+
+    ``(c_r, s_r, n_r) = ref_robust_stats(hist, T)`` per member row over its
+    own finite samples; ``lim_r = fp32(reject) * s_r``, one fp32 product.  A
+    complete column ``t`` (every member finite) is an incident column when
+    any member has ``fabs(fp32(x_rt - c_r)) > lim_r``, all in fp32; a
+    comparison against a NaN limit is false, and a constant row (``s = 0``,
+    every deviation 0) rejects nothing.  ``reject <= 0``, NaN or +inf rejects
+    nothing.  Breakdown guard: a group with ``2 * rejected > complete``
+    rejects nothing (``rejected = 0``): the robust start does not describe
+    its bulk.  The incident columns are then masked (NaN) and the group goes
+    through :func:`ref_mvn` itself, so N, the ``valid`` gate ``N >=
+    max(min_n, K + 2)`` and everything after are taken over the columns kept,
+    and with nothing rejected the result is :func:`ref_mvn`'s.  No
+    consistency correction is applied for the trimmed tails."""
+    hist = np.asarray(hist, np.float32)
+    cur = np.asarray(cur, np.float32)
+    rows = np.asarray(rows)
+    lowered = np.asarray(lowered)
+    G, T = rows.shape[0], hist.shape[1]
+    rejected = np.zeros(G, np.int32)
+    if G == 0:
+        return ref_mvn(hist, cur, rows, K, cuts, lowered, min_n) + (rejected,)
+    members = np.unique(rows[:, :K].astype(np.int64))
+    c = np.full(hist.shape[0], np.nan, np.float32)
+    lim = np.full(hist.shape[0], np.inf, np.float32)
+    rj = np.float32(reject)
+    c[members], s, _ = ref_robust_stats(hist[members], T)
+    if rj > 0 and np.isfinite(rj):
+        lim[members] = rj * s
+    own = np.full((1, MVN_MAX_K), -1, np.int32)
+    own[0, :K] = np.arange(K)
+    parts = []
+    for g in range(G):
+        r = rows[g, :K].astype(np.int64)
+        h = hist[r]                                           # a copy
+        complete = np.isfinite(h).all(0)
+        with np.errstate(invalid="ignore", over="ignore"):
+            out = complete & (np.abs(h - c[r, None]) > lim[r, None]).any(0)
+        if 2 * int(out.sum()) <= int(complete.sum()):
+            rejected[g] = out.sum()
+            h[:, out] = np.nan
+        parts.append(ref_mvn(h, cur[r], own, K, cuts, lowered[g:g + 1], min_n))
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(5)) + (rejected,)
+
+
+def mvn_robust(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts,
+               lowered: torch.Tensor, min_n: int, reject: float = MVN_REJECT):
+    """Robust joint detector (K13 + K17): :func:`mvn`'s arguments and
+    ``reject``; returns what :func:`ref_mvn_robust` returns, which is also
+    the CPU path.  On the GPU the members' median / MAD statistics come from
+    ``fm_robust_stats``: one launch over the whole buffer when the groups'
+    ``G * K`` member rows are at least half of its rows, else over a gathered
+    copy of the member rows (scattered back by row id)."""
+    cuts = _mvn_args(hist, T, cur, rows, K, cuts, lowered)
+    G, n = rows.shape[0], cur.shape[1]
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_mvn_robust(hist.numpy()[:, :T], cur.numpy(), rows.numpy(), K,
+                                                                 cuts, lowered.numpy(), min_n, reject))
+    require_native(hist)
+    d = hist.device
+    out = _mvn_outputs(G, n, K, d)
+    rejected = torch.zeros((G,), dtype=torch.int32, device=d)
+    if G == 0 or n == 0:
+        return out + (rejected,)
+    params, dist, flags, cnt, valid = out
+    R = hist.shape[0]
+    stats = torch.empty((R, 3), dtype=torch.float32, device=d)
+    if 2 * G * int(K) >= R:
+        LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), int(T), R, ptr(stats), stream_of(hist))
+    else:
+        ids = torch.unique(rows[:, :K]).long()
+        sub = hist.index_select(0, ids)
+        part = torch.empty((ids.numel(), 3), dtype=torch.float32, device=d)
+        LIB.call("fm_robust_stats", ptr(sub), sub.stride(0), int(T), ids.numel(), ptr(part), stream_of(hist))
+        stats[ids] = part
+    ct = torch.from_numpy(cuts).to(d)
+    rows = rows.contiguous()
+    LIB.call("fm_mvn_robust", ptr(hist), hist.stride(0), int(T), R, ptr(cur), cur.stride(0), n, ptr(rows), G, int(K),
+             ptr(ct), ptr(lowered.contiguous()), int(min_n), ptr(stats), float(reject), ptr(params), ptr(dist),
+             ptr(flags), flags.shape[1], ptr(cnt), ptr(valid), ptr(rejected), stream_of(hist))
+    return params, dist, flags, cnt, valid, rejected
 
 
 # --------------------------------------------------------------------------- K13
