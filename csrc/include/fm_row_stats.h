@@ -129,6 +129,8 @@ __device__ __forceinline__ int64_t hist_row(const int* __restrict__ rowmap, int6
 //     slower: 4.10 vs 0.546 ms at 80k rows); duplicates again store the same
 //     bits.
 // Across launches the kernel boundary orders everything.
+// K18 (robust_stats.hip) keeps a row's (median, sigma, n) in a second cache of
+// the same layout under the same protocol, both forms.
 // ---------------------------------------------------------------------------
 template <bool publish>
 __device__ __forceinline__ void row_cache_put(float* __restrict__ cache, unsigned* __restrict__ valid, int64_t p,

@@ -13,117 +13,120 @@
 // The keys and the selection (MSB-first radix passes of up to 11 bits over
 // 2,048 LDS bins) are fm_radix_select.h, shared with K14.  Phase two
 // overwrites the keys with the bits of |x - centre| (non-negative floats are
-// monotone as they are), sums them in fp64 and selects again.
+// monotone as they are), sums them in fp64 and selects again.  The row
+// computation itself is fm_robust_row.h (robust_row_stats).
 //
 // Rows longer than the LDS capacity run the same passes re-reading global
 // memory (no limit on T; not a fast path).  The contract is
 // foremast_amd/ops/misc.py ref_robust_stats; centre and MAD are exact.
+//
+// K18 (fm_robust_stats_cached) is the same row computation over the rows of a
+// device-resident history store: logical row r reads physical row rowmap[r],
+// and the three floats are kept per physical row in a row-statistics cache
+// (fm_row_stats.h: layout, tags and the release / acquire protocol), so a
+// static history is selected once and costs 12 bytes per tick afterwards.
 #include "fm_common.h"
 #include "fm_radix_select.h"
+#include "fm_robust_row.h"
+#include "fm_row_stats.h"
 
 using namespace fm;
 
 namespace {
 
 constexpr int kRobustThreads = 512;
+// workgroups of K18's scan form when the caller names none: two per CU of a
+// 256-CU part, which is what the LDS of a 7-day row lets a CU hold
+constexpr int kRobustScanBlocks = 512;
 
 template <int NT, bool LDS>
 __global__ __launch_bounds__(NT) void robust_stats_kernel(const float* __restrict__ hist, int64_t ld, int T, int64_t R,
                                                           float* __restrict__ out /*[R,3]*/) {
   extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
   __shared__ __attribute__((aligned(16))) unsigned s_bins[kBins];
-  __shared__ unsigned s_sel[3];
-  __shared__ unsigned s_redu[NT / FM_WAVE];
-  __shared__ int s_redi[NT / FM_WAVE];
-  __shared__ double s_redd[NT / FM_WAVE];
+  __shared__ RobustScratch<NT> s_sc;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
-  const float* p = hist + row * ld;
-  RowKeys<NT, LDS> rk{p, T, s_keys, (T + 3) >> 2, false, 0.f};
   for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
-
-  // ---- the row -> keys; finite count and key range
-  int n = 0;
-  unsigned kmin = kMissing, kmax = 0u;
-  auto track = [&](unsigned k) {
-    if (k != kMissing) {
-      ++n;
-      kmin = k < kmin ? k : kmin;
-      kmax = k > kmax ? k : kmax;
-    }
-  };
-  if constexpr (LDS) {
-    int head = (int)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);   // elements before the 16-B boundary
-    if (head > T) head = T;
-    const int nb = (T - head) >> 2, edge = T - 4 * nb;                        // edge = head + tail elements, < 7
-    const float4* b4 = reinterpret_cast<const float4*>(p + head);
-    for (int q = tid; q < nb; q += NT) {
-      const float4 x = b4[q];
-      const uint4 k = make_uint4(enc_key(x.x), enc_key(x.y), enc_key(x.z), enc_key(x.w));
-      track(k.x); track(k.y); track(k.z); track(k.w);
-      s_keys[q] = k;
-    }
-    if (tid < 4 * (rk.nq - nb)) {                                             // head, tail, padding to whole quads
-      unsigned k = kMissing;
-      if (tid < edge) k = enc_key(p[tid < head ? tid : 4 * nb + tid]);
-      track(k);
-      reinterpret_cast<unsigned*>(s_keys)[4 * nb + tid] = k;
-    }
-  } else {
-    rk.sweep(track);
+  float center, sigma;
+  int n;
+  robust_row_stats<NT, LDS>(hist + row * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+  if (tid == 0) {
+    out[row * 3 + 0] = center;
+    out[row * 3 + 1] = sigma;
+    out[row * 3 + 2] = (float)n;
   }
-  n = block_sum<NT>(n, s_redi);                                               // (barriers: keys and bins visible)
-  if (n == 0) {
-    if (tid == 0) {
-      out[row * 3 + 0] = __uint_as_float(0x7FC00000u);
-      out[row * 3 + 1] = __uint_as_float(0x7FC00000u);
-      out[row * 3 + 2] = 0.f;
+}
+
+// K18.  scan == 0: every logical row is computed, a workgroup per row (the
+// grid may be capped: rows are then dealt round-robin), no validity word is
+// read and the entries are recorded with plain stores (cache may be null:
+// nothing is recorded).  scan != 0: the form of hist_scan_cached
+// (fm_row_stats.h) at 512 threads: each thread tests one row's word with an
+// agent-scope acquire load and copies the 12 bytes on a hit; the misses of a
+// pass are compacted into an LDS list and computed one by one by the whole
+// workgroup, thread 0 publishing each with the release store.
+template <int NT, bool LDS>
+__global__ __launch_bounds__(NT) void robust_stats_cached_kernel(const float* __restrict__ hist, int64_t ld, int T,
+                                                                 int64_t R, float* __restrict__ out /*[R,3]*/,
+                                                                 const int* __restrict__ rowmap,
+                                                                 float* __restrict__ cache,
+                                                                 unsigned* __restrict__ valid, int scan) {
+  extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
+  __shared__ __attribute__((aligned(16))) unsigned s_bins[kBins];
+  __shared__ RobustScratch<NT> s_sc;
+  __shared__ int s_list[NT];
+  __shared__ int s_cnt;
+  const int tid = threadIdx.x;
+  const unsigned tag = (unsigned)T;
+  const int64_t wg = blockIdx.x, nwg = gridDim.x;
+  // zero once: every selection hands the bins back zeroed, and a row without
+  // a finite sample never touches them
+  for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
+  float center, sigma;
+  int n;
+  if (!scan) {
+    for (int64_t row = wg; row < R; row += nwg) {
+      const int64_t p = hist_row(rowmap, row);
+      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+      if (tid == 0) {
+        out[row * 3 + 0] = center;
+        out[row * 3 + 1] = sigma;
+        out[row * 3 + 2] = (float)n;
+        if (cache != nullptr) row_cache_put<false>(cache, valid, p, tag, center, sigma, (float)n);
+      }
     }
     return;
   }
-  kmin = block_min_u32<NT>(kmin, s_redu);
-  kmax = ~block_min_u32<NT>(~kmax, s_redu);
-
-  // ---- median
-  unsigned klo, kup;
-  select_middles<NT, LDS>(rk, kmin, kmax, (unsigned)n, s_bins, s_sel, s_redu, klo, kup);
-  const float center = 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
-
-  // ---- deviations: keys, fp64 sum, range
-  double sum = 0.0;
-  unsigned dmin = kMissing, dmax = 0u;
-  auto track_dev = [&](unsigned d) {
-    if (d != kMissing) {
-      sum += (double)__uint_as_float(d);
-      dmin = d < dmin ? d : dmin;
-      dmax = d > dmax ? d : dmax;
+  const int64_t nk = wg < R ? (R - wg + nwg - 1) / nwg : 0;   // rows of this workgroup
+  for (int64_t k0 = 0; k0 < nk; k0 += NT) {
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    if (k0 + tid < nk) {
+      const int64_t row = wg + (k0 + tid) * nwg;
+      const int64_t p = hist_row(rowmap, row);
+      if (__hip_atomic_load(valid + p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == tag) {
+        out[row * 3 + 0] = cache[p * 3 + 0];
+        out[row * 3 + 1] = cache[p * 3 + 1];
+        out[row * 3 + 2] = cache[p * 3 + 2];
+      } else {
+        s_list[atomicAdd(&s_cnt, 1)] = tid;
+      }
     }
-  };
-  if constexpr (LDS) {
-    for (int q = tid; q < rk.nq; q += NT) {
-      const uint4 v = s_keys[q];
-      const uint4 d = make_uint4(dev_key(v.x, center), dev_key(v.y, center), dev_key(v.z, center),
-                                 dev_key(v.w, center));
-      track_dev(d.x); track_dev(d.y); track_dev(d.z); track_dev(d.w);
-      s_keys[q] = d;
+    __syncthreads();
+    const int nm = s_cnt;
+    for (int i = 0; i < nm; ++i) {
+      const int64_t row = wg + (k0 + __builtin_amdgcn_readfirstlane(s_list[i])) * nwg;
+      const int64_t p = hist_row(rowmap, row);
+      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+      if (tid == 0) {
+        out[row * 3 + 0] = center;
+        out[row * 3 + 1] = sigma;
+        out[row * 3 + 2] = (float)n;
+        row_cache_put<true>(cache, valid, p, tag, center, sigma, (float)n);
+      }
     }
-  } else {
-    rk.dev = true;
-    rk.c = center;
-    rk.sweep(track_dev);
-  }
-  sum = block_sum<NT>(sum, s_redd);
-  dmin = block_min_u32<NT>(dmin, s_redu);
-  dmax = ~block_min_u32<NT>(~dmax, s_redu);
-
-  // ---- MAD
-  unsigned dlo, dup;
-  select_middles<NT, LDS>(rk, dmin, dmax, (unsigned)n, s_bins, s_sel, s_redu, dlo, dup);
-  const float mad = 0.5f * __uint_as_float(dlo) + 0.5f * __uint_as_float(dup);
-  if (tid == 0) {
-    out[row * 3 + 0] = center;
-    out[row * 3 + 1] = mad > 0.f ? 1.4826f * mad : 1.2533f * (float)(sum / (double)n);
-    out[row * 3 + 2] = (float)n;
+    __syncthreads();   // the list is rebuilt by the next pass
   }
 }
 
@@ -141,6 +144,39 @@ FM_API int fm_robust_stats(const float* hist, int64_t ld, int T, int64_t R, floa
     hipLaunchKernelGGL((robust_stats_kernel<kRobustThreads, true>), grid, block, lds, stream, hist, ld, T, R, out);
   } else {
     hipLaunchKernelGGL((robust_stats_kernel<kRobustThreads, false>), grid, block, 0, stream, hist, ld, T, R, out);
+  }
+  FM_LAUNCH_CHECK();
+  return 0;
+}
+
+// K18: out [R,3] = fm_robust_stats of the rows hist[rowmap[r], :T] (identity
+// without a row map), with the statistics of physical row p kept in
+// cache[p,3] / valid[p] (tag = T, 0 = invalid; fm_row_stats.h).
+//   expect_miss != 0 or no cache: every row is computed, one workgroup per
+//     logical row (at most `blocks` when blocks > 0), entries recorded with
+//     plain stores;
+//   expect_miss == 0: validity words are tested, hits copy 12 bytes, misses
+//     are computed and published; `blocks` workgroups (<= 0: 512).
+// The hint shapes the launch only: either form gives the same out and leaves
+// every mapped entry valid.  T == 0 has no tag (0 = invalid): such a launch
+// computes its rows (NaN, NaN, 0) and records nothing.
+FM_API int fm_robust_stats_cached(const float* hist, int64_t ld, int T, int64_t R, float* out, const int* rowmap,
+                                  float* cache, unsigned* valid, int expect_miss, int blocks, hipStream_t stream) {
+  if (R <= 0) return 0;
+  if (T < 0 || R > 0x7FFFFFFF || (((uintptr_t)hist) & 3) != 0 || (cache != nullptr && valid == nullptr))
+    return (int)hipErrorInvalidValue;
+  if (T == 0) cache = nullptr;
+  const int scan = (cache != nullptr && expect_miss == 0) ? 1 : 0;
+  int64_t g = scan ? (blocks > 0 ? blocks : kRobustScanBlocks) : (blocks > 0 ? blocks : R);
+  if (g > R) g = R;
+  const dim3 grid((unsigned)g), block(kRobustThreads);
+  if (T <= kRobustLdsKeys) {
+    const size_t lds = (size_t)((T + 3) / 4) * sizeof(uint4);
+    hipLaunchKernelGGL((robust_stats_cached_kernel<kRobustThreads, true>), grid, block, lds, stream, hist, ld, T, R,
+                       out, rowmap, cache, valid, scan);
+  } else {
+    hipLaunchKernelGGL((robust_stats_cached_kernel<kRobustThreads, false>), grid, block, 0, stream, hist, ld, T, R,
+                       out, rowmap, cache, valid, scan);
   }
   FM_LAUNCH_CHECK();
   return 0;

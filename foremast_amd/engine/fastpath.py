@@ -89,6 +89,7 @@ class FastPath(PlanMixin, FetchMixin, ArraysMixin, ModelsMixin, FinishMixin):
         self._fused_par = 0       # which of the two counters the next fused launch appends to
         self._es_plan = None      # (keys, cache lookup) a declined fused cycle hands to es_forecast
         self.fused_steps = 0
+        self.robust_ticks = 0                       # static robust_moving_average_all groups ticked resident
         self.fused_declined: dict[str, int] = {}   # why a forecasting group's cycle took the op-by-op path
         self._col: dict = {}      # column-wise fetched windows of sliding groups (consumed by _arrays)
         self._ring = None         # merged sliding mode: host ring of the newest grid columns

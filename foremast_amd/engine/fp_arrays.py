@@ -48,17 +48,17 @@ class ArraysMixin:
         self._last_groups = g
         return g
 
-    def _scorer(self, aliases: tuple) -> CanaryScorer:
-        sc = self.scorers.get(aliases)
+    def _scorer(self, aliases: tuple, model: str = "moving_average_all") -> CanaryScorer:
+        sc = self.scorers.get((aliases, model))
         if sc is None:
             # XCD-balanced history ranges off in the brain: one scorer serves
             # every group of an alias set, so a split learned on one group's
             # launch steers the next group's, and churn moves the row count;
             # canary e2e with 0.5 % arrivals measured 29.8-31.3 ms/cycle with it
             # vs 26.3-28.3 without (profiles/front_xcd_fraction_ab_r6.jsonl)
-            sc = self.scorers[aliases] = CanaryScorer(
+            sc = self.scorers[(aliases, model)] = CanaryScorer(
                 list(aliases), self.b.cfg, device=self.b.device,
-                xcd_balance=os.environ.get("FM_BRAIN_XCD_BALANCE", "0") == "1")
+                xcd_balance=os.environ.get("FM_BRAIN_XCD_BALANCE", "0") == "1", model=model)
         if len(sc._out) > 8:
             sc._out.clear()
         return sc
@@ -381,8 +381,18 @@ class ArraysMixin:
         dev = self.b.device
         store = self.sliding if p0.sliding else self.static
         ga = self._arrays(works, key if key is not None else ("adhoc",) + p0.group)
+        model = "moving_average_all"
         if any(a != "moving_average_all" for a in p0.algos):
-            return self._score_models(works, now, ga, store)
+            # a static group judged by robust_moving_average_all alone ticks like
+            # the mean/std one, over the store's robust row-statistics cache: a
+            # canary job's history is written once, so its median and MAD are
+            # selected once.  Sliding and mixed-algorithm groups, and every
+            # other model, take the op-by-op path.
+            model = "robust_moving_average_all"
+            if (p0.sliding or any(a != model for a in p0.algos) or M > 16
+                    or os.environ.get("FM_ROBUST_TICK", "1") in ("0", "false")):
+                return self._score_models(works, now, ga, store)
+            self.robust_ticks += 1
         # last-use stamps for idle eviction (max_idle_cycles = 64): refreshed
         # every 16 cycles, not every cycle -- an 80k-row scatter is ~0.25 ms
         # of host time, and a stamp at most 15 cycles old never evicts a live row
@@ -390,7 +400,8 @@ class ArraysMixin:
             store.used[ga.rowmap] = self.cycle
             ga.marked = self.cycle
         n = ga.cur.shape[1]
-        o = self._scorer(p0.aliases).score_resident(store.view_until(ga.hist_end), ga.rm_d, ga.cur_dev, ga.base_d)
+        o = self._scorer(p0.aliases, model).score_resident(store.view_until(ga.hist_end), ga.rm_d, ga.cur_dev,
+                                                           ga.base_d)
         dec = o.decide
         if dev.type == "cuda":
             cap = max(1024, min(R * n, 1 << 16))

@@ -57,7 +57,8 @@ def _ceil4(x: int) -> int:
 
 
 class RowStatsCache:
-    """Per-row (mean, std, n) of a history tensor whose rows are written once
+    """Per-row (mean, std, n) -- or, in a store's second cache, the robust
+    (median, sigma, n) -- of a history tensor whose rows are written once
     and scored many times, kept by the statistics kernels themselves
     (csrc/include/fm_row_stats.h): ``stats[p]`` are the three floats the
     kernel computed for physical row ``p``, ``valid[p]`` the view length they
@@ -119,11 +120,13 @@ class RowStatsCache:
 class HistView:
     """What a scoring launch needs: the buffer view (16-B aligned rows), its
     leading dimension, the logical history length and the row map; for a
-    static store also the row-statistics cache of the buffer."""
+    static store also the row-statistics caches of the buffer: ``cache``
+    holds (mean, std, n), ``rcache`` the robust (median, sigma, n)."""
     hist: torch.Tensor        # [rows, >= T] view into the resident buffer
     ld: int
     T: int
     cache: RowStatsCache | None = None
+    rcache: RowStatsCache | None = None
 
 
 class ResidentHistory:
@@ -140,6 +143,10 @@ class ResidentHistory:
         # static rows are written once and re-scored every cycle: their
         # statistics are cached per row; a sliding window moves every cycle
         self.cache = None if sliding else RowStatsCache(0, self.device)
+        # the robust model's (median, sigma, n) of the same rows (K18): a cache
+        # of its own, with its own view length and dirty count -- a fleet may
+        # tick some groups with each model
+        self.rcache = None if sliding else RowStatsCache(0, self.device)
         self.slot: dict = {}
         self.free: list[int] = []
         self.last_t = np.zeros(0, np.float64)       # time of each row's newest sample (-inf: none)
@@ -184,6 +191,8 @@ class ResidentHistory:
         self.buf = nb
         if self.cache is not None:
             self.cache.grow(new_cap)
+        if self.rcache is not None:
+            self.rcache.grow(new_cap)
         self.free.extend(range(new_cap - 1, cap - 1, -1))
         self.last_t = np.concatenate([self.last_t, np.full(new_cap - cap, -np.inf)])
         self.nlen = np.concatenate([self.nlen, np.zeros(new_cap - cap, np.int64)])
@@ -311,11 +320,13 @@ class ResidentHistory:
         calls this (write_static, release, the checkpoint restore)."""
         if self.cache is not None and len(rows):
             idx = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows), dtype=torch.int64)
-            self.cache.touch(idx.to(self.device))
+            idx = idx.to(self.device)
+            self.cache.touch(idx)
+            self.rcache.touch(idx)
 
     def view(self) -> HistView:
         if not self.sliding:
-            return HistView(self.buf, self.width, max(1, self.max_len), self.cache)
+            return HistView(self.buf, self.width, max(1, self.max_len), self.cache, self.rcache)
         vs = max(0, self.ws // 4 * 4)
         return HistView(self.buf[:, vs:], self.width, self.e - vs)
 

@@ -39,6 +39,7 @@ class CanaryOutputs:
 
 
 MODES = ("front", "fused", "overlap", "serial")
+MODELS = ("moving_average_all", "robust_moving_average_all")
 
 
 class _BoundHist:
@@ -89,8 +90,16 @@ class CanaryScorer:
                  mode: str | None = None, hist_blocks: int = 0, pw_blocks: int = 0, pw_cap_rows: int = 32,
                  front_wgs: tuple[float, float] | None = None, front_queue: bool = True,
                  xcd_balance: bool | None = None, hist_cache: bool = True,
-                 front_hot_wgs: tuple[float, float] | None = None):
-        """``hist_cache`` (and env ``FM_HIST_CACHE``, ``0`` = off): keep each
+                 front_hot_wgs: tuple[float, float] | None = None, model: str = "moving_average_all"):
+        """``model``: what the history statistics ``hs [R, 3]`` are --
+        ``moving_average_all`` (mean, std, n) or ``robust_moving_average_all``
+        (median, 1.4826 MAD or its mean-deviation fallback, n: K13 / K18).  The
+        band centre +/- thr * sigma, the thresholds, bounds, pairwise factor,
+        history gate and service reduce are the same code for both.  The
+        robust model ticks through ``score`` and ``score_resident`` only (no
+        graph capture, split launchers or ``mode="fused"``).
+
+        ``hist_cache`` (and env ``FM_HIST_CACHE``, ``0`` = off): keep each
         history row's (mean, std, n) across ticks where the history has an
         owner that reports its writes -- a static ``ResidentHistory``
         (``score_resident``) or the tensor bound by ``split_launchers`` /
@@ -100,6 +109,12 @@ class CanaryScorer:
         self.mode = mode or ("front" if overlap else "serial")
         if self.mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
+        if model not in MODELS:
+            raise ValueError(f"model must be one of {MODELS}")
+        self.model = model
+        self.robust = model == "robust_moving_average_all"
+        if self.robust and self.mode == "fused":
+            raise ValueError("mode='fused' reads mean/std off the row image: not available for the robust model")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -178,6 +193,8 @@ class CanaryScorer:
         go instead of the scorer's own buffer (one per in-flight tick when
         the consumer of tick k overlaps tick k+1)."""
         R = cur.shape[0]
+        if self.robust:
+            return self._score_robust(hist, base, cur, n_hist, packed_out)
         if not cur.is_cuda:
             if base is not None and base.shape[1] > 0:
                 pv, ps, df = C.pairwise_tests(cur, base, self.pcfg)
@@ -251,6 +268,8 @@ class CanaryScorer:
         R = cur.shape[0]
         has_base = base is not None and base.shape[1] > 0
         if not cur.is_cuda:
+            if self.robust and self.hist_cache and getattr(hview, "rcache", None) is not None:
+                self._store_caches.add(hview.rcache)       # (invalidate_history reaches it on either device)
             hist = hview.hist.index_select(0, rowmap.to(torch.int64))
             return self.score(hist, base if has_base else None, cur, hview.T)
         from ..ops._lib import LIB, ptr, stream_of
@@ -260,6 +279,8 @@ class CanaryScorer:
         o = self._alloc(R, cur.shape[1], slot)
         st = stream_of(cur)
         n = cur.shape[1] + (base.shape[1] if has_base else 0)
+        if self.robust:
+            return self._resident_robust(hview, rowmap, cur, base if has_base else None, o, st)
         # a static store's rows keep their statistics between its writes
         cache = getattr(hview, "cache", None) if self.hist_cache else None
         miss = True
@@ -290,6 +311,97 @@ class CanaryScorer:
         self._decide_services(cur, o, has_base)
         return o
 
+    # -- robust_moving_average_all ------------------------------------------
+    def _score_robust(self, hist, base, cur, n_hist, packed_out) -> CanaryOutputs:
+        """``score`` of the robust model: K13 into ``hs``, the pairwise tests,
+        the decision kernel.  No cache: the tensor has no owner."""
+        R = cur.shape[0]
+        T = hist.shape[1] if n_hist is None else int(n_hist)
+        has_base = base is not None and base.shape[1] > 0
+        if not cur.is_cuda:
+            import numpy as np
+            from ..ops.misc import ref_robust_stats
+            from ..ops.smoothing import ref_band_decide
+            if has_base:
+                pv, ps, df = C.pairwise_tests(cur, base, self.pcfg)
+            else:
+                pv = torch.full((R, C.N_TESTS), float("nan"))
+                ps = pv.clone()
+                df = torch.zeros((R,), dtype=torch.int8)
+            c, s, n = ref_robust_stats(hist.numpy(), T)
+            x = cur.numpy()
+            with np.errstate(invalid="ignore", over="ignore"):
+                up, lo, flags, cnt, sc = ref_band_decide(x, c[:, None], s, self.M, self.thr.numpy(), self.bound.numpy(),
+                                                         self.minlb.numpy(), df.numpy(),
+                                                         self.cfg.pairwise_threshold_factor)
+            # the history gate of the decision kernel: a row without enough
+            # history flags nothing and scores nothing
+            has = torch.from_numpy((n >= self.cfg.min_historical_points) & (n > 0))
+            cnt = torch.where(has, cnt, torch.zeros_like(cnt))
+            sc = torch.where(has, sc, torch.zeros_like(sc))
+            flags = torch.where(has[:, None], flags, torch.zeros_like(flags))
+            valid = has.to(torch.int32) | (torch.from_numpy(np.isfinite(x).any(1)).to(torch.int32) << 1)
+            stats = torch.stack([torch.from_numpy(c), torch.from_numpy(s), up[:, 0], lo[:, 0]], 1)
+            dec = C.DecideResult(stats, flags, cnt, sc, valid)
+            return CanaryOutputs(pv, ps, df, None, dec, C.service_reduce(cnt, sc, valid, self.M))
+        from ..ops._lib import LIB, ptr, stream_of
+        C.check(hist.dim() == 2 and hist.dtype == torch.float32 and (hist.stride(1) == 1 or hist.shape[1] <= 1)
+                and hist.shape[0] == R and 0 <= T <= hist.shape[1],
+                "history must be fp32 [R, >= T] with unit column stride")
+        o = self._alloc(R, cur.shape[1])
+        if packed_out is not None:
+            C.check(packed_out.shape == o.packed.shape and packed_out.is_contiguous()
+                    and packed_out.dtype == torch.float32, "packed_out must be a contiguous fp32 [S, 4] tensor")
+            o = dataclasses.replace(o, packed=packed_out)
+        LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), T, R, ptr(o.hs), stream_of(cur))
+        if has_base:
+            self._pairwise_wide(cur, base, o)
+        self._decide_services(cur, o, has_base)
+        return o
+
+    def _pairwise_wide(self, cur, base, o: CanaryOutputs) -> None:
+        """p-values of windows of any width: the pairwise kernels up to
+        C.PAIRWISE_MAX pooled points, the bucketed / fp64 CPU oracle above."""
+        if cur.shape[1] + base.shape[1] <= C.PAIRWISE_MAX:
+            self._pairwise_into(cur, base, o, combine=False)
+        else:
+            p, s_, _ = C.pairwise_tests(cur, base, self.pcfg)
+            o.pvals.copy_(p)
+            o.pstats.copy_(s_)
+
+    def _resident_robust(self, hview, rowmap, cur, base, o: CanaryOutputs, st: int) -> CanaryOutputs:
+        """``score_resident`` of the robust model on the GPU: K18 fills ``hs``
+        from the store's robust row-statistics cache (selecting only the rows
+        written since their last robust tick), then the pairwise kernels, then
+        the decision kernel, all on the stream of ``cur``."""
+        from ..ops._lib import LIB, ptr
+        R = cur.shape[0]
+        T = hview.T
+        cache = getattr(hview, "rcache", None) if self.hist_cache else None
+        miss = True
+        if cache is not None:
+            self._store_caches.add(cache)
+            miss = cache.expect_miss(T, R)
+        c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
+        # streaming: a workgroup per row; scan: two workgroups per CU (what the
+        # LDS of a 7-day row lets a CU hold), so a batch of arrivals spreads out
+        LIB.call("fm_robust_stats_cached", ptr(hview.hist), hview.ld, T, R, ptr(o.hs), ptr(rowmap), c_stats, c_valid,
+                 int(miss), 0 if miss else 2 * self._cus, st)
+        # (the pairwise tests as their own launches: the role-split front launch
+        # in its all-hit shape over the robust cache measured 4 % slower here,
+        # docs/PERF.md K18, and would have to be kept from ever meeting an
+        # invalid tag, whose row it would fill with mean / std)
+        if base is not None:
+            self._pairwise_wide(cur, base, o)
+        self._decide_services(cur, o, base is not None)
+        if cache is not None:
+            cache.ticked(T)
+        return o
+
+    def _no_robust(self, what: str) -> None:
+        if self.robust:
+            raise ValueError(f"{what} is not available for model='robust_moving_average_all'")
+
     def _front_grid(self, miss: bool) -> tuple[int, int]:
         """(pairwise, history) workgroups of a front launch: ``front_wgs`` per
         CU when the tick streams history rows, ``front_hot_wgs`` when every row
@@ -312,8 +424,8 @@ class CanaryScorer:
     def invalidate_history(self) -> None:
         """Drop every cached row statistic this scorer can reach: the caches of
         the tensors bound by ``split_launchers`` / ``capture_front`` and of the
-        resident stores it has ticked.  The next tick of each recomputes all
-        rows.
+        resident stores it has ticked (a robust scorer: the stores' robust
+        caches).  The next tick of each recomputes all rows.
 
         The caches see a write in two ways only: a ``ResidentHistory`` clears
         the rows it writes itself, and a bound tensor is watched through
@@ -334,6 +446,7 @@ class CanaryScorer:
         the returned outputs finishes the tick; with one buffer set per
         in-flight step, the decision of tick k can run on another stream
         while tick k+1's front kernel runs."""
+        self._no_robust("front_only")
         C.check(cur.is_cuda and self.mode == "front" and base is not None and base.shape[1] > 0
                 and cur.shape[1] + base.shape[1] <= 256, "front_only needs a GPU front-mode tick with a baseline")
         o = self._alloc(cur.shape[0], cur.shape[1], slot)
@@ -360,6 +473,7 @@ class CanaryScorer:
         ``hist._version`` (any torch write) makes the next replay invalidate
         the cache, with a launch of its own ahead of the graph, and stream the
         rows again; for writes torch does not see, :meth:`invalidate_history`."""
+        self._no_robust("capture_front")
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)   # warm / allocate
         torch.cuda.synchronize(cur.device)
         bh = self._bind(hist)
@@ -448,6 +562,7 @@ class CanaryScorer:
         the cache on the front stream and stream the rows again; for writes
         torch does not see, :meth:`invalidate_history`."""
         from ..ops._lib import LIB
+        self._no_robust("split_launchers")
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)    # validate / allocate / warm
         torch.cuda.synchronize(cur.device)
         T = hist.shape[1] if n_hist is None else int(n_hist)
@@ -523,6 +638,7 @@ class CanaryScorer:
         callable producing outputs in ``self._out``.  ``epilogue(outputs)`` is
         captured after the tick (e.g. the verdict all-gather and the host
         copy), so a whole brain step is a single graph launch."""
+        self._no_robust("capture")
         assert cur.is_cuda
         o = self.score(hist, base, cur, n_hist, packed_out)  # warm / allocate
         if epilogue is not None:

@@ -89,6 +89,9 @@ _SIGS: dict[str, list] = {
                       c_void_p],
     # hist ld T R out stream
     "fm_robust_stats": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p],
+    # hist ld T R out rowmap cache valid expect_miss blocks stream
+    "fm_robust_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                               c_void_p],
     # hist ld T R m J k H forecast ldf stats profile stream
     "fm_seasonal_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p,
                            c_void_p, c_void_p],

@@ -358,6 +358,46 @@ def robust_stats(hist: torch.Tensor, T: int) -> tuple[torch.Tensor, torch.Tensor
     return out[:, 0], out[:, 1], out[:, 2].to(torch.int32)
 
 
+# --------------------------------------------------------------------------- K18
+def robust_stats_cached(hist: torch.Tensor, T: int, rowmap: torch.Tensor | None, cache,
+                        expect_miss: bool | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """K18: :func:`robust_stats` of the rows ``hist[rowmap[r], :T]`` (identity
+    without a row map) with the three floats of every physical row kept in
+    ``cache`` (an ``engine.resident.RowStatsCache`` over the rows of ``hist``,
+    or None): a row whose entry carries the tag ``T`` is copied, any other is
+    selected and recorded.  ``expect_miss`` only shapes the launch (None: the
+    cache's own estimate): True computes every row without looking at the
+    cache, False tests every entry.  Whoever writes a row of ``hist`` calls
+    ``cache.touch`` on the same stream.  CPU: :func:`ref_robust_stats` over
+    the mapped rows; the cache is ignored."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [P, >= T]")
+    if rowmap is not None:
+        check(rowmap.dim() == 1 and rowmap.dtype == torch.int32 and rowmap.device == hist.device,
+              "rowmap must be int32 [R] on the device of hist")
+        if rowmap.numel():
+            check(0 <= int(rowmap.min()) and int(rowmap.max()) < hist.shape[0], "rowmap points outside hist")
+    R = hist.shape[0] if rowmap is None else rowmap.numel()
+    if not hist.is_cuda:
+        x = hist.numpy() if rowmap is None else hist.numpy()[rowmap.numpy().astype(np.int64)]
+        c, s, n = ref_robust_stats(x, T)
+        return torch.from_numpy(c), torch.from_numpy(s), torch.from_numpy(n)
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    if cache is not None:
+        check(len(cache) >= hist.shape[0] and cache.valid.device == hist.device,
+              "the cache must cover every row of hist, on its device")
+    out = torch.empty((R, 3), dtype=torch.float32, device=hist.device)
+    if R:
+        miss = (cache is None or cache.expect_miss(int(T), R)) if expect_miss is None else bool(expect_miss)
+        LIB.call("fm_robust_stats_cached", ptr(hist), hist.stride(0), int(T), R, ptr(out), ptr(rowmap),
+                 ptr(cache.stats) if cache is not None else None, ptr(cache.valid) if cache is not None else None,
+                 int(miss), 0, stream_of(hist))
+        if cache is not None:
+            cache.ticked(int(T))
+    return out[:, 0], out[:, 1], out[:, 2].to(torch.int32)
+
+
 # --------------------------------------------------------------------------- K14
 # Most cycles the seasonal model reads (csrc/kernels/seasonal_robust.hip kMaxCycles).
 SEASONAL_MAX_CYCLES = 16
