@@ -3,12 +3,18 @@
 // history gives the mean vector and 2x2 covariance; each current point pair is
 // scored by its Mahalanobis distance d = sqrt(dx' S^-1 dx) and flagged when
 // d > threshold (threshold in sigma units, like the univariate models).
+// A history pair counts when both members are finite; fewer than two pairs
+// give d = NaN and no flag.  S is the covariance with a relative ridge on its
+// diagonal (below); ops/misc.py ref_bivariate is the contract.  T <= 16384.
 //
 // One 256-thread workgroup per pair; both history rows are read once with
 // 16-B loads and kept in registers for the two-pass moments.
 #include "fm_common.h"
 
 using namespace fm;
+
+// ops/misc.py BIVARIATE_RIDGE
+constexpr double kBivariateRidge = 1e-6;
 
 template <int NV>
 __global__ __launch_bounds__(256) void bivariate_kernel(const float* __restrict__ ha, const float* __restrict__ hb,
@@ -55,7 +61,10 @@ __global__ __launch_bounds__(256) void bivariate_kernel(const float* __restrict_
   sb = block_sum<256>(sb, red);
   c = block_sum<256>(c, redi);
   const float ma = c > 0 ? (float)(sa / c) : 0.f, mb = c > 0 ? (float)(sb / c) : 0.f;
-  float vaa = 0.f, vbb = 0.f, vab = 0.f;
+  // fp32 deviations (the rows stay fp32 in registers), their products summed in
+  // fp64: the determinant below cancels to 1e-6 of its terms for a dependent
+  // pair, where fp32 sums (1e-7) would leave it mostly noise.
+  double vaa = 0, vbb = 0, vab = 0;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const float av[4] = {qa[j].x, qa[j].y, qa[j].z, qa[j].w};
@@ -63,20 +72,23 @@ __global__ __launch_bounds__(256) void bivariate_kernel(const float* __restrict_
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (isfinite(av[e])) {
-        const float da = av[e] - ma, db = bv[e] - mb;
+        const float fa = av[e] - ma, fb = bv[e] - mb;
+        const double da = fa, db = fb;
         vaa += da * da; vbb += db * db; vab += da * db;
       }
     }
   }
-  const double saa = block_sum<256>((double)vaa, red), sbb = block_sum<256>((double)vbb, red),
-               sab = block_sum<256>((double)vab, red);
+  const double saa = block_sum<256>(vaa, red), sbb = block_sum<256>(vbb, red), sab = block_sum<256>(vab, red);
   const double den = c > 1 ? (double)(c - 1) : 1.0;
   const double Caa = saa / den, Cbb = sbb / den, Cab = sab / den;
-  double det = Caa * Cbb - Cab * Cab;
-  // regularise a (near-)singular covariance
-  const double eps = 1e-9 * (Caa + Cbb) + 1e-30;
-  if (det < eps * eps) det = (Caa + eps) * (Cbb + eps) - Cab * Cab;
-  const float iaa = (float)(Cbb / det), ibb = (float)(Caa / det), iab = (float)(-Cab / det);
+  // S = C with its diagonal scaled by 1 + ridge (the ridge K12 puts on the
+  // correlation matrix, MVN_RIDGE): positive definite for any C, independent of
+  // the members' units; the 1e-30 keeps a constant member finite.  The inverse
+  // and the quadratic form are fp64: for a dependent pair the three terms cancel
+  // to 1e-6 of their size, which fp32 (6e-8) turned into distances of 0 .. 16
+  // for points 0 .. 5 sigma along the line.
+  const double Saa = Caa * (1.0 + kBivariateRidge) + 1e-30, Sbb = Cbb * (1.0 + kBivariateRidge) + 1e-30;
+  const double det = Saa * Sbb - Cab * Cab;
   const float th = thr[0];
   int cnt = 0;
   for (int i0 = 0; i0 < n; i0 += 256) {
@@ -86,9 +98,9 @@ __global__ __launch_bounds__(256) void bivariate_kernel(const float* __restrict_
       const float xa = ca[p * ld_c + i], xb = cb[p * ld_c + i];
       float d = NAN;
       if (isfinite(xa) && isfinite(xb) && c > 1) {
-        const float da = xa - ma, db = xb - mb;
-        const float q = da * da * iaa + 2.f * da * db * iab + db * db * ibb;
-        d = sqrtf(fmaxf(q, 0.f));
+        const double da = (double)xa - ma, db = (double)xb - mb;
+        const double q = (da * da * Sbb - 2.0 * da * db * Cab + db * db * Saa) / det;
+        d = (float)sqrt(fmax(q, 0.0));
         f = d > th;
         cnt += f;
       }

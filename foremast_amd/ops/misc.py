@@ -36,7 +36,20 @@ def bivariate(ha: torch.Tensor, hb: torch.Tensor, T: int, ca: torch.Tensor, cb: 
     return params, dist, flags, cnt
 
 
+# Relative ridge on the diagonal of the 2x2 covariance (MVN_RIDGE's role in K12).
+BIVARIATE_RIDGE = 1e-6
+
+
 def ref_bivariate(ha, hb, ca, cb, threshold):
+    """fp64 oracle of K5.  A history pair counts when both members are finite;
+    mean and covariance C (n - 1 in the denominator) over those n pairs.
+    ``S`` = C with each diagonal entry scaled by ``1 + BIVARIATE_RIDGE`` plus
+    1e-30, which is positive definite for any C: on the correlation matrix
+    that is the ridge K12 adds, so the detector does not depend on the
+    members' units, a dependent pair (correlation 1) keeps a direction across
+    its line that is 1e-3 sigma wide, and a constant member stays finite.
+    ``dist = sqrt(dx' S^-1 dx)``, flagged when ``dist > threshold``; NaN and
+    no flag where a current member is not finite or ``n < 2``."""
     ha = np.asarray(ha, np.float64)
     hb = np.asarray(hb, np.float64)
     ok = np.isfinite(ha) & np.isfinite(hb)
@@ -47,14 +60,15 @@ def ref_bivariate(ha, hb, ca, cb, threshold):
     db = np.where(ok, hb - mb[:, None], 0)
     den = np.maximum(n - 1, 1)
     caa, cbb, cab = (da * da).sum(1) / den, (db * db).sum(1) / den, (da * db).sum(1) / den
-    det = caa * cbb - cab * cab
-    eps = 1e-9 * (caa + cbb) + 1e-30
-    det = np.where(det < eps * eps, (caa + eps) * (cbb + eps) - cab * cab, det)
-    xa = ca - ma[:, None]
-    xb = cb - mb[:, None]
-    q = (xa * xa * cbb[:, None] - 2 * xa * xb * cab[:, None] + xb * xb * caa[:, None]) / det[:, None]
-    dist = np.sqrt(np.maximum(q, 0))
-    fin = np.isfinite(ca) & np.isfinite(cb)
+    saa, sbb = caa * (1 + BIVARIATE_RIDGE) + 1e-30, cbb * (1 + BIVARIATE_RIDGE) + 1e-30
+    det = saa * sbb - cab * cab
+    with np.errstate(invalid="ignore", over="ignore"):
+        xa = ca - ma[:, None]
+        xb = cb - mb[:, None]
+        q = (xa * xa * sbb[:, None] - 2 * xa * xb * cab[:, None] + xb * xb * saa[:, None]) / det[:, None]
+        dist = np.sqrt(np.maximum(q, 0))
+    # fewer than two complete pairs: no covariance, so no distance and no flag
+    fin = np.isfinite(ca) & np.isfinite(cb) & (n > 1)[:, None]
     dist = np.where(fin, dist, np.nan)
     flag = fin & (dist > threshold)
     P, m = ca.shape
@@ -891,7 +905,8 @@ def ref_downstream_impact(g: CallGraph, a: np.ndarray, hops: int) -> np.ndarray:
     prev = np.zeros(S, np.float32)
     src = np.repeat(np.arange(S), np.diff(g.rowptr))
     for h in range(hops):
-        val = np.maximum(a[g.col], prev[g.col] if h > 0 else 0) * g.weight
+        # fmax: a NaN score is no evidence and counts as 0, as in the kernel
+        val = np.fmax(a[g.col], prev[g.col] if h > 0 else 0) * g.weight
         out = np.zeros(S, np.float32)
         np.maximum.at(out, src, val.astype(np.float32))
         prev = out
@@ -900,11 +915,13 @@ def ref_downstream_impact(g: CallGraph, a: np.ndarray, hops: int) -> np.ndarray:
 
 def segment_max(v: torch.Tensor, seg: torch.Tensor, K: int) -> torch.Tensor:
     """out[k] = max(0, max of v[i] with seg[i] == k) for non-negative scores
-    (per-cluster aggregate of the impact step)."""
+    (per-cluster aggregate of the impact step).  A NaN value is no evidence
+    and an id outside [0, K) belongs to no segment: both are ignored."""
     check(v.dtype == torch.float32 and seg.dtype == torch.int64 and v.numel() == seg.numel(), "bad segment_max args")
     if not v.is_cuda:
         out = torch.zeros((K,), dtype=torch.float32)
-        return out.scatter_reduce(0, seg, v.clamp(min=0), reduce="amax", include_self=True)
+        ok = (seg >= 0) & (seg < K) & ~torch.isnan(v)
+        return out.scatter_reduce(0, seg[ok], v[ok].clamp(min=0), reduce="amax", include_self=True)
     require_native(v)
     out = torch.empty((K,), dtype=torch.float32, device=v.device)
     LIB.call("fm_segment_max", ptr(v.contiguous()), ptr(seg.contiguous()), v.numel(), K, ptr(out), stream_of(v))
