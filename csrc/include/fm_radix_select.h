@@ -1,10 +1,12 @@
 // Exact order statistics of one row held by a workgroup: order-preserving
-// uint32 keys and an MSB-first radix selection over them.  Shared by K13
+// uint32 keys, the loader that puts a row of them into LDS, an MSB-first radix
+// selection over them, and the median / MAD / sigma routine built on it.
+// What the robust kernels share is here, and stated here only: K13 and K18
 // (robust_stats.hip: median and MAD of a row), K14 (seasonal_robust.hip: MAD
 // of the residuals about a per-phase median profile), K15 (level_shift.hip:
-// medians of the blocks of a row and of the segment behind a level shift) and
-// K16 (trend_robust.hip: the block medians selected together, then median and
-// MAD of the detrended row).
+// the band of the row, or of the segment behind a level shift found over the
+// block medians) and K16 (trend_robust.hip: a line through the block medians,
+// then median and MAD of the detrended row).
 //
 // Keys: negatives have all bits flipped, non-negatives get the sign bit set.
 // NaN / +-inf become the key 0xFFFFFFFF, which no finite value maps to and
@@ -27,10 +29,11 @@ constexpr int kDigitBits = 11;                 // bits settled per pass: three p
 constexpr int kBins = 1 << kDigitBits;
 constexpr int kBinsPerLane = kBins / FM_WAVE;  // wave 0 scans the bins, a run of them per lane
 static_assert(kBinsPerLane % 4 == 0, "a lane's bins are read as uint4");
-// The fast path's longest row: 52 KiB of keys, so that a workgroup's LDS (keys,
-// 8 KiB of bins, reduction scratch) stays under the 64 KiB a launch gets
+// The longest row held in LDS: 52 KiB of keys, so that a workgroup's LDS (keys,
+// 8 KiB of bins, reduction scratch) stays within the 64 KiB a launch gets
 // without a raised limit.  foremast_amd/ops/misc.py ROBUST_LDS_KEYS mirrors it.
 constexpr int kRobustLdsKeys = 13312;
+constexpr size_t kLaunchLds = 64 * 1024;
 constexpr unsigned kMissing = 0xFFFFFFFFu;
 
 __device__ __forceinline__ unsigned enc_key(float x) {
@@ -45,6 +48,35 @@ __device__ __forceinline__ float dec_key(unsigned k) {
 __device__ __forceinline__ unsigned dev_key(unsigned k, float c) {
   return k == kMissing ? kMissing : __float_as_uint(fabsf(dec_key(k) - c));
 }
+// the median of a set from its lower and upper middle keys
+__device__ __forceinline__ float mid_value(unsigned klo, unsigned kup) {
+  return 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
+}
+__device__ __forceinline__ float quiet_nan() { return __uint_as_float(0x7FC00000u); }
+
+// A reduction's result, the same in every lane, moved to scalar registers: the
+// branches and loops it steers become scalar too.  For values the code waits
+// for at once (a barrier or a branch follows), so the move hides no latency.
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ unsigned uniform(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ double uniform(double v) {
+  return __hiloint2double(uniform(__double2hiint(v)), uniform(__double2loint(v)));
+}
+
+// LDS scratch of a workgroup's selections: one instance per kernel.  The bins
+// are zero whenever no selection runs: the kernel clears them once, and every
+// selection hands them back zeroed.
+template <int NT>
+struct SelectScratch {
+  alignas(16) unsigned bins[kBins];
+  unsigned sel[3];
+  unsigned redu[NT / FM_WAVE];
+  int redi[NT / FM_WAVE];
+  double redd[NT / FM_WAVE];
+  __device__ __forceinline__ void clear_bins() {             // no barrier
+    for (int i = threadIdx.x; i < kBins; i += NT) bins[i] = 0u;
+  }
+};
 
 template <int NT>
 __device__ __forceinline__ unsigned block_min_u32(unsigned v, unsigned* scratch) {
@@ -58,172 +90,78 @@ __device__ __forceinline__ unsigned block_min_u32(unsigned v, unsigned* scratch)
   return r;
 }
 
-// The keys of one row: the LDS copy (LDS) or the row in global memory, encoded
-// on the way (phase two: as deviations from the centre c).
-template <int NT, bool LDS>
-struct RowKeys {
-  const float* p;
-  int T;
-  uint4* k4;
-  int nq;
-  bool dev;
-  float c;
-  template <class F>
-  __device__ __forceinline__ void sweep(F f) const {
-    if constexpr (LDS) {
-      for (int q = threadIdx.x; q < nq; q += NT) {
-        const uint4 v = k4[q];
-        f(v.x); f(v.y); f(v.z); f(v.w);
-      }
-    } else {
-      for (int i = threadIdx.x; i < T; i += NT) {
-        unsigned k = enc_key(p[i]);
-        if (dev) k = dev_key(k, c);
-        f(k);
-      }
-    }
+// The smallest and largest of a set of finite keys
+struct KeyRange {
+  unsigned min = kMissing, max = 0u;
+  __device__ __forceinline__ void add(unsigned k) {
+    min = k < min ? k : min;
+    max = k > max ? k : max;
   }
 };
-
-// A run of keys in LDS with key i at word i: the words [lo, hi) of kw, any
-// bounds (K15: the row sits at its global alignment, and a block of it or the
-// segment behind a level shift starts at any word).  The sweep reads whole
-// quads and masks the words outside the run as missing, so every lane of a
-// wave stays in it together.  dev: the keys are taken as deviations from c
-// on the fly, which leaves the raw keys in place for a later selection.
+// The threads' ranges folded over the workgroup in one round of barriers
+// (redi, free between two block sums, carries the maxima)
 template <int NT>
-struct SpanKeys {
-  const unsigned* kw;
-  int lo, hi;
-  bool dev;
-  float c;
-  template <class F>
-  __device__ __forceinline__ void sweep(F f) const {
-    const uint4* k4 = reinterpret_cast<const uint4*>(kw);
-    for (int q = (lo >> 2) + (int)threadIdx.x, qe = (hi + 3) >> 2; q < qe; q += NT) {
-      const uint4 v = k4[q];
-      const unsigned e[4] = {v.x, v.y, v.z, v.w};
+__device__ __forceinline__ KeyRange block_range(KeyRange r, SelectScratch<NT>* sc) {
+  const unsigned lo = wave_min(r.min);
+  if (lane_id() == 0) sc->redu[wave_id()] = lo;
+  const unsigned hi = wave_max(r.max);
+  if (lane_id() == 0) sc->redi[wave_id()] = (int)hi;
+  __syncthreads();
+  r.min = sc->redu[0];
+  r.max = (unsigned)sc->redi[0];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int w = 4 * q + j;
-        unsigned k = (w >= lo && w < hi) ? e[j] : kMissing;
-        if (dev) k = dev_key(k, c);
-        f(k);
-      }
-    }
+  for (int w = 1; w < NT / FM_WAVE; ++w) {
+    const unsigned a = sc->redu[w], b = (unsigned)sc->redi[w];
+    r.min = a < r.min ? a : r.min;
+    r.max = b > r.max ? b : r.max;
   }
-};
-
-// Key of rank k (0-based) among the n finite keys, all within [kmin, kmax].
-// cnt = how many keys equal it, resid = rank k inside that run.  bins[kBins]
-// is zero on entry and on return.  Keys is any source with a sweep(f) that
-// hands every key to f, the lanes of a wave together.
-template <int NT, class Keys>
-__device__ __forceinline__ unsigned radix_select_keys(const Keys& rk, unsigned kmin, unsigned kmax, unsigned k,
-                                                      unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
-                                                      unsigned& cnt) {
-  int hi = kmin == kmax ? 32 : __clz(kmin ^ kmax);            // leading bits shared by every finite key
-  unsigned pref = hi == 0 ? 0u : (hi == 32 ? kmin : (kmin & (~0u << (32 - hi))));
-  cnt = n;
-  while (hi < 32) {
-    const int w = 32 - hi < kDigitBits ? 32 - hi : kDigitBits, shift = 32 - hi - w;
-    const unsigned mask = hi == 0 ? 0u : (~0u << (32 - hi)), dm = (1u << w) - 1u;
-    rk.sweep([&](unsigned key) {
-      const bool m = ((key ^ pref) & mask) == 0u;
-      const unsigned d = (key >> shift) & dm;
-      const unsigned long long act = __ballot(m);
-      if (act == 0ull) return;
-      // the lanes that share the first matching lane's digit make one add (a
-      // row of ties would serialise 64 adds on one bin); the rest add singly
-      const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
-      const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, leader);
-      const bool same = m && d == d0;
-      const unsigned long long grp = __ballot(same);
-      if (lane_id() == leader) atomicAdd(&bins[d0], (unsigned)__popcll(grp));
-      else if (m && !same) atomicAdd(&bins[d], 1u);
-    });
-    __syncthreads();
-    if (wave_id() == 0) {
-      const int l = lane_id();
-      unsigned* mine = bins + l * kBinsPerLane;
-      unsigned s = 0u;
-#pragma unroll
-      for (int j = 0; j < kBinsPerLane / 4; ++j) {
-        const uint4 c = reinterpret_cast<const uint4*>(mine)[j];
-        s += c.x + c.y + c.z + c.w;
-      }
-      const unsigned inc = wave_incl_sum(s), exc = inc - s;
-      if (exc <= k && k < inc) {                               // one lane: the missing keys sort last
-        unsigned r = k - exc, b = 0u, cc = mine[0];
-        while (r >= cc) { r -= cc; ++b; cc = mine[b]; }
-        sel[0] = pref | (((unsigned)(l * kBinsPerLane) + b) << shift);
-        sel[1] = r;
-        sel[2] = cc;
-      }
-#pragma unroll
-      for (int j = 0; j < kBinsPerLane / 4; ++j) reinterpret_cast<uint4*>(mine)[j] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __syncthreads();
-    pref = sel[0];
-    k = sel[1];
-    cnt = sel[2];
-    hi += w;
-  }
-  resid = k;
-  return pref;
+  __syncthreads();
+  return KeyRange{uniform(r.min), uniform(r.max)};
 }
 
-template <int NT, bool LDS>
-__device__ __forceinline__ unsigned radix_select(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned k,
-                                                 unsigned n, unsigned* bins, unsigned* sel, unsigned& resid,
-                                                 unsigned& cnt) {
-  return radix_select_keys<NT>(rk, kmin, kmax, k, n, bins, sel, resid, cnt);
-}
-
-// Lower and upper middle keys of the n finite keys.
-template <int NT, class Keys>
-__device__ __forceinline__ void select_middles_keys(const Keys& rk, unsigned kmin, unsigned kmax, unsigned n,
-                                                    unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
-                                                    unsigned& up) {
-  unsigned resid, cnt;
-  lo = radix_select_keys<NT>(rk, kmin, kmax, (n - 1u) >> 1, n, bins, sel, resid, cnt);
-  up = lo;
-  if ((n & 1u) == 0u && resid + 1u >= cnt) {                   // the run of lo ends at the lower middle
-    unsigned above = kMissing;
-    rk.sweep([&](unsigned key) { if (key > lo && key < above) above = key; });
-    up = block_min_u32<NT>(above, redu);
-  }
-}
-template <int NT, bool LDS>
-__device__ __forceinline__ void select_middles(const RowKeys<NT, LDS>& rk, unsigned kmin, unsigned kmax, unsigned n,
-                                               unsigned* bins, unsigned* sel, unsigned* redu, unsigned& lo,
-                                               unsigned& up) {
-  select_middles_keys<NT>(rk, kmin, kmax, n, bins, sel, redu, lo, up);
-}
-
-// ---------------------------------------------------------------------------
-// A row held in LDS at its global alignment (K15, K16): key i at word a + i
-// with a = (address / 4) & 3 of the row's first sample, so that a 16-B global
-// load and its 16-B LDS store are aligned together whatever the row's
-// alignment, and a block of the row is a run of words.  The words before and
-// behind the row in its first and last quad hold the missing key.
-
-// The row p[0..T) -> keys in place; adds this thread's finite count to n and
-// folds its keys into [kmin, kmax].  No barrier: reduce n (block_sum) before
-// the keys are read.
-template <int NT>
-__device__ __forceinline__ void load_row_keys(const float* p, int T, int a, uint4* keys, int& n, unsigned& kmin,
-                                              unsigned& kmax) {
-  const int tid = threadIdx.x;
-  const int nq = (a + T + 3) >> 2;
-  unsigned* kw = reinterpret_cast<unsigned*>(keys);
-  auto track = [&](unsigned k) {
+// What a thread gathers while keys are made: the finite count and the range
+// (phase one), or the fp64 sum of the deviations and their range (phase two).
+struct RowTally {
+  int n = 0;
+  KeyRange range;
+  __device__ __forceinline__ void operator()(unsigned k) {
     if (k != kMissing) {
       ++n;
-      kmin = k < kmin ? k : kmin;
-      kmax = k > kmax ? k : kmax;
+      range.add(k);
     }
-  };
+  }
+};
+struct DevTally {
+  double sum = 0.0;
+  KeyRange range;
+  __device__ __forceinline__ void operator()(unsigned d) {
+    if (d != kMissing) {
+      sum += (double)__uint_as_float(d);
+      range.add(d);
+    }
+  }
+};
+
+// ---------------------------------------------------------------------------
+// A row held in LDS at its global alignment: key i at word a + i with a =
+// (address / 4) & 3 of the row's first sample, so that a 16-B global load and
+// its 16-B LDS store are aligned together whatever the row's alignment (the
+// row needs 4-byte alignment only), and a block of the row is a run of words.
+// The words before and behind the row in its first and last quad hold the
+// missing key, so a sweep of whole quads needs no mask.
+__device__ __forceinline__ int row_word(const float* p) { return (int)(((uintptr_t)p >> 2) & 3u); }
+constexpr int row_quads(int a, int T) { return (a + T + 3) >> 2; }
+// dynamic LDS of a row of T keys at any alignment: up to 3 words in front, whole quads
+constexpr size_t row_key_bytes(int T) { return (size_t)((T + 6) / 4) * sizeof(uint4); }
+
+// The row p[0..T) -> keys in place, every key (the missing ones too) handed to
+// track on the way.  No barrier: reduce what track gathered (block_sum)
+// before the keys are read.
+template <int NT, class Track>
+__device__ __forceinline__ void load_row_keys(const float* p, int T, int a, uint4* keys, Track& track) {
+  const int tid = threadIdx.x;
+  const int nq = row_quads(a, T);
+  unsigned* kw = reinterpret_cast<unsigned*>(keys);
   int head = (4 - a) & 3;                                    // samples before the 16-B boundary
   if (head > T) head = T;
   const int nb = (T - head) >> 2;
@@ -249,6 +187,192 @@ __device__ __forceinline__ void load_row_keys(const float* p, int T, int a, uint
   }
 }
 
+// ---------------------------------------------------------------------------
+// Key sources.  sweep(f) hands every key to f, the lanes of a wave together;
+// to_deviations(c, f) turns the source into the keys of |x - c|, handing each
+// to f, after which sweep yields those.
+
+// The whole row in LDS: every quad, unmasked; the deviations replace the keys.
+template <int NT>
+struct LdsRow {
+  uint4* k4;
+  int nq;
+  template <class F>
+  __device__ __forceinline__ void sweep(F&& f) const {
+    for (int q = threadIdx.x; q < nq; q += NT) {
+      const uint4 v = k4[q];
+      f(v.x); f(v.y); f(v.z); f(v.w);
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void to_deviations(float c, F&& f) {
+    for (int q = threadIdx.x; q < nq; q += NT) {
+      const uint4 v = k4[q];
+      const uint4 d = make_uint4(dev_key(v.x, c), dev_key(v.y, c), dev_key(v.z, c), dev_key(v.w, c));
+      f(d.x); f(d.y); f(d.z); f(d.w);
+      k4[q] = d;
+    }
+  }
+};
+
+// The row in global memory (K13's rows beyond kRobustLdsKeys): encoded on the
+// way, after to_deviations as deviations.
+template <int NT>
+struct GlobalRow {
+  const float* p;
+  int T;
+  bool dev = false;
+  float c = 0.f;
+  template <class F>
+  __device__ __forceinline__ void sweep(F&& f) const {
+    for (int i = threadIdx.x; i < T; i += NT) {
+      unsigned k = enc_key(p[i]);
+      if (dev) k = dev_key(k, c);
+      f(k);
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void to_deviations(float centre, F&& f) {
+    dev = true;
+    c = centre;
+    sweep(f);
+  }
+};
+
+// The words [lo, hi) of a row in LDS, any bounds (the row itself, or the
+// segment behind a level shift).  The sweep reads whole quads and masks the
+// words outside the run as missing, so every lane of a wave stays in it
+// together.  The deviations are taken on the fly, which leaves the raw keys in
+// place for a later selection.
+template <int NT>
+struct LdsSpan {
+  const unsigned* kw;
+  int lo, hi;
+  bool dev = false;
+  float c = 0.f;
+  template <class F>
+  __device__ __forceinline__ void sweep(F&& f) const {
+    const uint4* k4 = reinterpret_cast<const uint4*>(kw);
+    for (int q = (lo >> 2) + (int)threadIdx.x, qe = (hi + 3) >> 2; q < qe; q += NT) {
+      const uint4 v = k4[q];
+      const unsigned e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int w = 4 * q + j;
+        unsigned k = (w >= lo && w < hi) ? e[j] : kMissing;
+        if (dev) k = dev_key(k, c);
+        f(k);
+      }
+    }
+  }
+  template <class F>
+  __device__ __forceinline__ void to_deviations(float centre, F&& f) {
+    dev = true;
+    c = centre;
+    sweep(f);
+  }
+};
+
+// ---------------------------------------------------------------------------
+// One key's count into bin d, for every lane with m set; the lanes of a wave
+// call it together.  The lanes that share the first such lane's bin make one
+// add (a row of ties would serialise 64 adds on one bin), the rest add singly.
+// d is read only where m.
+__device__ __forceinline__ void bin_add(unsigned* bins, bool m, unsigned d) {
+  const unsigned long long act = __ballot(m);
+  if (act == 0ull) return;
+  const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
+  const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, leader);
+  const bool same = m && d == d0;
+  const unsigned long long grp = __ballot(same);
+  if (lane_id() == leader) atomicAdd(&bins[d0], (unsigned)__popcll(grp));
+  else if (m && !same) atomicAdd(&bins[d], 1u);
+}
+
+// Key of rank k (0-based) among the n finite keys of rk, all within r.
+// cnt = how many keys equal it, resid = rank k inside that run.
+template <int NT, class Keys>
+__device__ __forceinline__ unsigned radix_select(const Keys& rk, KeyRange r, unsigned k, unsigned n,
+                                                 SelectScratch<NT>* sc, unsigned& resid, unsigned& cnt) {
+  unsigned* bins = sc->bins;
+  int hi = r.min == r.max ? 32 : __clz(r.min ^ r.max);        // leading bits shared by every finite key
+  unsigned pref = hi == 0 ? 0u : (hi == 32 ? r.min : (r.min & (~0u << (32 - hi))));
+  cnt = n;
+  while (hi < 32) {
+    const int w = 32 - hi < kDigitBits ? 32 - hi : kDigitBits, shift = 32 - hi - w;
+    const unsigned mask = hi == 0 ? 0u : (~0u << (32 - hi)), dm = (1u << w) - 1u;
+    rk.sweep([&](unsigned key) { bin_add(bins, ((key ^ pref) & mask) == 0u, (key >> shift) & dm); });
+    __syncthreads();
+    if (wave_id() == 0) {
+      const int l = lane_id();
+      unsigned* mine = bins + l * kBinsPerLane;
+      unsigned s = 0u;
+#pragma unroll
+      for (int j = 0; j < kBinsPerLane / 4; ++j) {
+        const uint4 c = reinterpret_cast<const uint4*>(mine)[j];
+        s += c.x + c.y + c.z + c.w;
+      }
+      const unsigned inc = wave_incl_sum(s), exc = inc - s;
+      if (exc <= k && k < inc) {                               // one lane: the missing keys sort last
+        unsigned rest = k - exc, b = 0u, cc = mine[0];
+        while (rest >= cc) { rest -= cc; ++b; cc = mine[b]; }
+        sc->sel[0] = pref | (((unsigned)(l * kBinsPerLane) + b) << shift);
+        sc->sel[1] = rest;
+        sc->sel[2] = cc;
+      }
+#pragma unroll
+      for (int j = 0; j < kBinsPerLane / 4; ++j) reinterpret_cast<uint4*>(mine)[j] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+    pref = sc->sel[0];                                       // (left in vector registers: the next sweep's
+    k = sc->sel[1];                                          // first loads are issued before these arrive)
+    cnt = sc->sel[2];
+    hi += w;
+  }
+  resid = k;
+  return pref;
+}
+
+// Lower and upper middle keys of the n finite keys of rk, all within r.
+template <int NT, class Keys>
+__device__ __forceinline__ void select_middles(const Keys& rk, KeyRange r, unsigned n, SelectScratch<NT>* sc,
+                                               unsigned& lo, unsigned& up) {
+  unsigned resid, cnt;
+  lo = radix_select(rk, r, (n - 1u) >> 1, n, sc, resid, cnt);
+  up = lo;
+  if ((n & 1u) == 0u && resid + 1u >= cnt) {                   // the run of lo ends at the lower middle
+    unsigned above = kMissing;
+    rk.sweep([&](unsigned key) { if (key > lo && key < above) above = key; });
+    up = block_min_u32<NT>(above, sc->redu);
+  }
+}
+
+// sigma from the n >= 1 deviation keys that rk sweeps now, with their sum over
+// the workgroup and this thread's share of their range: 1.4826 MAD, or 1.2533
+// times the mean deviation where the MAD is zero.
+template <int NT, class Keys>
+__device__ __forceinline__ float mad_sigma(const Keys& rk, unsigned n, double sum, KeyRange mine,
+                                           SelectScratch<NT>* sc) {
+  unsigned dlo, dup;
+  select_middles(rk, block_range(mine, sc), n, sc, dlo, dup);
+  const float mad = 0.5f * __uint_as_float(dlo) + 0.5f * __uint_as_float(dup);
+  return mad > 0.f ? 1.4826f * mad : 1.2533f * (float)(sum / (double)n);
+}
+
+// Median and sigma of the n >= 1 finite keys of rk, all within r.  rk is left
+// as the deviations about the median.
+template <int NT, class Keys>
+__device__ __forceinline__ void median_sigma(Keys& rk, unsigned n, KeyRange r, SelectScratch<NT>* sc, float& center,
+                                             float& sigma) {
+  unsigned klo, kup;
+  select_middles(rk, r, n, sc, klo, kup);
+  center = mid_value(klo, kup);
+  DevTally t;
+  rk.to_deviations(center, t);
+  sigma = mad_sigma(rk, n, uniform(block_sum<NT>(t.sum, sc->redd)), t.range, sc);
+}
+
+// ---------------------------------------------------------------------------
 // The J blocks of L words that start at word lo of kw: f(key, block) for every
 // word of the quads they touch, block outside [0, J) for a word in front of or
 // behind them.  A thread walks its quads with the block and the position in it
@@ -309,41 +433,12 @@ __device__ __forceinline__ float small_median(float* v, int c) {
   return 0.5f * v[(c - 1) >> 1] + 0.5f * v[c >> 1];
 }
 
-// Median and sigma (1.4826 MAD, or the mean-deviation fallback) of the n >= 1
-// finite keys in words [lo, hi) of kw, all within [kmin, kmax].
-template <int NT>
-__device__ __forceinline__ void span_stats(const unsigned* kw, int lo, int hi, unsigned n, unsigned kmin, unsigned kmax,
-                                           unsigned* bins, unsigned* sel, unsigned* redu, double* redd, float& center,
-                                           float& sigma) {
-  SpanKeys<NT> sk{kw, lo, hi, false, 0.f};
-  unsigned klo, kup;
-  select_middles_keys<NT>(sk, kmin, kmax, n, bins, sel, redu, klo, kup);
-  center = 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
-  sk.dev = true;
-  sk.c = center;
-  double sum = 0.0;
-  unsigned dmin = kMissing, dmax = 0u;
-  sk.sweep([&](unsigned d) {
-    if (d != kMissing) {
-      sum += (double)__uint_as_float(d);
-      dmin = d < dmin ? d : dmin;
-      dmax = d > dmax ? d : dmax;
-    }
-  });
-  sum = block_sum<NT>(sum, redd);
-  dmin = block_min_u32<NT>(dmin, redu);
-  dmax = ~block_min_u32<NT>(~dmax, redu);
-  unsigned dlo, dup;
-  select_middles_keys<NT>(sk, dmin, dmax, n, bins, sel, redu, dlo, dup);
-  const float mad = 0.5f * __uint_as_float(dlo) + 0.5f * __uint_as_float(dup);
-  sigma = mad > 0.f ? 1.4826f * mad : 1.2533f * (float)(sum / (double)n);
-}
-
 // ---------------------------------------------------------------------------
-// The middles of up to 16 blocks of a row, all selected in the same passes
-// (K16).  Each block keeps its own prefix and residual rank; a pass settles
+// The middles of up to 16 blocks of a row, all selected in the same passes.
+// Each block keeps its own prefix and residual rank; a pass settles
 // kBatchBits of every block's prefix, block b counting into its own 128 bins
-// at bins[128 b], which is exactly the kBins array of the one-row selection.
+// at bins[128 b], which is exactly the kBins array of the one-row selection,
+// so a pass costs one sweep of the blocks whatever J is.
 constexpr int kBatchBlocks = 16;
 constexpr int kBatchBits = 7;
 constexpr int kBatchBins = 1 << kBatchBits;
@@ -362,16 +457,16 @@ struct BlockSel {
 
 // Lower and upper middle keys of every block b < J with st->n[b] != 0: the J
 // blocks of L words from word lo of kw (sweep_blocks), whose finite keys all
-// lie within [kmin, kmax].  st->n is set and visible on entry; bins[kBins] is
-// zero on entry and on return.
+// lie within r.  st->n is set and visible on entry; bins[kBins] is zero on
+// entry and on return.
 template <int NT>
-__device__ __forceinline__ void select_block_middles(const unsigned* kw, int lo, int L, int J, unsigned kmin,
-                                                     unsigned kmax, unsigned* bins, BlockSel* st) {
+__device__ __forceinline__ void select_block_middles(const unsigned* kw, int lo, int L, int J, KeyRange r,
+                                                     unsigned* bins, BlockSel* st) {
   const int tid = threadIdx.x;
-  int hi = kmin == kmax ? 32 : __clz(kmin ^ kmax);            // leading bits shared by every finite key
+  int hi = r.min == r.max ? 32 : __clz(r.min ^ r.max);        // leading bits shared by every finite key
   if (tid < kBatchBlocks) {
     const unsigned c = st->n[tid];
-    st->lo[tid] = hi == 0 ? 0u : (hi == 32 ? kmin : (kmin & (~0u << (32 - hi))));
+    st->lo[tid] = hi == 0 ? 0u : (hi == 32 ? r.min : (r.min & (~0u << (32 - hi))));
     st->up[tid] = kMissing;
     st->rank[tid] = c == 0u ? 0u : (c - 1u) >> 1;
     st->cnt[tid] = c;
@@ -390,18 +485,8 @@ __device__ __forceinline__ void select_block_middles(const unsigned* kw, int lo,
         live = blk >= 0 && blk < J && st->n[blk] != 0u;
         pref = live ? st->lo[blk] : 0u;
       }
-      const bool m = live && key != kMissing && ((key ^ pref) & mask) == 0u;
-      const unsigned d = ((unsigned)at << kBatchBits) | ((key >> shift) & dm);       // (read only where m)
-      const unsigned long long act = __ballot(m);
-      if (act == 0ull) return;
-      // as in radix_select_keys: the lanes that share the first matching
-      // lane's bin make one add, the rest add singly
-      const int leader = __builtin_amdgcn_readfirstlane(__ffsll((long long)act) - 1);
-      const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, leader);
-      const bool same = m && d == d0;
-      const unsigned long long grp = __ballot(same);
-      if (lane_id() == leader) atomicAdd(&bins[d0], (unsigned)__popcll(grp));
-      else if (m && !same) atomicAdd(&bins[d], 1u);
+      bin_add(bins, live && key != kMissing && ((key ^ pref) & mask) == 0u,
+              ((unsigned)at << kBatchBits) | ((key >> shift) & dm));
     });
     __syncthreads();
     if (wave_id() == 0) {
@@ -418,10 +503,10 @@ __device__ __forceinline__ void select_block_middles(const unsigned* kw, int lo,
       const unsigned k = st->rank[b], pref = st->lo[b];
       const bool live = b < J && st->n[b] != 0u;
       if (live && exc <= k && k < exc + s) {                   // one lane a block
-        unsigned r = k - exc, i = 0u, cc = mine[0];
-        while (r >= cc) { r -= cc; ++i; cc = mine[i]; }
+        unsigned rest = k - exc, i = 0u, cc = mine[0];
+        while (rest >= cc) { rest -= cc; ++i; cc = mine[i]; }
         st->lo[b] = pref | (((unsigned)(part * kBatchBinsPerLane) + i) << shift);
-        st->rank[b] = r;
+        st->rank[b] = rest;
         st->cnt[b] = cc;
       }
 #pragma unroll
@@ -456,6 +541,49 @@ __device__ __forceinline__ void select_block_middles(const unsigned* kw, int lo,
   }
   if (tid < kBatchBlocks && st->up[tid] == kMissing) st->up[tid] = st->lo[tid];
   __syncthreads();
+}
+
+// ---------------------------------------------------------------------------
+// The front K15 and K16 share: a row into LDS and the median of each of its
+// J <= kBatchBlocks blocks of L samples (the last J * L columns, block 0 the
+// oldest).
+struct RowBlocks {
+  int cnt[kBatchBlocks];         // finite samples of each block
+  float median[kBatchBlocks];    // NaN for a block with fewer than max(L / 4, 1) of them
+  BlockSel sel;
+};
+
+// Clears the bins, loads p[0..T) (load_row_keys at word a) and returns its
+// finite count, the same in every thread; 0 = an empty row, and nothing else
+// is done.  Otherwise range = the key range of the row, and rb->cnt[j] and
+// rb->median[j] are set for j < J and visible.
+template <int NT>
+__device__ __forceinline__ int load_row_blocks(const float* p, int T, int a, int L, int J, uint4* keys,
+                                               SelectScratch<NT>* sc, RowBlocks* rb, KeyRange& range) {
+  const int tid = threadIdx.x;
+  const unsigned* kw = reinterpret_cast<const unsigned*>(keys);
+  sc->clear_bins();
+  if (tid < kBatchBlocks) rb->cnt[tid] = 0;
+  RowTally t;
+  load_row_keys<NT>(p, T, a, keys, t);
+  const int n = uniform(block_sum<NT>(t.n, sc->redi));       // (barriers: keys, bins and counts visible)
+  if (n == 0) return 0;
+  range = block_range(t.range, sc);
+  const int lo = a + T - J * L;                              // word of block 0's first key
+  if (J > 0) count_block_keys<NT>(kw, lo, L, J, rb->cnt);
+  __syncthreads();
+  if (tid < kBatchBlocks) {
+    const int need = L / 4 > 1 ? L / 4 : 1;
+    rb->sel.n[tid] = (tid < J && rb->cnt[tid] >= need) ? (unsigned)rb->cnt[tid] : 0u;
+  }
+  __syncthreads();
+  if (J > 0) select_block_middles<NT>(kw, lo, L, J, range, sc->bins, &rb->sel);
+  if (tid < kBatchBlocks) {
+    const BlockSel& s = rb->sel;
+    rb->median[tid] = s.n[tid] != 0u ? mid_value(s.lo[tid], s.up[tid]) : quiet_nan();
+  }
+  __syncthreads();
+  return n;
 }
 
 }  // namespace fm

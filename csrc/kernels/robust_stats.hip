@@ -1,23 +1,11 @@
 // K13 robust history statistics: per-row median and MAD (Hampel band) by an
 // exact MSB-first radix selection, one 512-thread workgroup per row.
 //
-// The row is read from HBM once (16-B loads after a peeled head, so the row
-// needs 4-byte alignment only) and kept in LDS as order-preserving uint32
-// keys: negatives have all bits flipped, non-negatives get the sign bit set.
-// NaN / +-inf become the key 0xFFFFFFFF, which no finite value maps to and
-// which sorts above every finite key, so ranks below the finite count n
-// never see it and the keys need no compaction.  The position of a key in
-// LDS does not matter to a selection: the aligned body is stored first and
-// the peeled head / tail elements behind it.
-//
-// The keys and the selection (MSB-first radix passes of up to 11 bits over
-// 2,048 LDS bins) are fm_radix_select.h, shared with K14.  Phase two
-// overwrites the keys with the bits of |x - centre| (non-negative floats are
-// monotone as they are), sums them in fp64 and selects again.  The row
-// computation itself is fm_robust_row.h (robust_row_stats).
-//
-// Rows longer than the LDS capacity run the same passes re-reading global
-// memory (no limit on T; not a fast path).  The contract is
+// The row is read from HBM once and kept in LDS as the keys of
+// fm_radix_select.h (load_row_keys); median_sigma selects the median,
+// overwrites the keys with the bits of |x - centre|, sums them in fp64 and
+// selects again.  Rows longer than kRobustLdsKeys run the same passes
+// re-reading global memory (no limit on T; not a fast path).  The contract is
 // foremast_amd/ops/misc.py ref_robust_stats; centre and MAD are exact.
 //
 // K18 (fm_robust_stats_cached) is the same row computation over the rows of a
@@ -27,7 +15,6 @@
 // static history is selected once and costs 12 bytes per tick afterwards.
 #include "fm_common.h"
 #include "fm_radix_select.h"
-#include "fm_robust_row.h"
 #include "fm_row_stats.h"
 
 using namespace fm;
@@ -39,18 +26,56 @@ constexpr int kRobustThreads = 512;
 // 256-CU part, which is what the LDS of a 7-day row lets a CU hold
 constexpr int kRobustScanBlocks = 512;
 
+// K18 holds the most static LDS of the family: the scratch and the misses of a
+// scan pass (K13 has the scratch alone)
+static_assert(sizeof(SelectScratch<kRobustThreads>) + (kRobustThreads + 1) * sizeof(int) +
+                      row_key_bytes(kRobustLdsKeys) <= kLaunchLds, "the longest LDS row fits a launch");
+
+// (centre, sigma, finite count) of the keys rk makes of a row, tallied into t
+// on the way; the same in every thread.
+template <int NT, class Keys>
+__device__ __forceinline__ void tallied_stats(Keys& rk, const RowTally& t, SelectScratch<NT>* sc, float& center,
+                                              float& sigma, int& nfin) {
+  nfin = uniform(block_sum<NT>(t.n, sc->redi));               // (barriers: keys and bins visible)
+  if (nfin == 0) {                                            // (the same in every thread)
+    center = sigma = quiet_nan();
+    return;
+  }
+  median_sigma(rk, (unsigned)nfin, block_range(t.range, sc), sc, center, sigma);
+}
+
+// The statistics of p[0..T).  The bins are zero on entry and on return; keys
+// holds row_key_bytes(T) when LDS.  Every thread of the workgroup calls it; all
+// branches around barriers are workgroup-uniform, so it can be called for one
+// row after another: the last reads of keys and scratch sit in front of a
+// barrier that every thread passes before the next row's first write to them.
+template <int NT, bool LDS>
+__device__ __forceinline__ void robust_row_stats(const float* __restrict__ p, int T, uint4* keys,
+                                                 SelectScratch<NT>* sc, float& center, float& sigma, int& nfin) {
+  RowTally t;
+  if constexpr (LDS) {
+    const int a = row_word(p);
+    load_row_keys<NT>(p, T, a, keys, t);
+    LdsRow<NT> rk{keys, row_quads(a, T)};
+    tallied_stats(rk, t, sc, center, sigma, nfin);
+  } else {
+    GlobalRow<NT> rk{p, T};
+    rk.sweep(t);
+    tallied_stats(rk, t, sc, center, sigma, nfin);
+  }
+}
+
 template <int NT, bool LDS>
 __global__ __launch_bounds__(NT) void robust_stats_kernel(const float* __restrict__ hist, int64_t ld, int T, int64_t R,
                                                           float* __restrict__ out /*[R,3]*/) {
   extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
-  __shared__ __attribute__((aligned(16))) unsigned s_bins[kBins];
-  __shared__ RobustScratch<NT> s_sc;
+  __shared__ SelectScratch<NT> s_sc;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
-  for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
+  s_sc.clear_bins();
   float center, sigma;
   int n;
-  robust_row_stats<NT, LDS>(hist + row * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+  robust_row_stats<NT, LDS>(hist + row * ld, T, s_keys, &s_sc, center, sigma, n);
   if (tid == 0) {
     out[row * 3 + 0] = center;
     out[row * 3 + 1] = sigma;
@@ -73,22 +98,21 @@ __global__ __launch_bounds__(NT) void robust_stats_cached_kernel(const float* __
                                                                  float* __restrict__ cache,
                                                                  unsigned* __restrict__ valid, int scan) {
   extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
-  __shared__ __attribute__((aligned(16))) unsigned s_bins[kBins];
-  __shared__ RobustScratch<NT> s_sc;
-  __shared__ int s_list[NT];
+  __shared__ SelectScratch<NT> s_sc;
+  __shared__ int s_list[NT];                                 // the misses of a scan pass
   __shared__ int s_cnt;
   const int tid = threadIdx.x;
   const unsigned tag = (unsigned)T;
   const int64_t wg = blockIdx.x, nwg = gridDim.x;
   // zero once: every selection hands the bins back zeroed, and a row without
   // a finite sample never touches them
-  for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
+  s_sc.clear_bins();
   float center, sigma;
   int n;
   if (!scan) {
     for (int64_t row = wg; row < R; row += nwg) {
       const int64_t p = hist_row(rowmap, row);
-      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, &s_sc, center, sigma, n);
       if (tid == 0) {
         out[row * 3 + 0] = center;
         out[row * 3 + 1] = sigma;
@@ -118,7 +142,7 @@ __global__ __launch_bounds__(NT) void robust_stats_cached_kernel(const float* __
     for (int i = 0; i < nm; ++i) {
       const int64_t row = wg + (k0 + __builtin_amdgcn_readfirstlane(s_list[i])) * nwg;
       const int64_t p = hist_row(rowmap, row);
-      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, s_bins, &s_sc, center, sigma, n);
+      robust_row_stats<NT, LDS>(hist + p * ld, T, s_keys, &s_sc, center, sigma, n);
       if (tid == 0) {
         out[row * 3 + 0] = center;
         out[row * 3 + 1] = sigma;
@@ -140,8 +164,8 @@ FM_API int fm_robust_stats(const float* hist, int64_t ld, int T, int64_t R, floa
   if (T < 0 || R > 0x7FFFFFFF || (((uintptr_t)hist) & 3) != 0) return (int)hipErrorInvalidValue;
   const dim3 grid((unsigned)R), block(kRobustThreads);
   if (T <= kRobustLdsKeys) {
-    const size_t lds = (size_t)((T + 3) / 4) * sizeof(uint4);
-    hipLaunchKernelGGL((robust_stats_kernel<kRobustThreads, true>), grid, block, lds, stream, hist, ld, T, R, out);
+    hipLaunchKernelGGL((robust_stats_kernel<kRobustThreads, true>), grid, block, row_key_bytes(T), stream, hist, ld, T,
+                       R, out);
   } else {
     hipLaunchKernelGGL((robust_stats_kernel<kRobustThreads, false>), grid, block, 0, stream, hist, ld, T, R, out);
   }
@@ -171,9 +195,8 @@ FM_API int fm_robust_stats_cached(const float* hist, int64_t ld, int T, int64_t 
   if (g > R) g = R;
   const dim3 grid((unsigned)g), block(kRobustThreads);
   if (T <= kRobustLdsKeys) {
-    const size_t lds = (size_t)((T + 3) / 4) * sizeof(uint4);
-    hipLaunchKernelGGL((robust_stats_cached_kernel<kRobustThreads, true>), grid, block, lds, stream, hist, ld, T, R,
-                       out, rowmap, cache, valid, scan);
+    hipLaunchKernelGGL((robust_stats_cached_kernel<kRobustThreads, true>), grid, block, row_key_bytes(T), stream, hist,
+                       ld, T, R, out, rowmap, cache, valid, scan);
   } else {
     hipLaunchKernelGGL((robust_stats_cached_kernel<kRobustThreads, false>), grid, block, 0, stream, hist, ld, T, R,
                        out, rowmap, cache, valid, scan);

@@ -3,12 +3,8 @@
 // residuals about it, one 512-thread workgroup per row.
 //
 // The span (the last J * m columns of the row) is read from HBM once into LDS
-// as the order-preserving keys of fm_radix_select.h.  Unlike K13's loader,
-// key i lands at LDS word a + i with a = (address / 4) & 3 of the span's first
-// sample: a phase is a position, and with that offset a 16-B global load and
-// its 16-B LDS store are aligned together whatever the row's alignment.  The
-// words before and behind the span in its first and last quad hold the
-// missing key.
+// as the keys of fm_radix_select.h, key i at word a + i (load_row_keys): a
+// phase is a position.
 //
 // Raw profile: a thread takes phases p, p + 512, ...; the J keys of a phase
 // sit m words apart (adjacent lanes read adjacent words), are sorted in
@@ -38,6 +34,8 @@ namespace {
 constexpr int kSeasonalThreads = 512;
 constexpr int kMaxCycles = 16;                   // foremast_amd/ops/misc.py SEASONAL_MAX_CYCLES mirrors it
 constexpr int kMaxPeriod = kRobustLdsKeys / 4;   // (J + 2) m <= kRobustLdsKeys with J >= 2
+static_assert(sizeof(SelectScratch<kSeasonalThreads>) + row_key_bytes(kRobustLdsKeys) <= kLaunchLds,
+              "the longest span and a profile behind it fit a launch");
 
 // compare-exchange: the smaller key first
 __device__ __forceinline__ void cex(unsigned& a, unsigned& b) {
@@ -54,49 +52,22 @@ __global__ __launch_bounds__(NT) void seasonal_robust_kernel(const float* __rest
                                                              float* __restrict__ profile /*[R,m] or null*/) {
   constexpr int kPhases = (kMaxPeriod + NT - 1) / NT;        // most phases a thread takes
   extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
-  __shared__ __attribute__((aligned(16))) unsigned s_bins[kBins];
-  __shared__ unsigned s_sel[3];
-  __shared__ unsigned s_redu[NT / FM_WAVE];
-  __shared__ int s_redi[NT / FM_WAVE];
-  __shared__ double s_redd[NT / FM_WAVE];
+  __shared__ SelectScratch<NT> s_sc;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
   const int N = J * m;                                       // span length
   const float* p = hist + row * ld + (T - N);
-  const int a = (int)(((uintptr_t)p >> 2) & 3u);             // LDS word of key 0
-  const int nq = (a + N + 3) >> 2;
+  const int a = row_word(p);                                 // LDS word of key 0
+  const int nq = row_quads(a, N);
   unsigned* kw = reinterpret_cast<unsigned*>(s_keys);
-  float* prof = reinterpret_cast<float*>(m <= kBins ? s_bins : kw + 4 * nq);   // [m]: raw, then smoothed
+  float* prof = reinterpret_cast<float*>(m <= kBins ? s_sc.bins : kw + 4 * nq);   // [m]: raw, then smoothed
 
-  // ---- the span -> keys in place; finite count
+  // ---- the span -> keys in place; finite count (the key range is not needed)
   int n = 0;
-  {
-    int head = (4 - a) & 3;                                  // samples before the 16-B boundary
-    if (head > N) head = N;
-    const int nb = (N - head) >> 2;
-    const float4* b4 = reinterpret_cast<const float4*>(p + head);
-    uint4* d4 = s_keys + ((a + head) >> 2);
-    for (int q = tid; q < nb; q += NT) {
-      const float4 x = b4[q];
-      const uint4 key = make_uint4(enc_key(x.x), enc_key(x.y), enc_key(x.z), enc_key(x.w));
-      n += (key.x != kMissing) + (key.y != kMissing) + (key.z != kMissing) + (key.w != kMissing);
-      d4[q] = key;
-    }
-    // every word the body leaves out lies in the first or the last quad: a
-    // head / tail sample, or padding in front of / behind the span
-    if (tid < (nq > 1 ? 8 : 4)) {
-      const int w = tid < 4 ? tid : 4 * (nq - 1) + (tid - 4);
-      const int i = w - a;
-      if (i < head || i >= head + 4 * nb) {
-        unsigned key = kMissing;
-        if (i >= 0 && i < N) key = enc_key(p[i]);
-        n += key != kMissing;
-        kw[w] = key;
-      }
-    }
-  }
-  n = block_sum<NT>(n, s_redi);                              // (barriers: keys visible)
-  const float qnan = __uint_as_float(0x7FC00000u);
+  auto count = [&](unsigned k) { n += k != kMissing; };
+  load_row_keys<NT>(p, N, a, s_keys, count);
+  n = uniform(block_sum<NT>(n, s_sc.redi));                  // (barriers: keys visible)
+  const float qnan = quiet_nan();
   if (n == 0) {
     for (int h = tid; h < H; h += NT) forecast[row * ldf + h] = qnan;
     if (profile != nullptr)
@@ -182,8 +153,7 @@ __global__ __launch_bounds__(NT) void seasonal_robust_kernel(const float* __rest
   }
 
   // ---- residuals about the profile: keys, fp64 sum, range
-  double sum = 0.0;
-  unsigned dmin = kMissing, dmax = 0u;
+  DevTally dev;
   {
     // word w holds span index w - a: its phase, carried along instead of divided out
     const int stepm = (4 * NT) % m;
@@ -196,11 +166,8 @@ __global__ __launch_bounds__(NT) void seasonal_robust_kernel(const float* __rest
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (e[j] != kMissing) {
-          const unsigned d = __float_as_uint(fabsf(dec_key(e[j]) - prof[ph]));
-          sum += (double)__uint_as_float(d);
-          dmin = d < dmin ? d : dmin;
-          dmax = d > dmax ? d : dmax;
-          e[j] = d;
+          e[j] = dev_key(e[j], prof[ph]);
+          dev(e[j]);
         }
         if (++ph == m) ph = 0;
       }
@@ -209,18 +176,14 @@ __global__ __launch_bounds__(NT) void seasonal_robust_kernel(const float* __rest
       if (ph0 >= m) ph0 -= m;
     }
   }
-  sum = block_sum<NT>(sum, s_redd);                          // (barriers: the last read of the profile is behind)
-  for (int i = tid; i < kBins; i += NT) s_bins[i] = 0u;
-  dmin = block_min_u32<NT>(dmin, s_redu);
-  dmax = ~block_min_u32<NT>(~dmax, s_redu);                  // (barriers: bins clear)
+  const double sum = uniform(block_sum<NT>(dev.sum, s_sc.redd));   // (barriers: the last read of the profile is behind)
+  s_sc.clear_bins();                                         // (made visible by the barriers of mad_sigma's range)
 
-  // ---- MAD
-  const RowKeys<NT, true> rk{p, N, s_keys, nq, false, 0.f};
-  unsigned dlo, dup;
-  select_middles<NT, true>(rk, dmin, dmax, (unsigned)n, s_bins, s_sel, s_redu, dlo, dup);
-  const float mad = 0.5f * __uint_as_float(dlo) + 0.5f * __uint_as_float(dup);
+  // ---- MAD: the padding words hold the missing key, so the span is swept as a whole row
+  const LdsRow<NT> rk{s_keys, nq};
+  const float sigma = mad_sigma(rk, (unsigned)n, sum, dev.range, &s_sc);
   if (tid == 0) {
-    stats[row * 2 + 0] = mad > 0.f ? 1.4826f * mad : 1.2533f * (float)(sum / (double)n);
+    stats[row * 2 + 0] = sigma;
     stats[row * 2 + 1] = (float)n;
   }
 }
@@ -242,7 +205,8 @@ FM_API int fm_seasonal_robust(const float* hist, int64_t ld, int T, int64_t R, i
   if (R <= 0) return 0;
   // keys: the span plus up to 3 words in front, in whole quads; behind them
   // the profile when the bin array is too short for it
-  const size_t lds = ((size_t)((J * m + 6) / 4) * 4 + (m > kBins ? (size_t)m : 0)) * sizeof(unsigned);
+  const size_t lds = row_key_bytes(J * m) + (m > kBins ? (size_t)m : 0) * sizeof(float);
+  if (lds + sizeof(SelectScratch<kSeasonalThreads>) > kLaunchLds) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL((seasonal_robust_kernel<kSeasonalThreads>), dim3((unsigned)R), dim3(kSeasonalThreads), lds, stream,
                      hist, ld, T, m, J, k, H, forecast, ldf, stats, profile);
   FM_LAUNCH_CHECK();

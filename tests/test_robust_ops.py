@@ -223,8 +223,8 @@ def _check(got, x, T, what):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("T,R", [(1, 37), (2, 37), (3, 37), (63, 37), (64, 37), (65, 37), (255, 37), (256, 37),
-                                 (257, 37), (1000, 37), (4099, 37), (10080, 37), (MI.ROBUST_LDS_KEYS + 3, 5),
-                                 (1000, 1), (257, 700)])
+                                 (257, 37), (1000, 37), (4099, 37), (10080, 37), (MI.ROBUST_LDS_KEYS, 5),
+                                 (MI.ROBUST_LDS_KEYS + 3, 5), (1000, 1), (257, 700)])
 def test_gpu_robust_stats_matches_oracle(cuda, T, R):
     """Kernel == contract: centre and n equal as floats (-0 == +0), sigma equal
     where MAD > 0 and within rtol 1e-6 on the fp64-mean fallback.  Rows cycle

@@ -132,6 +132,23 @@ def test_gpu_global_memory_path(cuda):
 
 
 @pytest.mark.gpu
+def test_gpu_longest_lds_row(cuda):
+    """T = ROBUST_LDS_KEYS, the launch with the most LDS in the family, on a
+    view that starts at column 1 of an odd-stride buffer (the key array takes
+    its extra quad): cold in the scan form (every row a miss) and with no
+    cache, against ref_robust_stats."""
+    T, R = MI.ROBUST_LDS_KEYS, 3
+    x = _rows(R, T, 6)
+    x[0, 17] = 3.0                                            # (not all missing: three rows, three kinds)
+    buf = np.full((R, T + 3), 1e9, np.float32)
+    buf[:, 1:1 + T] = x
+    view = torch.from_numpy(buf).to(cuda)[:, 1:]
+    assert view.data_ptr() % 16 == 4 and view.stride(0) % 2 == 1
+    _check(MI.robust_stats_cached(view, T, None, RowStatsCache(R, cuda), expect_miss=False), x, T, "scan form")
+    _check(MI.robust_stats_cached(view, T, None, None), x, T, "no cache")
+
+
+@pytest.mark.gpu
 def test_gpu_hits_do_not_read_history(cuda):
     P, T, R = 40, 37, 90
     x = _rows(P, T, 2)

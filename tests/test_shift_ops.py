@@ -244,7 +244,8 @@ def test_aliases_config_and_not_a_forecaster():
 
 # ---------------------------------------------------------------------- GPU
 STEP, NOISE = 60.0, 2.0                                       # a 30 sigma step
-SHAPES = [(32, 4), (64, 4), (97, 6), (77, 8), (200, 24), (47, 12), (10080, 1440), (MI.ROBUST_LDS_KEYS, 832)]
+SHAPES = [(32, 4), (64, 4), (97, 6), (77, 8), (200, 24), (47, 12), (10080, 1440), (MI.ROBUST_LDS_KEYS, 832),
+          (19, 1), (50, 3), (30, 12)]                          # blocks narrower than a quad (J = 16); J = 2: no candidate
 SPECIAL = 12
 
 
