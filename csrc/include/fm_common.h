@@ -30,7 +30,7 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // DPP does the same exchange as a VALU operand modifier, and the gfx950
 // v_permlane16_swap / v_permlane32_swap move whole rows / half-waves:
 //   xor 1, 2  quad_perm [1,0,3,2] / [2,3,0,1]
-//   xor 4     row_shl:4 for lanes with bit 2 clear, row_shr:4 otherwise
+//   xor 4     row_shl:4 for lanes with bit 2 clear, row_shr:4 otherwise (bank mask)
 //   xor 8     row_ror:8 (a rotate by half a row IS the xor)
 //   xor 16    permlane16_swap(v, v): rows {r0,r0,r2,r2} / {r1,r1,r3,r3}
 //   xor 32    permlane32_swap(v, v): halves {lo,lo} / {hi,hi}
@@ -44,9 +44,10 @@ __device__ __forceinline__ unsigned xor_lane_u32(unsigned v) {
   } else if constexpr (S == 2) {
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true);
   } else if constexpr (S == 4) {
-    const unsigned up = (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x104, 0xF, 0xF, true);
-    const unsigned dn = (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x114, 0xF, 0xF, true);
-    return (lane_id() & 4) ? dn : up;
+    // row_shl:4 everywhere, then row_shr:4 written over banks 1 and 3 only
+    // (bank_mask 0xA: the lanes with bit 2 set): no select
+    const int up = __builtin_amdgcn_mov_dpp((int)v, 0x104, 0xF, 0xF, true);
+    return (unsigned)__builtin_amdgcn_update_dpp(up, (int)v, 0x114, 0xF, 0xA, false);
   } else if constexpr (S == 8) {
     return (unsigned)__builtin_amdgcn_mov_dpp((int)v, 0x128, 0xF, 0xF, true);
   } else if constexpr (S == 16) {
@@ -65,6 +66,13 @@ __device__ __forceinline__ T dpp_mov(T old, T x) {
   static_assert(sizeof(T) == 4, "32-bit");
   return __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_update_dpp(
       (int)__builtin_bit_cast(unsigned, old), (int)__builtin_bit_cast(unsigned, x), CTRL, 0xF, 0xF, false));
+}
+
+// DPP move whose control gives every lane a valid source (quad_perm, row_ror).
+template <int CTRL, typename T>
+__device__ __forceinline__ T dpp_mov_all(T x) {
+  static_assert(sizeof(T) == 4, "32-bit");
+  return __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_mov_dpp((int)__builtin_bit_cast(unsigned, x), CTRL, 0xF, 0xF, true));
 }
 
 template <int S, typename T>
@@ -90,6 +98,100 @@ __device__ __forceinline__ T xor_lane_any(T v, int s) {
     case 16: return xor_lane<16>(v);
     default: return xor_lane<32>(v);
   }
+}
+
+// A stride-16 / stride-32 pair after ONE permlane swap: lo is the value of the
+// pair's lower lane, hi of its upper lane, and both lanes hold the same
+// (lo, hi).  xor_lane<16/32> is `upper ? lo : hi`; a caller that combines the
+// two symmetrically (lo + hi, a compare-exchange) can skip that select.
+template <int S, typename T>
+__device__ __forceinline__ void lane_pair(T v, T& lo, T& hi) {
+  static_assert(S == 16 || S == 32, "permlane swap strides");
+  static_assert(sizeof(T) == 4, "32-bit");
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  if constexpr (S == 16) {
+    const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    lo = __builtin_bit_cast(T, (unsigned)r[0]); hi = __builtin_bit_cast(T, (unsigned)r[1]);
+  } else {
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    lo = __builtin_bit_cast(T, (unsigned)r[0]); hi = __builtin_bit_cast(T, (unsigned)r[1]);
+  }
+}
+
+// Compare-exchange with the partner lane at `stride`: v becomes the pair's
+// smaller value where keep_min, the larger elsewhere (keep_min must differ
+// between the two lanes of a pair).  The multiset of values is preserved; no
+// NaNs.  Strides 16 / 32 take `(lo < hi) == keep_min ? lo : hi` straight from
+// lane_pair: equal values simply trade lanes.
+template <typename T>
+__device__ __forceinline__ void cmpx_lane_any(T& v, int stride, bool keep_min) {
+  if (stride >= 16) {
+    T lo, hi;
+    if (stride == 16) lane_pair<16>(v, lo, hi); else lane_pair<32>(v, lo, hi);
+    v = (lo < hi) == keep_min ? lo : hi;
+  } else {
+    const T ov = xor_lane_any(v, stride);
+    v = (v < ov) == keep_min ? v : ov;
+  }
+}
+// The same for (value, tag) pairs: the multiset of pairs is preserved.  At
+// strides 16 / 32 value and tag are picked by one mask (a tied pair trades
+// both); below, a lane that keeps its own value on a tie while its partner
+// takes that same value would duplicate a pair, so the tag follows only a
+// value that actually changed.
+template <typename T>
+__device__ __forceinline__ void cmpx_lane_any(T& v, int& tag, int stride, bool keep_min) {
+  if (stride >= 16) {
+    T lo, hi;
+    int tlo, thi;
+    if (stride == 16) { lane_pair<16>(v, lo, hi); lane_pair<16>(tag, tlo, thi); }
+    else { lane_pair<32>(v, lo, hi); lane_pair<32>(tag, tlo, thi); }
+    const bool take_lo = (lo < hi) == keep_min;
+    v = take_lo ? lo : hi;
+    tag = take_lo ? tlo : thi;
+  } else {
+    const T ov = xor_lane_any(v, stride);
+    const int ot = xor_lane_any(tag, stride);
+    const T nv = (v < ov) == keep_min ? v : ov;
+    tag = nv != v ? ot : tag;
+    v = nv;
+  }
+}
+
+// Wave-uniform (SGPR) reduction of a 32-bit INTEGER with an exact, commutative
+// op (sum, max): in-row through four DPP operands (xor 1, xor 2, row_ror:4,
+// row_ror:8 -- after the rotates every lane holds its row's total), the four
+// row totals combined on the scalar unit.  8 VALU against wave_sum's 17; the
+// association differs from wave_sum's butterfly, so not for floating point.
+template <typename T, typename Op>
+__device__ __forceinline__ T wave_reduce_uniform(T v, Op op) {
+  static_assert(sizeof(T) == 4, "32-bit");
+  v = op(v, dpp_mov_all<0xB1>(v));
+  v = op(v, dpp_mov_all<0x4E>(v));
+  v = op(v, dpp_mov_all<0x124>(v));
+  v = op(v, dpp_mov_all<0x128>(v));
+  auto rd = [&](int l) { return __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_readlane((int)__builtin_bit_cast(unsigned, v), l)); };
+  return op(op(rd(0), rd(16)), op(rd(32), rd(48)));
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum_uniform(T v) { return wave_reduce_uniform(v, [](T a, T b) { return a + b; }); }
+template <typename T>
+__device__ __forceinline__ T wave_max_uniform(T v) { return wave_reduce_uniform(v, [](T a, T b) { return a > b ? a : b; }); }
+
+// wave_sum of an fp32 with the SAME additions in the same tree (bit-identical
+// result), as a wave-uniform value.  The butterfly's stride-4 and stride-8
+// levels become row_ror:4 / row_ror:8 operands: lane i then adds lane i - 4
+// (i - 8), which is its xor partner for the lanes with bit 2 (bits 2, 3) set,
+// so lanes 12-15 of every row carry the butterfly's value; strides 16 / 32 add
+// lane_pair's lo + hi (a + b == b + a); lane 63 is read out.
+__device__ __forceinline__ float wave_sum_f32_uniform(float v) {
+  v += xor_lane<1>(v); v += xor_lane<2>(v);
+  v += dpp_mov_all<0x124>(v);
+  v += dpp_mov_all<0x128>(v);
+  float lo, hi;
+  lane_pair<16>(v, lo, hi); v = lo + hi;
+  lane_pair<32>(v, lo, hi); v = lo + hi;
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
 template <typename T>
@@ -122,22 +224,25 @@ __device__ __forceinline__ T wave_min(T v) {
 }
 
 // Inclusive prefix scans over the 64 lanes (Hillis-Steele: row_shr 1,2,4,8
-// inside each 16-lane row, then the row totals carried by permlane swaps).
+// inside each 16-lane row, then the row totals carried by row_bcast:15 / :31).
+template <int V> struct DppC { static constexpr int v = V; };
 template <typename T, typename Op>
 __device__ __forceinline__ T wave_incl_scan_dpp(T v, T ident, Op op) {
   static_assert(sizeof(T) == 4, "32-bit scans");
-  const int l = lane_id();
   v = op(v, dpp_mov<0x111>(ident, v));  // row_shr:1 (lanes with l%16 < 1 read the identity)
   v = op(v, dpp_mov<0x112>(ident, v));
   v = op(v, dpp_mov<0x114>(ident, v));
   v = op(v, dpp_mov<0x118>(ident, v));
-  // row r's total sits in lane 16r+15; carry row 0 -> 1 and row 2 -> 3
-  const T t15 = __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_readlane((int)__builtin_bit_cast(unsigned, v), 15));
-  const T t47 = __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_readlane((int)__builtin_bit_cast(unsigned, v), 47));
-  if ((l >> 4) == 1) v = op(v, t15);
-  if ((l >> 4) == 3) v = op(v, t47);
-  const T t31 = __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_readlane((int)__builtin_bit_cast(unsigned, v), 31));
-  if (l >= 32) v = op(v, t31);
+  // row r's total sits in lane 16r+15: row_bcast:15 hands it to every lane of
+  // row r + 1 (rows 1 and 3 take it, row_mask 0xA), then row_bcast:31 hands
+  // lane 31 (rows 0 + 1) to rows 2 and 3 (row_mask 0xC); masked rows get ident
+  auto bcast = [&](auto ctrl, auto rows) {
+    return __builtin_bit_cast(T, (unsigned)__builtin_amdgcn_update_dpp(
+        (int)__builtin_bit_cast(unsigned, ident), (int)__builtin_bit_cast(unsigned, v), decltype(ctrl)::v,
+        decltype(rows)::v, 0xF, false));
+  };
+  v = op(v, bcast(DppC<0x142>{}, DppC<0xA>{}));
+  v = op(v, bcast(DppC<0x143>{}, DppC<0xC>{}));
   return v;
 }
 

@@ -34,19 +34,23 @@ constexpr float kPad = INFINITY;
 // exchange; they are rebuilt (k, or -1 for pads) before the final 128-merge.
 // That drops the tag exchange and select from 21 of the 27 lane-exchange
 // steps.
-template <int K, bool SPLIT = false>
-__device__ __forceinline__ void bitonic_sort(float (&v)[K], int (&tag)[K]) {
+// TAGGED = false sorts bare keys (the Wilcoxon sort: the sign rides in bit 0
+// of an unsigned key, see pw_compute) and never touches `tag`.
+template <int K, bool SPLIT = false, bool TAGGED = true, typename T>
+__device__ __forceinline__ void bitonic_sort(T (&v)[K], int (&tag)[K]) {
   // Branch-free compare-exchange (selects, no exec-mask branches): strides
   // >= 64 swap registers inside the lane, smaller strides exchange with the
-  // partner lane through DPP / permlane (xor_lane_any).
-  static_assert(!SPLIT || K == 2, "split layout is two 64-lane registers");
+  // partner lane through DPP / permlane (cmpx_lane_any).
+  static_assert(!SPLIT || (K == 2 && TAGGED), "split layout is two tagged 64-lane registers");
   const int lane = lane_id();
 #pragma unroll
   for (int size = 2; size <= 64 * K; size <<= 1) {
-    const bool tags = !SPLIT || size > 64;
-    if (SPLIT && size == 128) {
+    const bool tags = TAGGED && (!SPLIT || size > 64);
+    if constexpr (SPLIT) {
+      if (size == 128) {
 #pragma unroll
-      for (int k = 0; k < K; ++k) tag[k] = v[k] == kPad ? -1 : k;
+        for (int k = 0; k < K; ++k) tag[k] = v[k] == kPad ? -1 : k;
+      }
     }
 #pragma unroll
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
@@ -58,23 +62,17 @@ __device__ __forceinline__ void bitonic_sort(float (&v)[K], int (&tag)[K]) {
           if (p > k) {
             const int i = k * 64 + lane;
             const bool asc = (i & size) == 0;
-            const float a = v[k], b = v[p];
-            const int ta = tag[k], tb = tag[p];
-            const bool alt = a < b;
-            const float mn = alt ? a : b, mx = alt ? b : a;
-            const int tmn = alt ? ta : tb, tmx = alt ? tb : ta;
-            v[k] = asc ? mn : mx; v[p] = asc ? mx : mn;
-            tag[k] = asc ? tmn : tmx; tag[p] = asc ? tmx : tmn;
+            const T a = v[k], b = v[p];
+            // the smaller value goes to register k of an ascending pair
+            const bool first = (a < b) == asc;
+            v[k] = first ? a : b; v[p] = first ? b : a;
+            if (tags) {
+              const int ta = tag[k], tb = tag[p];
+              tag[k] = first ? ta : tb; tag[p] = first ? tb : ta;
+            }
           }
         }
       } else {
-        float ov[K];
-        int ot[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          ov[k] = xor_lane_any(v[k], stride);
-          ot[k] = tags ? xor_lane_any(tag[k], stride) : 0;
-        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
           const int i = k * 64 + lane;
@@ -82,13 +80,8 @@ __device__ __forceinline__ void bitonic_sort(float (&v)[K], int (&tag)[K]) {
           const bool lower = (lane & stride) == 0;
           // keep the smaller value in the lower lane of an ascending pair
           const bool keep_min = lower == asc;
-          // select min or max of the pair; the tag follows only when the value
-          // actually moved (equal values keep their own tags on both lanes)
-          const bool vlt = v[k] < ov[k];
-          const float mn = vlt ? v[k] : ov[k], mx = vlt ? ov[k] : v[k];
-          const float nv = keep_min ? mn : mx;
-          if (tags) tag[k] = nv != v[k] ? ot[k] : tag[k];
-          v[k] = nv;
+          if (tags) cmpx_lane_any(v[k], tag[k], stride, keep_min);
+          else cmpx_lane_any(v[k], stride, keep_min);
         }
       }
     }
@@ -96,21 +89,22 @@ __device__ __forceinline__ void bitonic_sort(float (&v)[K], int (&tag)[K]) {
 }
 
 // Average (1-based) ranks for a sorted register array whose first n entries are
-// real.  tie_term accumulates sum(t^3 - t) over tie runs; is_end marks the last
-// element of each run (where empirical CDFs are evaluated).
-template <int K>
-__device__ __forceinline__ void avg_ranks(const float (&v)[K], int n, int (&rank2)[K], bool (&is_end)[K],
-                                          int& tie_term) {
+// real.  The return value is this lane's share of the tie term sum(t^3 - t)
+// over tie runs (the caller reduces it, packed with its other integer sums);
+// is_end marks the last element of each run (where empirical CDFs are
+// evaluated).
+template <int K, typename T>
+__device__ __forceinline__ int avg_ranks(const T (&v)[K], int n, int (&rank2)[K], bool (&is_end)[K]) {
   // rank2 = 2 x (1-based average rank) = start + end + 2: exact integers, so
   // rank sums and the tie term sum(t^3 - t) (<= 1024^3 < 2^31) need no doubles.
   const int lane = lane_id();
   int start_idx[K];
   int carry = 0;
-  float last_prev = 0.f;
+  T last_prev = 0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int i = k * 64 + lane;
-    const float prev = lane_prev(v[k], last_prev);
+    const T prev = lane_prev(v[k], last_prev);
     const bool st = (i == 0) || (v[k] != prev);
     int s = st ? i : 0;
     s = wave_incl_max(s, 0);
@@ -120,12 +114,12 @@ __device__ __forceinline__ void avg_ranks(const float (&v)[K], int n, int (&rank
     last_prev = lane_bcast(v[k], 63);
   }
   int carry_e = 0x7fffffff;
-  float next_first = 0.f;
+  T next_first = 0;
   int tl = 0;
 #pragma unroll
   for (int k = K - 1; k >= 0; --k) {
     const int i = k * 64 + lane;
-    const float next = lane_next(v[k], next_first);
+    const T next = lane_next(v[k], next_first);
     const bool en = (i < n) && ((i == n - 1) || (v[k] != next));
     int e = en ? i : 0x7fffffff;
     e = wave_incl_suffix_min(e, 0x7fffffff);
@@ -135,12 +129,16 @@ __device__ __forceinline__ void avg_ranks(const float (&v)[K], int n, int (&rank
     is_end[k] = en;
     rank2[k] = start_idx[k] + e + 2;
     if (i < n && i == start_idx[k]) {
+      // t <= 1024: t^2 - 1 and t both fit the full-rate 24-bit multiplier
       const int t = e - start_idx[k] + 1;
-      tl += t * t * t - t;
+      tl += __mul24(__mul24(t, t) - 1, t);
     }
   }
-  tie_term = wave_sum(tl);
+  return tl;
 }
+
+// Bits needed for an integer sum whose total is at most `bound`.
+constexpr int pw_bits(long long bound) { return bound <= 0 ? 0 : 1 + pw_bits(bound >> 1); }
 
 }  // namespace
 
@@ -187,11 +185,14 @@ template <int K, bool SPLIT = false>
 __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o) {
   // Everything exact is carried in integers (counts, doubled rank sums, tie
   // terms, the KS numerator); only the Welch moments are floating point.
+  // Counts come from ballots (scalar popcounts), the integer sums are reduced
+  // after both sorts, packed into as few words as their bounds allow, and
+  // every reduction result is wave-uniform (only lane 0 writes the row).
   const int lane = lane_id();
   float (&v)[K] = in.v;
   int tag[K];
   float s1 = 0.f, s2 = 0.f;
-  int c12 = 0;  // n1 | n2 << 16
+  int n1 = 0, n2 = 0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int i = k * 64 + lane;
@@ -199,87 +200,123 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
     float x = v[k];
     if (!isfinite(x)) { x = kPad; t = -1; }
     v[k] = x; tag[k] = t;
-    if (t == 0) { s1 += x; c12 += 1; }
-    if (t == 1) { s2 += x; c12 += 1 << 16; }
+    if (t == 0) s1 += x;
+    if (t == 1) s2 += x;
+    n1 += __popcll(__ballot(t == 0));
+    n2 += __popcll(__ballot(t == 1));
   }
-  c12 = wave_sum(c12);
-  const int n1 = c12 & 0xFFFF, n2 = c12 >> 16;
   const int n = n1 + n2;
-  const float m1 = wave_sum(s1) / (float)(n1 > 0 ? n1 : 1), m2 = wave_sum(s2) / (float)(n2 > 0 ? n2 : 1);
+  const float m1 = wave_sum_f32_uniform(s1) / (float)(n1 > 0 ? n1 : 1);
+  const float m2 = wave_sum_f32_uniform(s2) / (float)(n2 > 0 ? n2 : 1);
   float q1 = 0.f, q2 = 0.f;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     if (tag[k] == 0) { const float d = v[k] - m1; q1 += d * d; }
     if (tag[k] == 1) { const float d = v[k] - m2; q2 += d * d; }
   }
-  q1 = wave_sum(q1); q2 = wave_sum(q2);
+  q1 = wave_sum_f32_uniform(q1); q2 = wave_sum_f32_uniform(q2);
 
   // ---- Wilcoxon signed-rank on position-paired differences (zero_method='wilcox')
+  // One unsigned key per pair: (bits(|d|) << 1) | (d > 0).  |d| > 0 or the
+  // +inf pad, so bit 31 of its pattern is clear and the shift loses nothing;
+  // unsigned order of the keys is the order of |d| (fp32 denormals are kept in
+  // this build, .amdhsa_float_denorm_mode_32 = 3, so a float compare tells
+  // subnormal |d| apart exactly as the integer compare does), key >> 1 gives
+  // |d|-equality for the tie runs and key & 1 the sign.  Pads: (+inf << 1).
   constexpr int KW = PwIn<K>::KW;
-  float dv[KW];
-  int dt[KW];
+  constexpr unsigned kPadMag = 0x7F800000u;
+  unsigned dk[KW];
   const int npair = n_cur < n_base ? n_cur : n_base;
-  int cwz = 0;  // nonzero | positive << 10 | zero << 20 (each <= 512)
+  int nw = 0, npos = 0, nzero = 0;
 #pragma unroll
   for (int k = 0; k < KW; ++k) {
     const int j = k * 64 + lane;
-    float d = kPad;
-    int t = -1;
-    if (j < npair) {
-      const float xc = in.pc[k], xb = in.pb[k];
-      if (isfinite(xc) && isfinite(xb)) {
-        const float dd = xc - xb;
-        if (dd != 0.f) { d = fabsf(dd); t = dd > 0.f ? 1 : 0; cwz += 1 + (t << 10); }
-        else cwz += 1 << 20;
-      }
-    }
-    dv[k] = d; dt[k] = t;
+    const float xc = in.pc[k], xb = in.pb[k];
+    const float dd = xc - xb;
+    const bool ok = j < npair && isfinite(xc) && isfinite(xb);
+    const bool nz = ok && dd != 0.f, pos = nz && dd > 0.f;
+    dk[k] = nz ? ((__float_as_uint(fabsf(dd)) << 1) | (pos ? 1u : 0u)) : (kPadMag << 1);
+    nw += __popcll(__ballot(nz));
+    npos += __popcll(__ballot(pos));
+    nzero += __popcll(__ballot(ok && !nz));
   }
-  cwz = wave_sum(cwz);
-  const int nw = cwz & 0x3FF, npos = (cwz >> 10) & 0x3FF, nzero = cwz >> 20;
 
   bitonic_sort<K, SPLIT>(v, tag);
   int rk2[K];
   bool en[K];
-  int tie = 0;
-  avg_ranks<K>(v, n, rk2, en, tie);
+  const int tie_l = avg_ranks<K>(v, n, rk2, en);
 
-  int r1x2 = 0;
+  unsigned r1x2 = 0;
   int dnum = 0;   // max |a1 n2 - a2 n1| over tie-run ends = D n1 n2
   int base12 = 0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    if (tag[k] == 0) r1x2 += rk2[k];
+    if (tag[k] == 0) r1x2 += (unsigned)rk2[k];
     // KS: inclusive prefix counts of both samples along the sorted order, one packed scan
     const int a12 = wave_incl_sum(tag[k] == 0 ? 1 : (tag[k] == 1 ? (1 << 16) : 0)) + base12;
     base12 = lane_bcast(a12, 63);
     if (en[k] && n1 > 0 && n2 > 0) {
       const int a1 = a12 & 0xFFFF, a2 = a12 >> 16;
-      const int dd = abs(a1 * n2 - a2 * n1);
+      const int dd = abs(__mul24(a1, n2) - __mul24(a2, n1));   // counts <= 1024
       dnum = dd > dnum ? dd : dnum;
     }
   }
-  r1x2 = wave_sum(r1x2);
-  dnum = wave_max(dnum);
+  dnum = wave_max_uniform(dnum);
 
-  bitonic_sort<KW>(dv, dt);
+  int dt_unused[KW];
+  bitonic_sort<KW, false, false>(dk, dt_unused);
+  unsigned dmag[KW];
+#pragma unroll
+  for (int k = 0; k < KW; ++k) dmag[k] = dk[k] >> 1;
   int rw2[KW];
   bool ew[KW];
-  int tiew = 0;
-  avg_ranks<KW>(dv, nw, rw2, ew, tiew);
-  int rplus2 = 0;
+  const int tiew_l = avg_ranks<KW>(dmag, nw, rw2, ew);
+  unsigned rplus2 = 0;
 #pragma unroll
   for (int k = 0; k < KW; ++k)
-    if (dt[k] == 1) rplus2 += rw2[k];
-  rplus2 = wave_sum(rplus2);
+    if ((dk[k] & 1u) != 0u) rplus2 += (unsigned)rw2[k];
+
+  // The four integer sums, packed by their bounds at n <= 64 K pooled values
+  // and nw <= 64 KW pairs (what the registers hold): tie <= n^3 - n (one run),
+  // r1x2 <= n (n + 1) (the doubled average ranks of all n values sum to that),
+  // likewise tiew and rplus2 over nw.  K = 1: two words; K = 2 and 4: three;
+  // K >= 8: four.
+  constexpr long long N = 64LL * K, NW = 64LL * KW;
+  constexpr int bTie = pw_bits(N * N * N - N), bR1 = pw_bits(N * (N + 1));
+  constexpr int bTiew = pw_bits(NW * NW * NW - NW), bRp = pw_bits(NW * (NW + 1));
+  static_assert(bTie <= 32 && bTiew <= 32 && bR1 <= 32 && bRp <= 32, "32-bit sums");
+  constexpr bool packA = bTie + bR1 <= 32;                        // tie | r1x2
+  constexpr bool packB = bTiew + bRp <= 32;                       // tiew | rplus2
+  constexpr bool packC = !packA && !packB && bR1 + bRp <= 32;     // r1x2 | rplus2
+  unsigned tie, tiew, r1s, rps;
+  auto lowbits = [](unsigned w, int b) { return b >= 32 ? w : (w & ((1u << (b & 31)) - 1u)); };
+  if constexpr (packA) {
+    const unsigned w = wave_sum_uniform((unsigned)tie_l | (r1x2 << bTie));
+    tie = lowbits(w, bTie); r1s = w >> bTie;
+  } else {
+    tie = wave_sum_uniform((unsigned)tie_l);
+  }
+  if constexpr (packB) {
+    const unsigned w = wave_sum_uniform((unsigned)tiew_l | (rplus2 << bTiew));
+    tiew = lowbits(w, bTiew); rps = w >> bTiew;
+  } else {
+    tiew = wave_sum_uniform((unsigned)tiew_l);
+  }
+  if constexpr (packC) {
+    const unsigned w = wave_sum_uniform(r1x2 | (rplus2 << bR1));
+    r1s = lowbits(w, bR1); rps = w >> bR1;
+  } else {
+    if constexpr (!packA) r1s = wave_sum_uniform(r1x2);
+    if constexpr (!packB) rps = wave_sum_uniform(rplus2);
+  }
 
   // Per-row sufficient statistics; p-values are evaluated one row per THREAD
   // by pvalue_kernel (the double-precision special functions would otherwise
   // run on lane 0 with 63 lanes idle).
   if (lane == 0) {
-    o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * r1x2; o[4] = tie;
+    o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * (double)r1s; o[4] = (double)tie;
     o[5] = (n1 > 0 && n2 > 0) ? (double)dnum / ((double)n1 * n2) : 0.0;
-    o[6] = 0.5 * rplus2; o[7] = tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
+    o[6] = 0.5 * (double)rps; o[7] = (double)tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
     o[12] = npos; o[13] = nzero;
   }
 }

@@ -31,11 +31,14 @@ __device__ __attribute__((noinline)) void eval_test_call(int t, const double* __
 
 // FM_FRONT_TIMING builds (tools/front_timing.py): every workgroup of the
 // front kernel records its start / end on the 100 MHz real-time counter, so
-// the critical role (pairwise or history) of a shape can be read off.
+// the critical role (pairwise or history) of a shape can be read off; a
+// pairwise workgroup also records the barrier between its rank-test rows and
+// its p-values (mark 2; a history workgroup leaves that slot alone).
 #ifdef FM_FRONT_TIMING
-__device__ unsigned long long g_front_t[2 * 8192];
+constexpr int kFtMarks = 3;
+__device__ unsigned long long g_front_t[kFtMarks * 8192];
 #define FM_FT_MARK(k) \
-  do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_front_t[2 * blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+  do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_front_t[kFtMarks * blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define FM_FT_MARK(k) do {} while (0)
 #endif
@@ -130,16 +133,31 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
       pw_row<K>(cur + row * ld_c, base + row * ld_b, n_cur, n_base, suff + row * kSuff);
     }
     __syncthreads();   // this workgroup's suff rows are visible to all its waves
+    FM_FT_MARK(2);
     // local row j -> global row first + (j & 3) + (j >> 2) * stride
     const int64_t span = R > first ? R - first : 0;
     const int nr = (int)(((span + stride - 1) / stride) * 4);
     // wave-sized chunks of (test, 64 rows); the test is wave-uniform so the
     // special-function switch stays a scalar branch (a per-lane test index
-    // made the compiler keep every path live: 256 VGPRs)
+    // made the compiler keep every path live: 256 VGPRs).  Chunks are listed
+    // costliest test first (Welch's incomplete beta, then the Kolmogorov
+    // series, then the erfc tests) and dealt to the four waves back and forth
+    // (0 1 2 3 3 2 1 0 ...), so at one chunk per test the Welch and KS chunks
+    // have a wave each and the four cheap tests pair up.  Wave w of every
+    // co-resident workgroup sits on the same SIMD and all of them reach this
+    // phase together, so the deal is rotated by blockIdx: the Welch chains of
+    // neighbouring workgroups land on different SIMDs.
+    // T_T, T_KS, T_MW, T_KRU, T_WIL, T_FRI, one per nibble from the low end
+    static_assert(T_T == 4 && T_KS == 3 && T_MW == 0 && T_KRU == 2 && T_WIL == 1 && T_FRI == 5, "kByCost");
+    constexpr unsigned kByCost = 0x512034u;
     const int cpt = (nr + 63) >> 6;
-    for (int ci = wave_id(); ci < N_TESTS * cpt; ci += 4) {
-      const int t = __builtin_amdgcn_readfirstlane(ci / cpt);
-      const int j = (ci - t * cpt) * 64 + lane_id();
+    const int slot = (wave_id() + (int)blockIdx.x) & 3;
+    for (int u = 0;; ++u) {
+      const int ci = (u >> 1) * 8 + ((u & 1) ? 7 - slot : slot);
+      if (ci >= N_TESTS * cpt) break;
+      const int tp = ci / cpt;
+      const int t = __builtin_amdgcn_readfirstlane((int)((kByCost >> (4 * tp)) & 7u));
+      const int j = (ci - tp * cpt) * 64 + lane_id();
       const int64_t row = first + (j & 3) + (int64_t)(j >> 2) * stride;
       if (j < nr && row < R) {
         double pv, sv;
@@ -343,7 +361,7 @@ FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, floa
 
 FM_API int fm_front_timing_read(unsigned long long* host, int n) {
 #ifdef FM_FRONT_TIMING
-  if (n > 2 * 8192) n = 2 * 8192;
+  if (n > kFtMarks * 8192) n = kFtMarks * 8192;
   return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_front_t), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
 #else
   (void)host; (void)n;

@@ -3,7 +3,12 @@
 csrc/kernels/tick_front.hip with -DFM_FRONT_TIMING:
 ``python tools/build_native.py --variant NAME:tick_front:-DFM_FRONT_TIMING``,
 load the variant through FOREMAST_HIP_LIB): which role ends the
-kernel at a given shard size, and when the late history workgroups start.
+kernel at a given shard size, when the late history workgroups start, and how
+a pairwise workgroup's time splits between its rank-test rows and its
+p-values (the barrier between the two is the third mark).  The launches
+measured are the scorer's steady ticks: with the row-statistics cache on
+(the default) that is the ``front_hot_wgs`` shape, with ``FM_HIST_CACHE=0``
+the streaming ``front_wgs`` shape given in WGS.
 Prints one JSON object per shape (times in us from the first start)."""
 from __future__ import annotations
 
@@ -25,6 +30,9 @@ from foremast_amd.ops._lib import LIB  # noqa: E402
 ALIASES = ["error5xx", "latency", "traffic", "error4xx", "cpu", "memory", "tomcat_threads", "jvm_heap"]
 
 
+MARKS = 3   # start, end, rows -> p-values barrier (kFtMarks in tick_front.hip)
+
+
 def pct(a, q):
     return round(float(np.percentile(a, q)), 1) if len(a) else None
 
@@ -42,15 +50,19 @@ def main() -> None:
                 front()
             torch.cuda.synchronize()
             cus = torch.cuda.get_device_properties(dev).multi_processor_count
-            nP = min(int(wgs[0] * cus), (S * 8 + 3) // 4)
-            nH = min(int(wgs[1] * cus), S * 8)
+            R = S * 8
+            hot = bool(sc.hist_cache)           # steady ticks expect every row in the cache
+            nP, nH = sc._front_grid(not hot)
+            nP = min(nP, (R + 3) // 4) if nP > 0 else (R + 3) // 4
+            nH = min(nH if nH > 0 else ((R + 255) // 256 if hot else R), R)
             n = nP + nH
-            buf = (ctypes.c_ulonglong * (2 * n))()
-            LIB.call("fm_front_timing_read", ctypes.cast(buf, ctypes.c_void_p), 2 * n)
-            t = np.frombuffer(buf, dtype=np.uint64).astype(np.float64).reshape(n, 2) / 100.0   # 100 MHz -> us
+            buf = (ctypes.c_ulonglong * (MARKS * n))()
+            LIB.call("fm_front_timing_read", ctypes.cast(buf, ctypes.c_void_p), MARKS * n)
+            t = np.frombuffer(buf, dtype=np.uint64).astype(np.float64).reshape(n, MARKS) / 100.0   # 100 MHz -> us
             t0 = t[:, 0].min()
             t -= t0
             p, hh = t[:nP], t[nP:]
+            rows_us, pval_us = p[:, 2] - p[:, 0], p[:, 1] - p[:, 2]
             # per-XCD end of the history role (workgroups are dealt round-robin
             # over the 8 XCDs; the history queue splits rows into 8 XCD ranges),
             # over REPS further launches: is the late XCD always the same one?
@@ -58,17 +70,20 @@ def main() -> None:
             for _ in range(int(os.environ.get("REPS", "6"))):
                 front()
                 torch.cuda.synchronize()
-                LIB.call("fm_front_timing_read", ctypes.cast(buf, ctypes.c_void_p), 2 * n)
-                tt = np.frombuffer(buf, dtype=np.uint64).astype(np.float64).reshape(n, 2) / 100.0
+                LIB.call("fm_front_timing_read", ctypes.cast(buf, ctypes.c_void_p), MARKS * n)
+                tt = np.frombuffer(buf, dtype=np.uint64).astype(np.float64).reshape(n, MARKS) / 100.0
                 tt -= tt[:, 0].min()
                 hx = tt[nP:]
                 xid = np.arange(nH) & 7
                 xe.append([round(float(hx[xid == x, 1].max()), 1) for x in range(8)])
             print(json.dumps({"services": S, "wgs": wgs, "history_end_us_per_xcd": xe}), flush=True)
             print(json.dumps({
-                "services": S, "wgs": wgs, "nP": nP, "nH": nH,
+                "services": S, "wgs": wgs, "hot": hot, "nP": nP, "nH": nH,
                 "kernel_us": round(float(t[:, 1].max()), 1),
                 "pairwise_end_us": {"p50": pct(p[:, 1], 50), "p90": pct(p[:, 1], 90), "max": pct(p[:, 1], 100)},
+                "pairwise_rows_phase_us": {"p50": pct(rows_us, 50), "max": pct(rows_us, 100)},
+                "pairwise_pvalue_phase_us": {"p50": pct(pval_us, 50), "max": pct(pval_us, 100)},
+                "pairwise_pvalue_start_us": {"p50": pct(p[:, 2], 50), "max": pct(p[:, 2], 100)},
                 "history_start_us": {"p50": pct(hh[:, 0], 50), "p90": pct(hh[:, 0], 90), "max": pct(hh[:, 0], 100)},
                 "history_end_us": {"p10": pct(hh[:, 1], 10), "p50": pct(hh[:, 1], 50), "max": pct(hh[:, 1], 100)},
             }), flush=True)
