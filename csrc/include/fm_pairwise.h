@@ -181,8 +181,19 @@ __device__ __forceinline__ void pw_load(const float* __restrict__ c, const float
   }
 }
 
-template <int K, bool SPLIT = false>
-__device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o) {
+// Hook of pw_compute for a caller with work of its own to place inside the
+// row (tick_front.hip requests its next row index): loaded() runs once every
+// loaded sample has been consumed into registers (no load outstanding, the
+// sorts still ahead), done() after the last reduction, before the row's
+// stores.  The default does nothing.
+struct PwNoHook {
+  __device__ __forceinline__ void loaded() const {}
+  __device__ __forceinline__ void done() const {}
+};
+
+template <int K, bool SPLIT = false, class Hook = PwNoHook>
+__device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o,
+                                           Hook hook = Hook()) {
   // Everything exact is carried in integers (counts, doubled rank sums, tie
   // terms, the KS numerator); only the Welch moments are floating point.
   // Counts come from ballots (scalar popcounts), the integer sums are reduced
@@ -241,6 +252,7 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
     nzero += __popcll(__ballot(ok && !nz));
   }
 
+  hook.loaded();
   bitonic_sort<K, SPLIT>(v, tag);
   int rk2[K];
   bool en[K];
@@ -310,6 +322,7 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
     if constexpr (!packB) rps = wave_sum_uniform(rplus2);
   }
 
+  hook.done();
   // Per-row sufficient statistics; p-values are evaluated one row per THREAD
   // by pvalue_kernel (the double-precision special functions would otherwise
   // run on lane 0 with 63 lanes idle).

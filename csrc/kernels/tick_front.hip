@@ -1,7 +1,11 @@
-// fm-hipcc-flags: -mllvm -pragma-unroll-threshold=1000000
+// fm-hipcc-flags: -mllvm -pragma-unroll-threshold=1000000 -mllvm -amdgpu-atomic-optimizer-strategy=None
 // (the 1024-sample pairwise sort, K = 16: past LLVM's default pragma-unroll
 // size limit the stage loops stayed rolled -- runtime register indexing
-// through scratch (132 B/lane) and s_set_gpr_idx; fully unrolled: 0 scratch)
+// through scratch (132 B/lane) and s_set_gpr_idx; fully unrolled: 0 scratch.
+// Atomic optimizer off: every fetch-add here is already issued by one lane,
+// and the pass's wave aggregation reads the result back -- a vmcnt(0) --
+// right behind the instruction, which is what the pairwise row queue places
+// its request inside the row to avoid.)
 #include "fm_pairwise.h"
 #include "fm_row_stats.h"
 
@@ -19,7 +23,9 @@
 // graph starts ~11-13 us late, and whether the branches land on different
 // hardware queues varied run to run: profiles/tick_timeline_*.txt).  The
 // pairwise workgroups have the lowest ids, so the dispatcher places them
-// first and the history workgroups fill the remaining slots.
+// first and the history workgroups fill the remaining slots.  (A steady
+// launch with the pairwise row queue, fm_tick_front_dyn, turns the order
+// round: see tick_front_body.)
 // ---------------------------------------------------------------------------
 // Out-of-line p-value evaluation for the fused kernel: inlined into the
 // role-split kernel the special functions pushed it to 256 VGPRs (one wave
@@ -33,14 +39,18 @@ __device__ __attribute__((noinline)) void eval_test_call(int t, const double* __
 // front kernel records its start / end on the 100 MHz real-time counter, so
 // the critical role (pairwise or history) of a shape can be read off; a
 // pairwise workgroup also records the barrier between its rank-test rows and
-// its p-values (mark 2; a history workgroup leaves that slot alone).
+// its p-values (mark 2; a history workgroup leaves that slot alone) and the
+// number of rows it ranked (mark 3, a count, not a time).
 #ifdef FM_FRONT_TIMING
-constexpr int kFtMarks = 3;
+constexpr int kFtMarks = 4;
 __device__ unsigned long long g_front_t[kFtMarks * 8192];
 #define FM_FT_MARK(k) \
   do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_front_t[kFtMarks * blockIdx.x + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#define FM_FT_ROWS(n) \
+  do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_front_t[kFtMarks * blockIdx.x + 3] = (unsigned long long)(n); } while (0)
 #else
 #define FM_FT_MARK(k) do {} while (0)
+#define FM_FT_ROWS(n) do {} while (0)
 #endif
 
 #define FM_FRONT_PARAMS                                                                                        \
@@ -122,12 +132,186 @@ __device__ __attribute__((noinline)) void xcd_rebalance(unsigned* ctl, int xcd, 
   __hip_atomic_store(ctl + kCtlR, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int NV, int K>
-__device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
+// ---------------------------------------------------------------------------
+// Dynamic row queue of the pairwise role (fm_tick_front_dyn).  Equal static
+// shares of rows do not end together: the five pairwise waves of a SIMD are
+// all VALU-issue-bound and the issue arbiter favours the oldest, so the
+// workgroups dispatched last rank their rows slowest (docs/PERF.md, "Dynamic
+// pairwise rows").  A wave therefore takes only `s` rows by the static formula
+// (no atomics) and then grabs rows one at a time from the pool [pool0, R),
+// which is cut into `q` contiguous ranges with one counter each (one 128-B
+// line per counter: pq[x * 32], the word after it counts the workgroups done).
+// Pairwise workgroup pb uses range (pb + pb / q) % q, so a range is shared by
+// workgroups of every dispatch age and of every XCD (ids are dealt round-robin
+// over the XCDs), and a counter sees a few hundred fetch-adds per tick
+// (cross-XCD atomics on one address serialise at ~28 ns).
+// No wave or workgroup ever waits on another: the only cross-workgroup
+// operations are relaxed fetch-adds, there are no flags, spins or fences, and
+// a workgroup evaluates the p-values of exactly the rows its own waves
+// ranked (their list is kept in LDS), so no `suff` row crosses workgroups
+// inside the launch.  The last workgroup of a range to finish zeroes its two
+// words for the next launch (every other workgroup of the range has made its
+// last grab by then).
+// ---------------------------------------------------------------------------
+constexpr int kRowCap = 64;   // rows one wave may rank (its LDS list); front_plan keeps 4 nP kRowCap >= R
+constexpr int kDynShare = 85; // percent of a wave's even share of the rows it takes statically
+struct FrontDyn {
+  unsigned* pq;   // q x 32 words, zero between launches
+  int q;          // ranges (1 <= q <= nP)
+  int s;          // static rows per wave
+  int pool0;      // first dynamic row (= 4 nP s)
+};
+
+// A wave's request for its next queue index, placed inside the row it is
+// ranking (the hook of pw_compute): lane 0's fetch-add is issued once the
+// row's loads have been consumed, so no later wait for a load also waits for
+// it, and it returns under the row's sorts; the index is read back (wave-
+// uniform) after the last reduction, ahead of the row's stores.  The empty asm
+// pins that read: without it the compiler hoists the readfirstlane, and with it
+// a vmcnt(0), to right behind the fetch-add.
+struct PwGrab {
+  unsigned* ctr;
+  bool want;        // wave-uniform
+  unsigned& next;   // out (wave-uniform), when want
+  unsigned idx = 0;
+  __device__ __forceinline__ void loaded() {
+    if (want && lane_id() == 0) idx = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __device__ __forceinline__ void done() {
+    if (want) {
+      asm volatile("" : "+v"(idx));
+      next = (unsigned)__builtin_amdgcn_readfirstlane((int)idx);
+    }
+  }
+};
+
+// pw_row with the request for the wave's next row inside it.
+template <int K>
+__device__ __forceinline__ void pw_row_grab(const float* __restrict__ c, const float* __restrict__ b, int n_cur,
+                                            int n_base, double* __restrict__ o, bool want, unsigned* ctr,
+                                            unsigned& next) {
+  PwIn<K> in;
+  if constexpr (K == 2) {
+    if (n_cur <= 64 && n_base <= 64) {
+      pw_load<K, true>(c, b, n_cur, n_base, in);
+      pw_compute<K, true>(in, n_cur, n_base, o, PwGrab{ctr, want, next});
+      return;
+    }
+  }
+  pw_load<K>(c, b, n_cur, n_base, in);
+  pw_compute<K, false>(in, n_cur, n_base, o, PwGrab{ctr, want, next});
+}
+
+// The pairwise role of workgroup pb (0 <= pb < nP) with dynamic rows.
+template <int K>
+__device__ __forceinline__ void front_pairwise_dyn(FM_FRONT_PARAMS, const FrontDyn dq, const int pb) {
+  __shared__ int s_rows[4][kRowCap];
+  __shared__ int s_cnt[4];
+  const int w = wave_id(), lane = lane_id();
+  const int W = nP * 4, Q = dq.q;
+  const int x = (pb + pb / Q) % Q;
+  const int64_t pool = R - dq.pool0;
+  const int lo = dq.pool0 + (int)(pool * x / Q), hi = dq.pool0 + (int)(pool * (x + 1) / Q);
+  const unsigned nx = (unsigned)(hi - lo);       // rows of this range (0: nobody touches its counter)
+  unsigned* ctr = dq.pq + x * 32;
+  unsigned next = 0;                             // the index drawn last (wave-uniform)
+  bool pending = false;                          // an index was drawn and its row is not yet taken
+  if (dq.s == 0 && nx != 0u) {                   // no static row to draw it under
+    unsigned idx = 0;
+    if (lane == 0) idx = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    next = (unsigned)__builtin_amdgcn_readfirstlane((int)idx);
+    pending = true;
+  }
+  const int cls = pb / (nP >= 5 ? nP / 5 : 1);   // dispatch age class: the pairwise ids in fifths
+  int i = 0;                                     // rows ranked by this wave
+  for (;;) {
+    int row;
+    if (i < dq.s) {
+      row = pb * 4 + w + i * W;                  // (< pool0 <= R)
+    } else {
+      if (!pending) break;                       // list full (or an empty range)
+      if (next >= nx) break;                     // range drained
+      row = lo + (int)next;
+    }
+    // rotating wave priority: VALU issue goes by priority, then age, so left
+    // alone the oldest of a SIMD's pairwise waves runs nearly unimpeded and
+    // the youngest gets the leftover slots (the static tick's five end times,
+    // 52 .. 114 us by dispatch age class).  With (age class + rows done) & 3
+    // every wave is the arbitration winner for an equal share of its rows.
+    switch ((cls + i) & 3) {
+      case 0: __builtin_amdgcn_s_setprio(0); break;
+      case 1: __builtin_amdgcn_s_setprio(1); break;
+      case 2: __builtin_amdgcn_s_setprio(2); break;
+      default: __builtin_amdgcn_s_setprio(3); break;
+    }
+    // the next index is requested only when the list will have room for its
+    // row: every index drawn below nx is ranked by the wave that drew it
+    const bool want = nx != 0u && i + 1 >= dq.s && i + 1 < kRowCap;
+    pw_row_grab<K>(cur + (int64_t)row * ld_c, base + (int64_t)row * ld_b, n_cur, n_base, suff + (int64_t)row * kSuff,
+                   want, ctr, next);
+    pending = want;
+    if (lane == 0) s_rows[w][i] = row;
+    ++i;
+  }
+  __builtin_amdgcn_s_setprio(0);
+  if (lane == 0) s_cnt[w] = i;
+  __syncthreads();   // this workgroup's suff rows and row lists are visible to all its waves
+  FM_FT_MARK(2);
+  // the p-value phase of the static role over the concatenated lists
+  const int c0 = s_cnt[0], c1 = c0 + s_cnt[1], c2 = c1 + s_cnt[2], nr = c2 + s_cnt[3];
+  FM_FT_ROWS(nr);
+  constexpr unsigned kByCost = 0x512034u;
+  const int cpt = (nr + 63) >> 6;
+  const int slot = (w + pb) & 3;
+  for (int u = 0;; ++u) {
+    const int ci = (u >> 1) * 8 + ((u & 1) ? 7 - slot : slot);
+    if (ci >= N_TESTS * cpt) break;
+    const int tp = ci / cpt;
+    const int t = __builtin_amdgcn_readfirstlane((int)((kByCost >> (4 * tp)) & 7u));
+    const int j = (ci - tp * cpt) * 64 + lane;
+    if (j < nr) {
+      const int ww = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
+      const int j0 = ww == 0 ? 0 : (ww == 1 ? c0 : (ww == 2 ? c1 : c2));
+      const int64_t row = s_rows[ww][j - j0];
+      double pv, sv;
+      eval_test_call(t, suff + row * kSuff, min_mw, min_wil, min_kru, pv, sv);
+      pvals[row * N_TESTS + t] = (float)pv;
+      pstats[row * N_TESTS + t] = (float)sv;
+    }
+  }
+  // every wave of this workgroup made its last grab before the barrier above
+  if (nx != 0u && threadIdx.x == 0) {
+    const int full = nP / Q, rem = nP - full * Q;
+    const int xr = x - full % Q;                 // range x is range (x - full) mod Q of the partial round
+    const unsigned nwg = (unsigned)(full + ((xr < 0 ? xr + Q : xr) < rem ? 1 : 0));
+    const unsigned d = __hip_atomic_fetch_add(ctr + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (d == nwg - 1u) {
+      __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  FM_FT_MARK(1);
+}
+
+// DYN: the pairwise role takes its rows from the queue above, and in the scan
+// shape the (short) history role has the lowest block ids: its workgroups are
+// placed first and are gone after a few microseconds, and the pairwise
+// workgroups that inherit their slots start late and simply grab fewer rows.
+// The streaming shape keeps the pairwise workgroups first (see the top).
+template <int NV, int K, bool DYN>
+__device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS, const FrontDyn dq) {
   __shared__ double red[4];
   __shared__ int redi[4];
   FM_FT_MARK(0);
-  if ((int)blockIdx.x < nP) {
+  const int nHg = (int)gridDim.x - nP;
+  const bool hfirst = DYN && scan != 0;
+  const int pb = hfirst ? (int)blockIdx.x - nHg : (int)blockIdx.x;     // pairwise workgroup index
+  const int64_t hb = hfirst ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - nP;   // history workgroup index
+  if (pb >= 0 && pb < nP) {
+    if constexpr (DYN) {
+      front_pairwise_dyn<K>(FM_FRONT_ARGS, dq, pb);
+      return;
+    }
     const int64_t first = (int64_t)blockIdx.x * 4, stride = (int64_t)nP * 4;
     for (int64_t row = first + wave_id(); row < R; row += stride) {
       pw_row<K>(cur + row * ld_c, base + row * ld_b, n_cur, n_base, suff + row * kSuff);
@@ -137,6 +321,13 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
     // local row j -> global row first + (j & 3) + (j >> 2) * stride
     const int64_t span = R > first ? R - first : 0;
     const int nr = (int)(((span + stride - 1) / stride) * 4);
+#ifdef FM_FRONT_TIMING
+    {
+      int64_t took = 0;
+      for (int w = 0; w < 4; ++w) took += span > w ? (span - w + stride - 1) / stride : 0;
+      FM_FT_ROWS(took);
+    }
+#endif
     // wave-sized chunks of (test, 64 rows); the test is wave-uniform so the
     // special-function switch stays a scalar branch (a per-lane test index
     // made the compiler keep every path live: 256 VGPRs).  Chunks are listed
@@ -169,7 +360,7 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
     FM_FT_MARK(1);
     return;
   }
-  const int nH = (int)gridDim.x - nP;
+  const int nH = nHg;
   // Row-statistics cache (fm_row_stats.h).  scan: the host expects (nearly)
   // every row to hit -- the history workgroups test their rows one per
   // thread, copy the hits and reduce only the misses.  Otherwise (first tick,
@@ -180,13 +371,13 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
   if (scan) {
     __shared__ int s_list[256];
     __shared__ int s_cnt;
-    hist_scan_cached<NV>(hist, ld_h, T, R, hs, rowmap, cache, valid, (int64_t)blockIdx.x - nP, nH, red, redi, s_list,
+    hist_scan_cached<NV>(hist, ld_h, T, R, hs, rowmap, cache, valid, hb, nH, red, redi, s_list,
                          &s_cnt);
     FM_FT_MARK(1);
     return;
   }
   if (queue == nullptr) {
-    for (int64_t row = (int64_t)blockIdx.x - nP; row < R; row += nH) {
+    for (int64_t row = hb; row < R; row += nH) {
       float mf, sd;
       int n;
       const int64_t p = hist_row(rowmap, row);
@@ -214,8 +405,7 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
   // tail waits on at most one row instead of two (0.0951/0.0919 -> 0.0937/
   // 0.0904 ms per step, interleaved runs); neutral at 10k services.
   __shared__ unsigned s_next;
-  const int hb = (int)blockIdx.x - nP;
-  const int xcd = hb & 7;
+  const int xcd = (int)hb & 7;
   const int nwg = (nH >> 3) + ((nH & 7) > xcd ? 1 : 0);   // workgroups sharing this range
   // XCD-balanced ranges: the XCDs do not stream equally fast (per-XCD end
   // times of the history role, tools/front_timing.py: XCDs 3-5 end 30-40 us
@@ -278,7 +468,67 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS) {
 
 template <int NV, int K>
 __global__ __launch_bounds__(256) void tick_front_kernel(FM_FRONT_PARAMS) {
-  tick_front_body<NV, K>(FM_FRONT_ARGS);
+  tick_front_body<NV, K, false>(FM_FRONT_ARGS, FrontDyn{});
+}
+
+template <int NV, int K>
+__global__ __launch_bounds__(256) void tick_front_dyn_kernel(FM_FRONT_PARAMS, const FrontDyn dq) {
+  tick_front_body<NV, K, true>(FM_FRONT_ARGS, dq);
+}
+
+// The host's plan of the pairwise role for R rows, nP requested workgroups
+// (<= 0: one per 4 rows) and q_ranges requested ranges.  q == 0: static rows
+// (today's kernel).  Otherwise wave w of workgroup pb ranks the s rows
+// 4 pb + w + i 4 nP (i < s; together exactly [0, pool0)) and the pool
+// [pool0, R) is cut into q ranges, range x = [pool0 + pool x / q,
+// pool0 + pool (x + 1) / q).  s is kDynShare percent (FM_FRONT_DYN_SHARE=<percent>
+// overrides, read once) of the rows a wave would get statically, rounded down
+// (sweep at 80k rows, docs/PERF.md: 66 / 75 / 85 / 95 / 100 % -> 0.1318 /
+// 0.1315 / 0.1306 / 0.1336 / 0.1352 ms per step).
+// A wave ranks at most kRowCap rows, so the plan keeps 4 nP kRowCap >= R and,
+// range by range, the rows of a range within what the lists of its workgroups
+// still hold after the static share: no row can be left over; where the
+// requested nP is too small for that, nP grows.
+// Only the scan shape gets the queue.  A streaming launch keeps static rows
+// and its grid: its pairwise workgroups (one per CU) end long before the
+// history stream does, and with the queue the tick that recomputes every row
+// of the 1,250-service shard measured 0.096-0.097 ms against 0.077-0.078.
+struct FrontPlan {
+  int nP, s, q;
+  int64_t pool0;
+};
+static FrontPlan front_plan(int64_t R, int nP, int q_ranges, bool scan) {
+  static const int share = [] {
+    const char* e = getenv("FM_FRONT_DYN_SHARE");
+    const int v = e != nullptr ? atoi(e) : -1;
+    return v < 0 || v > 100 ? -1 : v;
+  }();
+  const int64_t pmax = (R + 3) / 4;
+  if (nP <= 0 || nP > pmax) nP = (int)pmax;
+  const int64_t per0 = R > 0 ? (R + 4 * (int64_t)nP - 1) / (4 * (int64_t)nP) : 0;
+  const FrontPlan fixed{nP, (int)(per0 < 0x7fffffff ? per0 : 0x7fffffff), 0, R};
+  if (!scan || q_ranges <= 0 || R <= 0 || R > 0x7fffffff) return fixed;
+  if ((int64_t)nP * 4 * kRowCap < R) nP = (int)((R + 4 * kRowCap - 1) / (4 * kRowCap));
+  for (;;) {
+    const int64_t W = 4 * (int64_t)nP, per = R / W;
+    const int s = (int)(per * (share >= 0 ? share : kDynShare) / 100);
+    const int q = q_ranges < nP ? q_ranges : nP;
+    const int64_t pool = R - W * s;
+    // the longest range against the fewest workgroups a range can have
+    if (s < kRowCap && (pool + q - 1) / q <= (int64_t)(nP / q) * 4 * (kRowCap - s)) return FrontPlan{nP, s, q, W * s};
+    if (nP >= pmax) return fixed;   // (not reached: at nP = pmax s <= 1 and pool <= 4 nP, which always fits)
+    const int64_t up = (int64_t)nP + nP / 2 + 1;
+    nP = (int)(up < pmax ? up : pmax);
+  }
+}
+
+// out[4]: static rows per wave, first row of the pool, ranges (0 = static
+// rows only: the pool is empty), effective nP.  Host only: no device call.
+FM_API int fm_front_plan(int64_t R, int nP, int q_ranges, int scan, int64_t* out) {
+  if (out == nullptr) return (int)hipErrorInvalidValue;
+  const FrontPlan p = front_plan(R, nP, q_ranges, scan != 0);
+  out[0] = p.s, out[1] = p.pool0, out[2] = p.q, out[3] = p.nP;
+  return 0;
 }
 
 // FM_FRONT_LDS=<bytes> (environment, read once): dynamic LDS requested per
@@ -308,11 +558,18 @@ static unsigned front_lds() {
 // (computing whatever does miss), nP / nH are taken as given for that shape
 // (nH 0 = one workgroup per 256 rows) and no dynamic LDS caps the pairwise
 // workgroups per CU.  A wrong expectation costs time, never correctness.
-FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
-                                int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff,
-                                int nP, int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
-                                unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
-                                hipStream_t stream) {
+//
+// pqueue / q_ranges (fm_tick_front_dyn; nullptr / 0: static pairwise rows):
+// the pairwise role's dynamic row queue, q_ranges x 32 zero-initialised
+// uint32 kept zero between launches by the kernel itself (front_plan above;
+// one launch at a time per pqueue).  The scan shape uses it: the history
+// workgroups then have the lowest block ids, and nP is raised where the wave
+// lists would not hold R rows.  A streaming launch keeps static rows.
+static int front_launch(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
+                        int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
+                        int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
+                        const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
+                        int q_ranges, hipStream_t stream) {
   if (R <= 0) return 0;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
   const int n = n_cur + n_base;
@@ -321,6 +578,8 @@ FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t 
   const int scan = cache != nullptr && expect_miss == 0 ? 1 : 0;
   const int64_t pmax = (R + 3) / 4;
   if (nP <= 0 || nP > pmax) nP = (int)pmax;
+  const FrontPlan plan = front_plan(R, nP, pqueue != nullptr ? q_ranges : 0, scan != 0);
+  nP = plan.nP;
   if (scan && nH <= 0) nH = (int)((R + 255) / 256);
   if (nH <= 0 || nH > R) nH = (int)R;
   // queue: 8 x 32 + 64 zero-initialised uints (the counters are kept zero
@@ -330,7 +589,14 @@ FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t 
   const int nq = (T + 3) / 4;
   const dim3 grid((unsigned)(nP + nH)), block(256);
   const unsigned lds = scan ? 0u : front_lds();
-#define FM_TF(KK) hipLaunchKernelGGL((tick_front_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS)
+  const FrontDyn dq{pqueue, plan.q, plan.s, (int)plan.pool0};
+#define FM_TF(KK)                                                                                            \
+  do {                                                                                                       \
+    if (plan.q > 0)                                                                                          \
+      hipLaunchKernelGGL((tick_front_dyn_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS, dq);      \
+    else                                                                                                     \
+      hipLaunchKernelGGL((tick_front_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS);              \
+  } while (0)
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
     constexpr int NV = decltype(nv)::value;
     if (n <= 64) FM_TF(1);
@@ -341,6 +607,25 @@ FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t 
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
   return 0;
+}
+
+FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
+                                int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff,
+                                int nP, int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
+                                unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
+                                hipStream_t stream) {
+  return front_launch(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
+                      min_kru, pvals, pstats, queue, rowmap, cache, valid, expect_miss, nullptr, 0, stream);
+}
+
+// fm_tick_front_cached with the pairwise role's dynamic row queue.
+FM_API int fm_tick_front_dyn(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
+                             int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
+                             int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
+                             unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
+                             unsigned* pqueue, int q_ranges, hipStream_t stream) {
+  return front_launch(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
+                      min_kru, pvals, pstats, queue, rowmap, cache, valid, expect_miss, pqueue, q_ranges, stream);
 }
 
 FM_API int fm_tick_front_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,

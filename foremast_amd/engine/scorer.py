@@ -144,8 +144,15 @@ class CanaryScorer:
         # are all expected in the row-statistics cache has no history stream
         # to make room for: front_hot_wgs, workgroups per CU again)
         self.front_wgs = front_wgs or (1.0, 4.0)
+        # dynamic row queue of the pairwise role (tick_front.hip, fm_tick_front_dyn;
+        # FM_FRONT_DYN_Q=0 keeps static rows, fm_tick_front_cached): ranges
+        self._q_ranges = int(os.environ.get("FM_FRONT_DYN_Q", "64")) if self.device.type == "cuda" else 0
         if front_hot_wgs is None:
-            front_hot_wgs = tuple(float(x) for x in os.environ.get("FM_FRONT_HOT_WGS", "5:0.25").split(":"))
+            # with the queue (and its rotating wave priority) four pairwise
+            # workgroups per CU measure faster than five (docs/PERF.md,
+            # "Dynamic pairwise rows"); static rows keep five
+            front_hot_wgs = tuple(float(x) for x in os.environ.get(
+                "FM_FRONT_HOT_WGS", "4:0.25" if self._q_ranges > 0 else "5:0.25").split(":"))
         self.front_hot_wgs = front_hot_wgs
         self.hist_cache = hist_cache and os.environ.get("FM_HIST_CACHE", "1") != "0"
         self._bound: dict[int, _BoundHist] = {}            # id(history tensor) -> its cache
@@ -160,6 +167,10 @@ class CanaryScorer:
             xcd_balance = os.environ.get("FM_XCD_BALANCE", "1") != "0"
         if self._queue is not None and xcd_balance:
             self._queue[8 * 32 + 31] = 1      # control block: XCD-balanced history ranges (tick_front.hip kXcdCtl)
+        # the pairwise row queue: one counter line per range, kept zero between
+        # launches by the kernel itself
+        self._pqueue = (torch.zeros(self._q_ranges * 32, dtype=torch.int32, device=self.device)
+                        if self._q_ranges > 0 else None)
         self._cus = (torch.cuda.get_device_properties(self.device).multi_processor_count
                      if self.device.type == "cuda" else 0)
         rules = [self.cfg.rule_for(a) for a in aliases]
@@ -290,10 +301,10 @@ class CanaryScorer:
         c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
         if has_base and n <= 256:
             n_p, n_h = self._front_grid(miss)
-            LIB.call("fm_tick_front_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), ptr(cur),
+            LIB.call(self._front_cached_fn, ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), ptr(cur),
                      cur.stride(0), cur.shape[1], ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h,
                      self.pcfg.min_mann_white, self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals),
-                     ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid, int(miss), st)
+                     ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid, int(miss), *self._dyn_args(), st)
         else:
             LIB.call("fm_hist_stats_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), 0, ptr(rowmap),
                      c_stats, c_valid, int(miss), st)
@@ -411,6 +422,17 @@ class CanaryScorer:
         n_h = int(fh * self._cus) if fh > 0 else 0
         return n_p, (n_h if miss or fh <= 0 else max(1, n_h))
 
+    @property
+    def _front_cached_fn(self) -> str:
+        """The cached front launch: with the pairwise role's dynamic row queue
+        unless it is switched off."""
+        return "fm_tick_front_dyn" if self._pqueue is not None else "fm_tick_front_cached"
+
+    def _dyn_args(self) -> tuple:
+        """The arguments fm_tick_front_dyn takes after fm_tick_front_cached's."""
+        from ..ops._lib import ptr
+        return (ptr(self._pqueue), self._q_ranges) if self._pqueue is not None else ()
+
     def _bind(self, hist: torch.Tensor) -> _BoundHist | None:
         """The row-statistics cache of a history tensor bound to a launcher
         (one per tensor, shared by the launchers of every slot)."""
@@ -493,7 +515,7 @@ class CanaryScorer:
             return capture(lambda: self.front_only(hist, base, cur, n_hist, packed_out, slot)).replay, o
         from ..ops._lib import LIB, stream_of
         graphs = {miss: capture(lambda miss=miss: LIB.call(
-            "fm_tick_front_cached", *self._front_cached_args(bh, base, cur, T, o, miss), stream_of(cur)))
+            self._front_cached_fn, *self._front_cached_args(bh, base, cur, T, o, miss), stream_of(cur)))
             for miss in (True, False)}
 
         def replay() -> None:
@@ -536,15 +558,16 @@ class CanaryScorer:
                 self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue))
 
     def _front_cached_args(self, bh: _BoundHist, base, cur, T: int, o: CanaryOutputs, miss: bool) -> tuple:
-        """Arguments of fm_tick_front_cached (all but the stream) over a bound
-        history tensor, for a tick expected to miss / to hit."""
+        """Arguments of fm_tick_front_cached / fm_tick_front_dyn (``_front_cached_fn``;
+        all but the stream) over a bound history tensor, for a tick expected
+        to miss / to hit."""
         from ..ops._lib import ptr
         hist = bh.hist
         n_p, n_h = self._front_grid(miss)
         return (ptr(hist), hist.stride(0), T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1],
                 ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white,
                 self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue), None,
-                ptr(bh.cache.stats), ptr(bh.cache.valid), int(miss))
+                ptr(bh.cache.stats), ptr(bh.cache.valid), int(miss), *self._dyn_args())
 
     def split_launchers(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0,
                         front_stream=None, decide_stream=None):
@@ -581,14 +604,14 @@ class CanaryScorer:
 
         bh = self._bind(hist)
         if bh is not None:
-            c_fn, R = lib.fm_tick_front_cached, cur.shape[0]
+            c_fn, R = getattr(lib, self._front_cached_fn), cur.shape[0]
             c_args = {miss: self._front_cached_args(bh, base, cur, T, o, miss) + (fs,) for miss in (True, False)}
             expect, ticked = bh.expect_miss, bh.cache.ticked
 
             def front() -> None:   # noqa: F811 - the cached form replaces the plain one
                 rc = c_fn(*c_args[expect(T, R, fs)])
                 if rc:
-                    raise RuntimeError(f"fm_tick_front_cached failed with hipError {rc}")
+                    raise RuntimeError(f"{self._front_cached_fn} failed with hipError {rc}")
                 ticked(T)
 
         def decide() -> None:

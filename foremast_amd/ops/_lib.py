@@ -136,6 +136,12 @@ _SIGS: dict[str, list] = {
     "fm_tick_front_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
                              c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_int, c_void_p],
+    # fm_tick_front_cached + pqueue q_ranges (before the stream)
+    "fm_tick_front_dyn": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
+                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    # R nP q_ranges scan out[4] (int64: static rows per wave, pool start, ranges, effective nP); host only
+    "fm_front_plan": [c_i64, c_int, c_int, c_int, c_void_p],
     "fm_hist_stats_rm": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p],
     "fm_hist_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p],
