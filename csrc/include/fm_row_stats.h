@@ -103,9 +103,14 @@ __device__ __forceinline__ void block_row_stats(const float* __restrict__ hrow, 
 
 // History row of logical row `row`: identity, or a slot of the brain's
 // device-resident history store (engine/resident.py) when a row map is given.
-// The row index is wave-uniform, so the map read is one scalar load.
+// The row index is wave-uniform, so the map read is one scalar load: it goes
+// through the constant address space (no launch that reads a map writes it),
+// which a kernel whose pointers arrive in a struct (tick_front.hip) cannot
+// say with a `const __restrict__` parameter -- there the read was a vector
+// load and a readfirstlane per row.
 __device__ __forceinline__ int64_t hist_row(const int* __restrict__ rowmap, int64_t row) {
-  return rowmap != nullptr ? (int64_t)rowmap[row] : row;
+  typedef const __attribute__((address_space(4))) int* const_map;
+  return rowmap != nullptr ? (int64_t)((const_map)rowmap)[row] : row;
 }
 
 // ---------------------------------------------------------------------------
@@ -142,6 +147,26 @@ __device__ __forceinline__ void row_cache_put(float* __restrict__ cache, unsigne
   else valid[p] = tag;
 }
 
+// One history row by a 256-thread workgroup: reduce the physical row of
+// logical row `row`, write hs[row * 3 ..] and, when a cache is given, record
+// the three floats in it (publish: row_cache_put's two forms above).
+template <int NV, bool publish>
+__device__ __forceinline__ void hist_row_emit(const float* __restrict__ hist, int64_t ld_h, int T,
+                                              float* __restrict__ hs, const int* __restrict__ rowmap,
+                                              float* __restrict__ cache, unsigned* __restrict__ valid, int64_t row,
+                                              double* red, int* redi) {
+  float mf, sd;
+  int n;
+  const int64_t p = hist_row(rowmap, row);
+  block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
+  if (threadIdx.x == 0) {
+    hs[row * 3 + 0] = mf;
+    hs[row * 3 + 1] = sd;
+    hs[row * 3 + 2] = (float)n;
+    if (cache != nullptr) row_cache_put<publish>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
+  }
+}
+
 // Hit scan of the history rows {wg, wg + nwg, wg + 2 nwg, ..} by one
 // 256-thread workgroup: one row per thread, hits are copied (12 bytes) and the
 // misses of each 256-row pass are compacted into an LDS list, over which the
@@ -174,16 +199,7 @@ __device__ __forceinline__ void hist_scan_cached(const float* __restrict__ hist,
     const int nm = *s_cnt;
     for (int i = 0; i < nm; ++i) {
       const int64_t row = wg + (k0 + __builtin_amdgcn_readfirstlane(s_list[i])) * nwg;
-      const int64_t p = hist_row(rowmap, row);
-      float mf, sd;
-      int n;
-      block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
-      if (tid == 0) {
-        hs[row * 3 + 0] = mf;
-        hs[row * 3 + 1] = sd;
-        hs[row * 3 + 2] = (float)n;
-        if (cache != nullptr) row_cache_put<true>(cache, valid, p, tag, mf, sd, (float)n);
-      }
+      hist_row_emit<NV, true>(hist, ld_h, T, hs, rowmap, cache, valid, row, red, redi);
     }
     __syncthreads();   // the list is rebuilt by the next pass
   }

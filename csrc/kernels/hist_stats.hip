@@ -108,39 +108,9 @@ __global__ __launch_bounds__(256) void hist_stats_kernel(const float* __restrict
                                                          unsigned* __restrict__ valid) {
   __shared__ double red[4];
   __shared__ int redi[4];
-  for (int64_t row = blockIdx.x; row < R; row += gridDim.x) {
-    float mf, sd;
-    int n;
-    const int64_t p = hist_row(rowmap, row);
-    block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
-    if (threadIdx.x == 0) {
-      out[row * 3 + 0] = mf;
-      out[row * 3 + 1] = sd;
-      out[row * 3 + 2] = (float)n;
-      // (row-statistics cache, fm_row_stats.h: this launch tests no word)
-      if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
-    }
-  }
-}
-
-static int hist_stats_launch(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
-                             const int* rowmap, float* cache, unsigned* valid, hipStream_t stream) {
-  if (R <= 0) return 0;
-  if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
-  const int nq = (T + 3) / 4;
-  const dim3 grid((unsigned)(max_blocks > 0 && R > max_blocks ? max_blocks : R)), block(256);
-  const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    hipLaunchKernelGGL(hist_stats_kernel<decltype(nv)::value>, grid, block, 0, stream, hist, ld_h, T, R, out, rowmap,
-                       cache, valid);
-  });
-  if (rc != 0) return rc;
-  FM_LAUNCH_CHECK();
-  return 0;
-}
-
-FM_API int fm_hist_stats_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
-                            const int* rowmap, hipStream_t stream) {
-  return hist_stats_launch(hist, ld_h, T, R, out, max_blocks, rowmap, nullptr, nullptr, stream);
+  // (row-statistics cache, fm_row_stats.h: this launch tests no word)
+  for (int64_t row = blockIdx.x; row < R; row += gridDim.x)
+    hist_row_emit<NV, false>(hist, ld_h, T, out, rowmap, cache, valid, row, red, redi);
 }
 
 // The same with the row-statistics cache of the history tensor
@@ -159,23 +129,24 @@ __global__ __launch_bounds__(256) void hist_stats_cached_kernel(const float* __r
   hist_scan_cached<NV>(hist, ld_h, T, R, out, rowmap, cache, valid, blockIdx.x, gridDim.x, red, redi, s_list, &s_cnt);
 }
 
-// expect_miss 1: every row is reduced and recorded without a look at its
-// word, one workgroup per row (capped by max_blocks) as fm_hist_stats_rm;
-// 0: one workgroup per 256 rows, a row per thread, which reduces what does
-// miss.  Null cache pointers: fm_hist_stats_rm.
+// expect_miss 1 (or null cache pointers, which record nothing): every row is
+// reduced and recorded without a look at its word, one workgroup per row
+// (capped by max_blocks); 0: one workgroup per 256 rows, a row per thread,
+// which reduces what does miss.
 FM_API int fm_hist_stats_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
                                 const int* rowmap, float* cache, unsigned* valid, int expect_miss,
                                 hipStream_t stream) {
-  if (cache == nullptr || valid == nullptr || T <= 0) cache = nullptr, valid = nullptr;   // (tag 0 means invalid)
-  if (cache == nullptr || expect_miss != 0)
-    return hist_stats_launch(hist, ld_h, T, R, out, max_blocks, rowmap, cache, valid, stream);
   if (R <= 0) return 0;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
+  if (cache == nullptr || valid == nullptr || T <= 0) cache = nullptr, valid = nullptr;   // (tag 0 means invalid)
+  const bool scan = cache != nullptr && expect_miss == 0;
   const int nq = (T + 3) / 4;
-  const dim3 grid((unsigned)((R + 255) / 256)), block(256);
+  const dim3 grid((unsigned)(scan ? (R + 255) / 256 : (max_blocks > 0 && R > max_blocks ? max_blocks : R))), block(256);
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    hipLaunchKernelGGL(hist_stats_cached_kernel<decltype(nv)::value>, grid, block, 0, stream, hist, ld_h, T, R, out,
-                       rowmap, cache, valid);
+    constexpr int NV = decltype(nv)::value;
+    if (scan) hipLaunchKernelGGL(hist_stats_cached_kernel<NV>, grid, block, 0, stream, hist, ld_h, T, R, out, rowmap,
+                                 cache, valid);
+    else hipLaunchKernelGGL(hist_stats_kernel<NV>, grid, block, 0, stream, hist, ld_h, T, R, out, rowmap, cache, valid);
   });
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
@@ -190,9 +161,9 @@ FM_API int fm_hist_cache_invalidate(unsigned* valid, int64_t n, hipStream_t stre
 
 FM_API int fm_hist_stats_capped(const float* hist, int64_t ld_h, int T, int64_t R, float* out, int max_blocks,
                                 hipStream_t stream) {
-  return fm_hist_stats_rm(hist, ld_h, T, R, out, max_blocks, nullptr, stream);
+  return fm_hist_stats_cached(hist, ld_h, T, R, out, max_blocks, nullptr, nullptr, nullptr, 1, stream);
 }
 
 FM_API int fm_hist_stats(const float* hist, int64_t ld_h, int T, int64_t R, float* out, hipStream_t stream) {
-  return fm_hist_stats_rm(hist, ld_h, T, R, out, 0, nullptr, stream);
+  return fm_hist_stats_cached(hist, ld_h, T, R, out, 0, nullptr, nullptr, nullptr, 1, stream);
 }

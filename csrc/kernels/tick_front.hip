@@ -24,7 +24,7 @@
 // hardware queues varied run to run: profiles/tick_timeline_*.txt).  The
 // pairwise workgroups have the lowest ids, so the dispatcher places them
 // first and the history workgroups fill the remaining slots.  (A steady
-// launch with the pairwise row queue, fm_tick_front_dyn, turns the order
+// launch with the pairwise row queue, tick_front_dyn_kernel, turns the order
 // round: see tick_front_body.)
 // ---------------------------------------------------------------------------
 // Out-of-line p-value evaluation for the fused kernel: inlined into the
@@ -53,14 +53,37 @@ __device__ unsigned long long g_front_t[kFtMarks * 8192];
 #define FM_FT_ROWS(n) do {} while (0)
 #endif
 
-#define FM_FRONT_PARAMS                                                                                        \
-  const float *__restrict__ hist, int64_t ld_h, int T, int64_t R, float *__restrict__ hs /*[R,3]*/,            \
-      const float *__restrict__ cur, int64_t ld_c, int n_cur, const float *__restrict__ base, int64_t ld_b,    \
-      int n_base, double *__restrict__ suff, int nP, int min_mw, int min_wil, int min_kru,                     \
-      float *__restrict__ pvals, float *__restrict__ pstats, unsigned *__restrict__ queue,                    \
-      const int *__restrict__ rowmap, float *__restrict__ cache, unsigned *__restrict__ valid, int scan
-#define FM_FRONT_ARGS hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, min_mw, min_wil, \
-      min_kru, pvals, pstats, queue, rowmap, cache, valid, scan
+// Everything a front launch reads and writes, the kernel's one argument.
+// rowmap, cache / valid and queue may be null; scan: the history role tests
+// the row-statistics cache (front_hist_scan) instead of streaming every row.
+// The fields are grouped by who reads them, and the order is part of the
+// kernel's register budget: the compiler merges the loads of adjacent fields
+// into one wide scalar load whose registers stay live as long as any of them
+// does.  With R among the history pointers, or the p-value fields ahead of
+// the rank-test fields, the NV >= 10 instantiations spilled SGPRs into 3-8
+// more VGPRs (NV = 12: 91 -> 98, a wave per SIMD less).
+struct FrontArgs {
+  int64_t R;
+  int nP, scan, T;
+  // history roles
+  const float* hist;
+  int64_t ld_h;
+  float* hs;   // [R, 3]
+  const int* rowmap;
+  float* cache;
+  unsigned* valid;
+  unsigned* queue;
+  // pairwise roles: the rank-test rows ...
+  const float* cur;
+  int64_t ld_c;
+  const float* base;
+  int64_t ld_b;
+  double* suff;
+  int n_cur, n_base;
+  // ... and their p-values
+  float *pvals, *pstats;
+  int min_mw, min_wil, min_kru;
+};
 
 // Control block of the front kernel's history queue (uint32 words from
 // queue[kXcdCtl]; the queue is 8 x 32 counters + this block, zeroed by the
@@ -80,7 +103,7 @@ __device__ inline int64_t xcd_bound(int64_t R, unsigned f) { return (R * (int64_
 
 // The last workgroup of XCD range ``xcd``: its end time; the last range of
 // the tick to finish computes the next tick's bounds.
-__device__ __attribute__((noinline)) void xcd_rebalance(unsigned* ctl, int xcd, int64_t R, int64_t lo, int64_t hi) {
+__device__ __attribute__((noinline)) void xcd_rebalance(unsigned* ctl, int xcd, int64_t R) {
   unsigned long long* t0 = reinterpret_cast<unsigned long long*>(ctl + kCtlT0);
   unsigned long long* t1 = reinterpret_cast<unsigned long long*>(ctl + kCtlT1);
   __hip_atomic_store(t1 + xcd, __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -133,7 +156,7 @@ __device__ __attribute__((noinline)) void xcd_rebalance(unsigned* ctl, int xcd, 
 }
 
 // ---------------------------------------------------------------------------
-// Dynamic row queue of the pairwise role (fm_tick_front_dyn).  Equal static
+// Dynamic row queue of the pairwise role (tick_front_dyn_kernel).  Equal static
 // shares of rows do not end together: the five pairwise waves of a SIMD are
 // all VALU-issue-bound and the issue arbiter favours the oldest, so the
 // workgroups dispatched last rank their rows slowest (docs/PERF.md, "Dynamic
@@ -202,15 +225,78 @@ __device__ __forceinline__ void pw_row_grab(const float* __restrict__ c, const f
   pw_compute<K, false>(in, n_cur, n_base, o, PwGrab{ctr, want, next});
 }
 
+// The p-value phase of a pairwise workgroup, after the barrier behind its
+// rank-test rows: the six p-values of its nr local rows, one (test, row) pair
+// per thread.  rowOf(j), j < nr: the global row of local row j, or negative
+// where there is none.
+// Wave-sized chunks of (test, 64 rows); the test is wave-uniform so the
+// special-function switch stays a scalar branch (a per-lane test index
+// made the compiler keep every path live: 256 VGPRs).  Chunks are listed
+// costliest test first (Welch's incomplete beta, then the Kolmogorov
+// series, then the erfc tests) and dealt to the four waves back and forth
+// (0 1 2 3 3 2 1 0 ...), so at one chunk per test the Welch and KS chunks
+// have a wave each and the four cheap tests pair up.  Wave w of every
+// co-resident workgroup sits on the same SIMD and all of them reach this
+// phase together, so the deal is rotated by the workgroup's index (slot =
+// (wave + workgroup) & 3): the Welch chains of neighbouring workgroups land
+// on different SIMDs.
+template <class RowOf>
+__device__ __forceinline__ void front_pvalues(const FrontArgs& a, int nr, int slot, RowOf rowOf) {
+  // T_T, T_KS, T_MW, T_KRU, T_WIL, T_FRI, one per nibble from the low end
+  static_assert(T_T == 4 && T_KS == 3 && T_MW == 0 && T_KRU == 2 && T_WIL == 1 && T_FRI == 5, "kByCost");
+  constexpr unsigned kByCost = 0x512034u;
+  const int cpt = (nr + 63) >> 6;
+  for (int u = 0;; ++u) {
+    const int ci = (u >> 1) * 8 + ((u & 1) ? 7 - slot : slot);
+    if (ci >= N_TESTS * cpt) break;
+    const int tp = ci / cpt;
+    const int t = __builtin_amdgcn_readfirstlane((int)((kByCost >> (4 * tp)) & 7u));
+    const int j = (ci - tp * cpt) * 64 + lane_id();
+    const int64_t row = j < nr ? rowOf(j) : -1;
+    if (row >= 0) {
+      double pv, sv;
+      eval_test_call(t, a.suff + row * kSuff, a.min_mw, a.min_wil, a.min_kru, pv, sv);
+      a.pvals[row * N_TESTS + t] = (float)pv;
+      a.pstats[row * N_TESTS + t] = (float)sv;
+    }
+  }
+}
+
+// The pairwise role of workgroup pb (0 <= pb < nP) with static rows: a wave
+// per row, grid-stride.
+template <int K>
+__device__ __forceinline__ void front_pairwise_static(const FrontArgs& a, const int pb) {
+  const int64_t R = a.R, first = (int64_t)pb * 4, stride = (int64_t)a.nP * 4;
+  for (int64_t row = first + wave_id(); row < R; row += stride) {
+    pw_row<K>(a.cur + row * a.ld_c, a.base + row * a.ld_b, a.n_cur, a.n_base, a.suff + row * kSuff);
+  }
+  __syncthreads();   // this workgroup's suff rows are visible to all its waves
+  FM_FT_MARK(2);
+  // local row j -> global row first + (j & 3) + (j >> 2) * stride
+  const int64_t span = R > first ? R - first : 0;
+  const int nr = (int)(((span + stride - 1) / stride) * 4);
+#ifdef FM_FRONT_TIMING
+  {
+    int64_t took = 0;
+    for (int w = 0; w < 4; ++w) took += span > w ? (span - w + stride - 1) / stride : 0;
+    FM_FT_ROWS(took);
+  }
+#endif
+  front_pvalues(a, nr, (wave_id() + pb) & 3, [&](int j) {
+    const int64_t row = first + (j & 3) + (int64_t)(j >> 2) * stride;
+    return row < R ? row : (int64_t)-1;
+  });
+}
+
 // The pairwise role of workgroup pb (0 <= pb < nP) with dynamic rows.
 template <int K>
-__device__ __forceinline__ void front_pairwise_dyn(FM_FRONT_PARAMS, const FrontDyn dq, const int pb) {
+__device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const FrontDyn& dq, const int pb) {
   __shared__ int s_rows[4][kRowCap];
   __shared__ int s_cnt[4];
   const int w = wave_id(), lane = lane_id();
-  const int W = nP * 4, Q = dq.q;
+  const int nP = a.nP, W = nP * 4, Q = dq.q;
   const int x = (pb + pb / Q) % Q;
-  const int64_t pool = R - dq.pool0;
+  const int64_t pool = a.R - dq.pool0;
   const int lo = dq.pool0 + (int)(pool * x / Q), hi = dq.pool0 + (int)(pool * (x + 1) / Q);
   const unsigned nx = (unsigned)(hi - lo);       // rows of this range (0: nobody touches its counter)
   unsigned* ctr = dq.pq + x * 32;
@@ -247,8 +333,8 @@ __device__ __forceinline__ void front_pairwise_dyn(FM_FRONT_PARAMS, const FrontD
     // the next index is requested only when the list will have room for its
     // row: every index drawn below nx is ranked by the wave that drew it
     const bool want = nx != 0u && i + 1 >= dq.s && i + 1 < kRowCap;
-    pw_row_grab<K>(cur + (int64_t)row * ld_c, base + (int64_t)row * ld_b, n_cur, n_base, suff + (int64_t)row * kSuff,
-                   want, ctr, next);
+    pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base,
+                   a.suff + (int64_t)row * kSuff, want, ctr, next);
     pending = want;
     if (lane == 0) s_rows[w][i] = row;
     ++i;
@@ -257,28 +343,14 @@ __device__ __forceinline__ void front_pairwise_dyn(FM_FRONT_PARAMS, const FrontD
   if (lane == 0) s_cnt[w] = i;
   __syncthreads();   // this workgroup's suff rows and row lists are visible to all its waves
   FM_FT_MARK(2);
-  // the p-value phase of the static role over the concatenated lists
+  // local row j: the four waves' lists, concatenated
   const int c0 = s_cnt[0], c1 = c0 + s_cnt[1], c2 = c1 + s_cnt[2], nr = c2 + s_cnt[3];
   FM_FT_ROWS(nr);
-  constexpr unsigned kByCost = 0x512034u;
-  const int cpt = (nr + 63) >> 6;
-  const int slot = (w + pb) & 3;
-  for (int u = 0;; ++u) {
-    const int ci = (u >> 1) * 8 + ((u & 1) ? 7 - slot : slot);
-    if (ci >= N_TESTS * cpt) break;
-    const int tp = ci / cpt;
-    const int t = __builtin_amdgcn_readfirstlane((int)((kByCost >> (4 * tp)) & 7u));
-    const int j = (ci - tp * cpt) * 64 + lane;
-    if (j < nr) {
-      const int ww = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
-      const int j0 = ww == 0 ? 0 : (ww == 1 ? c0 : (ww == 2 ? c1 : c2));
-      const int64_t row = s_rows[ww][j - j0];
-      double pv, sv;
-      eval_test_call(t, suff + row * kSuff, min_mw, min_wil, min_kru, pv, sv);
-      pvals[row * N_TESTS + t] = (float)pv;
-      pstats[row * N_TESTS + t] = (float)sv;
-    }
-  }
+  front_pvalues(a, nr, (w + pb) & 3, [&](int j) {
+    const int ww = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
+    const int j0 = ww == 0 ? 0 : (ww == 1 ? c0 : (ww == 2 ? c1 : c2));
+    return (int64_t)s_rows[ww][j - j0];
+  });
   // every wave of this workgroup made its last grab before the barrier above
   if (nx != 0u && threadIdx.x == 0) {
     const int full = nP / Q, rem = nP - full * Q;
@@ -290,120 +362,56 @@ __device__ __forceinline__ void front_pairwise_dyn(FM_FRONT_PARAMS, const FrontD
       __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
-  FM_FT_MARK(1);
 }
 
-// DYN: the pairwise role takes its rows from the queue above, and in the scan
-// shape the (short) history role has the lowest block ids: its workgroups are
-// placed first and are gone after a few microseconds, and the pairwise
-// workgroups that inherit their slots start late and simply grab fewer rows.
-// The streaming shape keeps the pairwise workgroups first (see the top).
-template <int NV, int K, bool DYN>
-__device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS, const FrontDyn dq) {
-  __shared__ double red[4];
-  __shared__ int redi[4];
-  FM_FT_MARK(0);
-  const int nHg = (int)gridDim.x - nP;
-  const bool hfirst = DYN && scan != 0;
-  const int pb = hfirst ? (int)blockIdx.x - nHg : (int)blockIdx.x;     // pairwise workgroup index
-  const int64_t hb = hfirst ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - nP;   // history workgroup index
-  if (pb >= 0 && pb < nP) {
-    if constexpr (DYN) {
-      front_pairwise_dyn<K>(FM_FRONT_ARGS, dq, pb);
-      return;
-    }
-    const int64_t first = (int64_t)blockIdx.x * 4, stride = (int64_t)nP * 4;
-    for (int64_t row = first + wave_id(); row < R; row += stride) {
-      pw_row<K>(cur + row * ld_c, base + row * ld_b, n_cur, n_base, suff + row * kSuff);
-    }
-    __syncthreads();   // this workgroup's suff rows are visible to all its waves
-    FM_FT_MARK(2);
-    // local row j -> global row first + (j & 3) + (j >> 2) * stride
-    const int64_t span = R > first ? R - first : 0;
-    const int nr = (int)(((span + stride - 1) / stride) * 4);
-#ifdef FM_FRONT_TIMING
-    {
-      int64_t took = 0;
-      for (int w = 0; w < 4; ++w) took += span > w ? (span - w + stride - 1) / stride : 0;
-      FM_FT_ROWS(took);
-    }
-#endif
-    // wave-sized chunks of (test, 64 rows); the test is wave-uniform so the
-    // special-function switch stays a scalar branch (a per-lane test index
-    // made the compiler keep every path live: 256 VGPRs).  Chunks are listed
-    // costliest test first (Welch's incomplete beta, then the Kolmogorov
-    // series, then the erfc tests) and dealt to the four waves back and forth
-    // (0 1 2 3 3 2 1 0 ...), so at one chunk per test the Welch and KS chunks
-    // have a wave each and the four cheap tests pair up.  Wave w of every
-    // co-resident workgroup sits on the same SIMD and all of them reach this
-    // phase together, so the deal is rotated by blockIdx: the Welch chains of
-    // neighbouring workgroups land on different SIMDs.
-    // T_T, T_KS, T_MW, T_KRU, T_WIL, T_FRI, one per nibble from the low end
-    static_assert(T_T == 4 && T_KS == 3 && T_MW == 0 && T_KRU == 2 && T_WIL == 1 && T_FRI == 5, "kByCost");
-    constexpr unsigned kByCost = 0x512034u;
-    const int cpt = (nr + 63) >> 6;
-    const int slot = (wave_id() + (int)blockIdx.x) & 3;
-    for (int u = 0;; ++u) {
-      const int ci = (u >> 1) * 8 + ((u & 1) ? 7 - slot : slot);
-      if (ci >= N_TESTS * cpt) break;
-      const int tp = ci / cpt;
-      const int t = __builtin_amdgcn_readfirstlane((int)((kByCost >> (4 * tp)) & 7u));
-      const int j = (ci - tp * cpt) * 64 + lane_id();
-      const int64_t row = first + (j & 3) + (int64_t)(j >> 2) * stride;
-      if (j < nr && row < R) {
-        double pv, sv;
-        eval_test_call(t, suff + row * kSuff, min_mw, min_wil, min_kru, pv, sv);
-        pvals[row * N_TESTS + t] = (float)pv;
-        pstats[row * N_TESTS + t] = (float)sv;
-      }
-    }
-    FM_FT_MARK(1);
-    return;
-  }
-  const int nH = nHg;
-  // Row-statistics cache (fm_row_stats.h).  scan: the host expects (nearly)
-  // every row to hit -- the history workgroups test their rows one per
-  // thread, copy the hits and reduce only the misses.  Otherwise (first tick,
-  // after an invalidation, no cache) every row is taken as a miss without
-  // looking: today's queue, plus the cache entry of each row it computes.
-  // Either way the device decides what is computed; the host's expectation
-  // only picks the shape.
-  if (scan) {
-    __shared__ int s_list[256];
-    __shared__ int s_cnt;
-    hist_scan_cached<NV>(hist, ld_h, T, R, hs, rowmap, cache, valid, hb, nH, red, redi, s_list,
-                         &s_cnt);
-    FM_FT_MARK(1);
-    return;
-  }
-  if (queue == nullptr) {
-    for (int64_t row = hb; row < R; row += nH) {
-      float mf, sd;
-      int n;
-      const int64_t p = hist_row(rowmap, row);
-      block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
-      if (threadIdx.x == 0) {
-        hs[row * 3 + 0] = mf;
-        hs[row * 3 + 1] = sd;
-        hs[row * 3 + 2] = (float)n;
-        if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
-      }
-    }
-    FM_FT_MARK(1);
-    return;
-  }
-  // Dynamic history queue: the rows are split into 8 contiguous ranges, one
-  // per XCD (workgroup ids are dealt round-robin over the XCDs), and the
-  // history workgroups of a range grab chunks of kHistChunk rows from its
-  // counter (one 128-B line per counter).  A slot freed by a finished
-  // pairwise workgroup is then filled by a history workgroup that starts late
-  // and simply takes what is left, instead of idling (static grid-stride).
-  // The next chunk index is requested while the current chunk streams.  The
-  // last workgroup of a range to find it empty resets the counters for the
-  // next tick (every other workgroup of the range has already exited).
-  // One row per grab: at the 1,250-service shard (~10 rows per workgroup) the
-  // tail waits on at most one row instead of two (0.0951/0.0919 -> 0.0937/
-  // 0.0904 ms per step, interleaved runs); neutral at 10k services.
+// The three history roles: workgroup hb of nH writes hs[row * 3 ..] of its
+// rows (hist_row_emit, fm_row_stats.h; red / redi: its reduction scratch).
+//
+// Row-statistics cache (fm_row_stats.h).  scan: the host expects (nearly)
+// every row to hit -- the history workgroups test their rows one per
+// thread, copy the hits and reduce only the misses.  Otherwise (first tick,
+// after an invalidation, no cache) every row is taken as a miss without
+// looking: the stride or the queue role, plus the cache entry of each row it
+// computes.  Either way the device decides what is computed; the host's
+// expectation only picks the shape.
+template <int NV>
+__device__ __forceinline__ void front_hist_scan(const FrontArgs& a, int64_t hb, int nH, double* red, int* redi) {
+  __shared__ int s_list[256];
+  __shared__ int s_cnt;
+  hist_scan_cached<NV>(a.hist, a.ld_h, a.T, a.R, a.hs, a.rowmap, a.cache, a.valid, hb, nH, red, redi, s_list, &s_cnt);
+}
+
+// Static grid-stride over the rows (no queue given).  This role and the queue
+// role take their pointers as __restrict__ parameters, not as FrontArgs: read
+// through the struct their row loops reloaded spilled SGPRs (+34 .. +700
+// VALU per kernel; 7 / 27 / 48 more VGPRs at NV = 10 / 12 / 16).
+template <int NV>
+__device__ __forceinline__ void front_hist_stride(const float* __restrict__ hist, int64_t ld_h, int T, int64_t R,
+                                                  float* __restrict__ hs, const int* __restrict__ rowmap,
+                                                  float* __restrict__ cache, unsigned* __restrict__ valid, int64_t hb,
+                                                  int nH, double* red, int* redi) {
+  for (int64_t row = hb; row < R; row += nH)
+    hist_row_emit<NV, false>(hist, ld_h, T, hs, rowmap, cache, valid, row, red, redi);
+}
+
+// Dynamic history queue: the rows are split into 8 contiguous ranges, one
+// per XCD (workgroup ids are dealt round-robin over the XCDs), and the
+// history workgroups of a range grab chunks of kHistChunk rows from its
+// counter (one 128-B line per counter).  A slot freed by a finished
+// pairwise workgroup is then filled by a history workgroup that starts late
+// and simply takes what is left, instead of idling (static grid-stride).
+// The next chunk index is requested while the current chunk streams.  The
+// last workgroup of a range to find it empty resets the counters for the
+// next tick (every other workgroup of the range has already exited).
+// One row per grab: at the 1,250-service shard (~10 rows per workgroup) the
+// tail waits on at most one row instead of two (0.0951/0.0919 -> 0.0937/
+// 0.0904 ms per step, interleaved runs); neutral at 10k services.
+template <int NV>
+__device__ __forceinline__ void front_hist_queue(const float* __restrict__ hist, int64_t ld_h, int T, int64_t R,
+                                                 float* __restrict__ hs, const int* __restrict__ rowmap,
+                                                 float* __restrict__ cache, unsigned* __restrict__ valid,
+                                                 unsigned* __restrict__ queue, int64_t hb, int nH, double* red,
+                                                 int* redi) {
   __shared__ unsigned s_next;
   const int xcd = (int)hb & 7;
   const int nwg = (nH >> 3) + ((nH & 7) > xcd ? 1 : 0);   // workgroups sharing this range
@@ -438,18 +446,8 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS, const FrontDyn 
     unsigned nxt = 0;
     if (threadIdx.x == 0) nxt = atomicAdd(ctr, (unsigned)kHistChunk);
     const int64_t r1 = r0 + kHistChunk < hi ? r0 + kHistChunk : hi;
-    for (int64_t row = r0; row < r1; ++row) {
-      float mf, sd;
-      int n;
-      const int64_t p = hist_row(rowmap, row);
-      block_row_stats<NV>(hist + p * ld_h, T, red, redi, mf, sd, n);
-      if (threadIdx.x == 0) {
-        hs[row * 3 + 0] = mf;
-        hs[row * 3 + 1] = sd;
-        hs[row * 3 + 2] = (float)n;
-        if (cache != nullptr) row_cache_put<false>(cache, valid, p, (unsigned)T, mf, sd, (float)n);
-      }
-    }
+    for (int64_t row = r0; row < r1; ++row)
+      hist_row_emit<NV, false>(hist, ld_h, T, hs, rowmap, cache, valid, row, red, redi);
     __syncthreads();               // everyone is done reading s_next
     if (threadIdx.x == 0) s_next = nxt;
     __syncthreads();
@@ -460,20 +458,47 @@ __device__ __forceinline__ void tick_front_body(FM_FRONT_PARAMS, const FrontDyn 
     if (d == (unsigned)nwg - 1) {
       __hip_atomic_store(ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(ctr + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (bal) xcd_rebalance(ctl, xcd, R, lo, hi);
+      if (bal) xcd_rebalance(ctl, xcd, R);
     }
+  }
+}
+
+// Block id -> role.  Static rows (tick_front_kernel, any history role): the
+// pairwise workgroups have the lowest ids (see the top).  DYN
+// (tick_front_dyn_kernel, the scan shape only: front_plan): the pairwise role
+// takes its rows from the queue above and the (short) history role has the
+// lowest block ids: its workgroups are placed first and are gone after a few
+// microseconds, and the pairwise workgroups that inherit their slots start
+// late and simply grab fewer rows.
+template <int NV, int K, bool DYN>
+__device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontDyn& dq) {
+  __shared__ double red[4];
+  __shared__ int redi[4];
+  FM_FT_MARK(0);
+  const int nH = (int)gridDim.x - a.nP;
+  const int pb = DYN ? (int)blockIdx.x - nH : (int)blockIdx.x;                  // pairwise workgroup index
+  const int64_t hb = DYN ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - a.nP;   // history workgroup index
+  if (pb >= 0 && pb < a.nP) {
+    if constexpr (DYN) front_pairwise_dyn<K>(a, dq, pb);
+    else front_pairwise_static<K>(a, pb);
+  } else if (DYN || a.scan) {
+    front_hist_scan<NV>(a, hb, nH, red, redi);
+  } else if (a.queue == nullptr) {
+    front_hist_stride<NV>(a.hist, a.ld_h, a.T, a.R, a.hs, a.rowmap, a.cache, a.valid, hb, nH, red, redi);
+  } else {
+    front_hist_queue<NV>(a.hist, a.ld_h, a.T, a.R, a.hs, a.rowmap, a.cache, a.valid, a.queue, hb, nH, red, redi);
   }
   FM_FT_MARK(1);
 }
 
 template <int NV, int K>
-__global__ __launch_bounds__(256) void tick_front_kernel(FM_FRONT_PARAMS) {
-  tick_front_body<NV, K, false>(FM_FRONT_ARGS, FrontDyn{});
+__global__ __launch_bounds__(256) void tick_front_kernel(const FrontArgs a) {
+  tick_front_body<NV, K, false>(a, FrontDyn{});
 }
 
 template <int NV, int K>
-__global__ __launch_bounds__(256) void tick_front_dyn_kernel(FM_FRONT_PARAMS, const FrontDyn dq) {
-  tick_front_body<NV, K, true>(FM_FRONT_ARGS, dq);
+__global__ __launch_bounds__(256) void tick_front_dyn_kernel(const FrontArgs a, const FrontDyn dq) {
+  tick_front_body<NV, K, true>(a, dq);
 }
 
 // The host's plan of the pairwise role for R rows, nP requested workgroups
@@ -559,27 +584,27 @@ static unsigned front_lds() {
 // (nH 0 = one workgroup per 256 rows) and no dynamic LDS caps the pairwise
 // workgroups per CU.  A wrong expectation costs time, never correctness.
 //
-// pqueue / q_ranges (fm_tick_front_dyn; nullptr / 0: static pairwise rows):
-// the pairwise role's dynamic row queue, q_ranges x 32 zero-initialised
-// uint32 kept zero between launches by the kernel itself (front_plan above;
-// one launch at a time per pqueue).  The scan shape uses it: the history
-// workgroups then have the lowest block ids, and nP is raised where the wave
-// lists would not hold R rows.  A streaming launch keeps static rows.
-static int front_launch(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
-                        int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
-                        int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
-                        const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
-                        int q_ranges, hipStream_t stream) {
+// pqueue / q_ranges (nullptr / 0: static pairwise rows): the pairwise role's
+// dynamic row queue, q_ranges x 32 zero-initialised uint32 kept zero between
+// launches by the kernel itself (front_plan above; one launch at a time per
+// pqueue).  The scan shape uses it: the history workgroups then have the
+// lowest block ids, and nP is raised where the wave lists would not hold R
+// rows.  A streaming launch keeps static rows.
+//
+// rowmap: history row of each logical row (fm_row_stats.h hist_row), or
+// nullptr for the identity.
+FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
+                         int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
+                         int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
+                         const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
+                         int q_ranges, hipStream_t stream) {
   if (R <= 0) return 0;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
   const int n = n_cur + n_base;
   if (base == nullptr || n_base <= 0 || n > 256) return (int)hipErrorInvalidValue;
   if (cache == nullptr || valid == nullptr || T <= 0) cache = nullptr, valid = nullptr;   // (tag 0 means invalid)
   const int scan = cache != nullptr && expect_miss == 0 ? 1 : 0;
-  const int64_t pmax = (R + 3) / 4;
-  if (nP <= 0 || nP > pmax) nP = (int)pmax;
   const FrontPlan plan = front_plan(R, nP, pqueue != nullptr ? q_ranges : 0, scan != 0);
-  nP = plan.nP;
   if (scan && nH <= 0) nH = (int)((R + 255) / 256);
   if (nH <= 0 || nH > R) nH = (int)R;
   // queue: 8 x 32 + 64 zero-initialised uints (the counters are kept zero
@@ -587,61 +612,24 @@ static int front_launch(const float* hist, int64_t ld_h, int T, int64_t R, float
   // workgroup per XCD range
   if (!scan && queue != nullptr && nH < 8) nH = 8;
   const int nq = (T + 3) / 4;
-  const dim3 grid((unsigned)(nP + nH)), block(256);
+  const dim3 grid((unsigned)(plan.nP + nH)), block(256);
   const unsigned lds = scan ? 0u : front_lds();
+  const FrontArgs a{R, plan.nP, scan, T, hist, ld_h, hs, rowmap, cache, valid, queue, cur, ld_c, base, ld_b, suff,
+                    n_cur, n_base, pvals, pstats, min_mw, min_wil, min_kru};
   const FrontDyn dq{pqueue, plan.q, plan.s, (int)plan.pool0};
-#define FM_TF(KK)                                                                                            \
-  do {                                                                                                       \
-    if (plan.q > 0)                                                                                          \
-      hipLaunchKernelGGL((tick_front_dyn_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS, dq);      \
-    else                                                                                                     \
-      hipLaunchKernelGGL((tick_front_kernel<NV, KK>), grid, block, lds, stream, FM_FRONT_ARGS);              \
-  } while (0)
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    constexpr int NV = decltype(nv)::value;
-    if (n <= 64) FM_TF(1);
-    else if (n <= 128) FM_TF(2);
-    else FM_TF(4);
+    auto launch = [&](auto k) {
+      constexpr int NV = decltype(nv)::value, K = decltype(k)::value;
+      if (plan.q > 0) hipLaunchKernelGGL((tick_front_dyn_kernel<NV, K>), grid, block, lds, stream, a, dq);
+      else hipLaunchKernelGGL((tick_front_kernel<NV, K>), grid, block, lds, stream, a);
+    };
+    if (n <= 64) launch(std::integral_constant<int, 1>{});
+    else if (n <= 128) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 4>{});
   });
-#undef FM_TF
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
   return 0;
-}
-
-FM_API int fm_tick_front_cached(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
-                                int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff,
-                                int nP, int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
-                                unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
-                                hipStream_t stream) {
-  return front_launch(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
-                      min_kru, pvals, pstats, queue, rowmap, cache, valid, expect_miss, nullptr, 0, stream);
-}
-
-// fm_tick_front_cached with the pairwise role's dynamic row queue.
-FM_API int fm_tick_front_dyn(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
-                             int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
-                             int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
-                             unsigned* queue, const int* rowmap, float* cache, unsigned* valid, int expect_miss,
-                             unsigned* pqueue, int q_ranges, hipStream_t stream) {
-  return front_launch(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
-                      min_kru, pvals, pstats, queue, rowmap, cache, valid, expect_miss, pqueue, q_ranges, stream);
-}
-
-FM_API int fm_tick_front_rm(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
-                            int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
-                            int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats,
-                            unsigned* queue, const int* rowmap, hipStream_t stream) {
-  return fm_tick_front_cached(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw,
-                              min_wil, min_kru, pvals, pstats, queue, rowmap, nullptr, nullptr, 1, stream);
-}
-
-FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
-                         int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
-                         int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
-                         hipStream_t stream) {
-  return fm_tick_front_rm(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
-                          min_kru, pvals, pstats, queue, nullptr, stream);
 }
 
 FM_API int fm_front_timing_read(unsigned long long* host, int n) {

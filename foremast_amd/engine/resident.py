@@ -8,7 +8,7 @@ docs/guides/design.md:31-43).  At fleet scale that is 80k x 10,080 samples =
 each history row is fetched ONCE and stays in device memory (288 GB of HBM3E
 holds ~90x the 10k x 8 fleet); a cycle only appends the samples that arrived
 since the row's newest one, and the scoring kernels read the rows in place
-through a row map (``fm_tick_front_rm`` / ``fm_hist_stats_rm``).
+through a row map (the ``rowmap`` of ``fm_tick_front`` / ``fm_hist_stats_cached``).
 
 Two layouts:
 

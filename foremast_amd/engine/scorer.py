@@ -144,8 +144,8 @@ class CanaryScorer:
         # are all expected in the row-statistics cache has no history stream
         # to make room for: front_hot_wgs, workgroups per CU again)
         self.front_wgs = front_wgs or (1.0, 4.0)
-        # dynamic row queue of the pairwise role (tick_front.hip, fm_tick_front_dyn;
-        # FM_FRONT_DYN_Q=0 keeps static rows, fm_tick_front_cached): ranges
+        # dynamic row queue of the pairwise role (tick_front.hip, fm_tick_front's
+        # pqueue / q_ranges; FM_FRONT_DYN_Q=0 keeps static rows): ranges
         self._q_ranges = int(os.environ.get("FM_FRONT_DYN_Q", "64")) if self.device.type == "cuda" else 0
         if front_hot_wgs is None:
             # with the queue (and its rotating wave priority) four pairwise
@@ -298,14 +298,11 @@ class CanaryScorer:
         if cache is not None:
             self._store_caches.add(cache)
             miss = cache.expect_miss(hview.T, R)
-        c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
         if has_base and n <= 256:
-            n_p, n_h = self._front_grid(miss)
-            LIB.call(self._front_cached_fn, ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), ptr(cur),
-                     cur.stride(0), cur.shape[1], ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h,
-                     self.pcfg.min_mann_white, self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals),
-                     ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid, int(miss), *self._dyn_args(), st)
+            LIB.call("fm_tick_front",
+                     *self._front_args(ptr(hview.hist), hview.ld, hview.T, base, cur, o, rowmap, cache, miss), st)
         else:
+            c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
             LIB.call("fm_hist_stats_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), 0, ptr(rowmap),
                      c_stats, c_valid, int(miss), st)
             if has_base and n <= C.PAIRWISE_MAX:
@@ -422,16 +419,20 @@ class CanaryScorer:
         n_h = int(fh * self._cus) if fh > 0 else 0
         return n_p, (n_h if miss or fh <= 0 else max(1, n_h))
 
-    @property
-    def _front_cached_fn(self) -> str:
-        """The cached front launch: with the pairwise role's dynamic row queue
+    def _front_args(self, hist_ptr, ld: int, T: int, base, cur, o: CanaryOutputs, rowmap, cache, miss: bool) -> tuple:
+        """Arguments of fm_tick_front, all but the stream: the history (pointer,
+        leading dimension, view length), ``rowmap`` (int32 [R]) or None, its
+        row-statistics cache or None, and whether the tick is expected to miss
+        (the launch streams the rows) or to hit; then the pairwise row queue
         unless it is switched off."""
-        return "fm_tick_front_dyn" if self._pqueue is not None else "fm_tick_front_cached"
-
-    def _dyn_args(self) -> tuple:
-        """The arguments fm_tick_front_dyn takes after fm_tick_front_cached's."""
         from ..ops._lib import ptr
-        return (ptr(self._pqueue), self._q_ranges) if self._pqueue is not None else ()
+        n_p, n_h = self._front_grid(miss)
+        c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
+        dyn = (ptr(self._pqueue), self._q_ranges) if self._pqueue is not None else (None, 0)
+        return (hist_ptr, ld, T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1], ptr(base),
+                base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white, self.pcfg.min_wilcoxon,
+                self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid,
+                int(miss), *dyn)
 
     def _bind(self, hist: torch.Tensor) -> _BoundHist | None:
         """The row-statistics cache of a history tensor bound to a launcher
@@ -513,10 +514,10 @@ class CanaryScorer:
             return g
         if bh is None:
             return capture(lambda: self.front_only(hist, base, cur, n_hist, packed_out, slot)).replay, o
-        from ..ops._lib import LIB, stream_of
+        from ..ops._lib import LIB, ptr, stream_of
         graphs = {miss: capture(lambda miss=miss: LIB.call(
-            self._front_cached_fn, *self._front_cached_args(bh, base, cur, T, o, miss), stream_of(cur)))
-            for miss in (True, False)}
+            "fm_tick_front", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, bh.cache, miss),
+            stream_of(cur))) for miss in (True, False)}
 
         def replay() -> None:
             graphs[bh.expect_miss(T, R, None)].replay()
@@ -541,33 +542,14 @@ class CanaryScorer:
                 ptr(d.score), ptr(d.valid), ptr(o.diff) if has_base else None, ptr(o.packed))
 
     def _front(self, hist, base, cur, n_hist, o: CanaryOutputs, decide: bool = True) -> None:
-        from ..ops._lib import LIB, stream_of
+        from ..ops._lib import LIB, ptr, stream_of
         T = hist.shape[1] if n_hist is None else int(n_hist)
         C.check(hist.stride(0) % 4 == 0 and hist.data_ptr() % 16 == 0, "history rows must be 16-B aligned")
-        LIB.call("fm_tick_front", *self._front_call_args(hist, base, cur, T, o), stream_of(cur))
+        # (a tensor nobody has bound: no cache, every row streams)
+        LIB.call("fm_tick_front", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, None, True),
+                 stream_of(cur))
         if decide:
             self._decide_services(cur, o, True)
-
-    def _front_call_args(self, hist, base, cur, T: int, o: CanaryOutputs) -> tuple:
-        from ..ops._lib import ptr
-        fp, fh = self.front_wgs
-        n_p = int(fp * self._cus) if fp > 0 else 0
-        n_h = int(fh * self._cus) if fh > 0 else 0
-        return (ptr(hist), hist.stride(0), T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1],
-                ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white,
-                self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue))
-
-    def _front_cached_args(self, bh: _BoundHist, base, cur, T: int, o: CanaryOutputs, miss: bool) -> tuple:
-        """Arguments of fm_tick_front_cached / fm_tick_front_dyn (``_front_cached_fn``;
-        all but the stream) over a bound history tensor, for a tick expected
-        to miss / to hit."""
-        from ..ops._lib import ptr
-        hist = bh.hist
-        n_p, n_h = self._front_grid(miss)
-        return (ptr(hist), hist.stride(0), T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1],
-                ptr(base), base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white,
-                self.pcfg.min_wilcoxon, self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue), None,
-                ptr(bh.cache.stats), ptr(bh.cache.valid), int(miss), *self._dyn_args())
 
     def split_launchers(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0,
                         front_stream=None, decide_stream=None):
@@ -584,7 +566,7 @@ class CanaryScorer:
         ``hist._version`` (any torch write) makes the next launch invalidate
         the cache on the front stream and stream the rows again; for writes
         torch does not see, :meth:`invalidate_history`."""
-        from ..ops._lib import LIB
+        from ..ops._lib import LIB, ptr
         self._no_robust("split_launchers")
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)    # validate / allocate / warm
         torch.cuda.synchronize(cur.device)
@@ -593,26 +575,21 @@ class CanaryScorer:
         fs = (front_stream or torch.cuda.current_stream(dev)).cuda_stream
         ds = (decide_stream or torch.cuda.current_stream(dev)).cuda_stream
         lib = LIB.load()
-        f_fn, d_fn = lib.fm_tick_front, lib.fm_decide_services
-        f_args = self._front_call_args(hist, base, cur, T, o) + (fs,)
+        f_fn, d_fn, R = lib.fm_tick_front, lib.fm_decide_services, cur.shape[0]
         d_args = self._decide_call_args(cur, o, True) + (ds,)
+        # without a cache (hist_cache off) every tick streams: one argument set
+        bh = self._bind(hist)
+        f_args = {miss: self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None,
+                                         bh.cache if bh is not None else None, miss) + (fs,)
+                  for miss in ((True, False) if bh is not None else (True,))}
+        expect = bh.expect_miss if bh is not None else (lambda T, R, fs: True)
+        ticked = bh.cache.ticked if bh is not None else (lambda T: None)
 
         def front() -> None:
-            rc = f_fn(*f_args)
+            rc = f_fn(*f_args[expect(T, R, fs)])
             if rc:
                 raise RuntimeError(f"fm_tick_front failed with hipError {rc}")
-
-        bh = self._bind(hist)
-        if bh is not None:
-            c_fn, R = getattr(lib, self._front_cached_fn), cur.shape[0]
-            c_args = {miss: self._front_cached_args(bh, base, cur, T, o, miss) + (fs,) for miss in (True, False)}
-            expect, ticked = bh.expect_miss, bh.cache.ticked
-
-            def front() -> None:   # noqa: F811 - the cached form replaces the plain one
-                rc = c_fn(*c_args[expect(T, R, fs)])
-                if rc:
-                    raise RuntimeError(f"{self._front_cached_fn} failed with hipError {rc}")
-                ticked(T)
+            ticked(T)
 
         def decide() -> None:
             rc = d_fn(*d_args)

@@ -127,22 +127,13 @@ _SIGS: dict[str, list] = {
                             c_void_p, c_int, c_void_p],
     "fm_lstm_forward_v": [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                           c_void_p, c_int, c_int, c_void_p],
+    # hist ld_h T R hs cur ld_c n_cur base ld_b n_base suff nP nH min_mw min_wil min_kru pvals pstats queue rowmap
+    # cache valid expect_miss pqueue q_ranges stream (rowmap, cache / valid, queue, pqueue may be null, q_ranges 0)
     "fm_tick_front": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
-                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
-    "fm_tick_front_rm": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
-                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                         c_void_p],
-    # fm_tick_front_rm + cache valid expect_miss
-    "fm_tick_front_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
-                             c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                             c_void_p, c_void_p, c_int, c_void_p],
-    # fm_tick_front_cached + pqueue q_ranges (before the stream)
-    "fm_tick_front_dyn": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
-                          c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                          c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                      c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
     # R nP q_ranges scan out[4] (int64: static rows per wave, pool start, ranges, effective nP); host only
     "fm_front_plan": [c_i64, c_int, c_int, c_int, c_void_p],
-    "fm_hist_stats_rm": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p],
     "fm_hist_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                              c_void_p],
     "fm_hist_cache_invalidate": [c_void_p, c_i64, c_void_p],

@@ -1,5 +1,5 @@
-"""Dynamic row queue of the front kernel's pairwise role (fm_tick_front_dyn,
-csrc/kernels/tick_front.hip): whichever wave ranks a row, the launch gives
+"""Dynamic row queue of the front kernel's pairwise role (fm_tick_front with a
+pqueue, csrc/kernels/tick_front.hip): whichever wave ranks a row, the launch gives
 exactly what the separate kernels give -- fm_pairwise_suff (all 14 ``suff``
 columns as raw fp64 bits), fm_pvalues_only (``pvals``, ``pstats``) and
 fm_hist_stats (``hs``).  They run the same pw_row / eval_test /
@@ -128,7 +128,7 @@ def _launch(d, R, n_p, q, miss, cache, rowmap=None):
     from foremast_amd.ops._lib import LIB, ptr, stream_of
     for t in (d.o_suff, d.o_pvals, d.o_pstats, d.o_hs):
         t.fill_(float("nan"))
-    LIB.call("fm_tick_front_dyn", ptr(d.h), d.h.stride(0), T, R, ptr(d.o_hs), ptr(d.cur), d.cur.stride(0), d.n_cur,
+    LIB.call("fm_tick_front", ptr(d.h), d.h.stride(0), T, R, ptr(d.o_hs), ptr(d.cur), d.cur.stride(0), d.n_cur,
              ptr(d.base), d.base.stride(0), d.n_base, ptr(d.o_suff), n_p, 0, MIN, MIN, MIN, ptr(d.o_pvals),
              ptr(d.o_pstats), ptr(d.queue), ptr(rowmap), ptr(cache.stats), ptr(cache.valid), miss, ptr(d.pq), q,
              stream_of(d.h))
@@ -158,13 +158,15 @@ def test_gpu_dynamic_rows_equal_the_separate_kernels(cuda, win):
     multiple of 4, static share 0 (R < 4 nP), more ranges than pool rows,
     several grabs per wave, 129 rows per wave at R = 1030 / nP = 2 (nP raised
     in the scan shape, static rows when streaming); both hints over a filled
-    and over an empty cache."""
+    and over an empty cache.  q = 0: static rows, in the scan shape too (the
+    p-value phase is one function for both row forms); pq then stays zero,
+    which _check asserts after every launch."""
     from foremast_amd.engine.resident import RowStatsCache
     d = _data(cuda, win)
     cache = RowStatsCache(RMAX + 3, cuda)
     for R in ROWS:
         for n_p in NPS:
-            for q in QS:
+            for q in (0,) + QS:
                 for miss in (0, 1):
                     for filled in (False, True):
                         if not filled:
@@ -215,7 +217,7 @@ def test_gpu_dynamic_rows_same_launch_three_times(cuda, win):
 @pytest.mark.gpu
 def test_gpu_scorer_ticks_with_the_queue_equal_static_rows(cuda, monkeypatch):
     """CanaryScorer: score_resident, split_launchers and capture_front
-    (replayed three times) go through fm_tick_front_dyn and give what a scorer
+    (replayed three times) launch with the pairwise row queue and give what a scorer
     with the queue switched off gives; the scorer's pqueue is zero after each."""
     from foremast_amd.engine.resident import HistView, RowStatsCache
     from foremast_amd.engine.scorer import CanaryScorer
@@ -223,10 +225,10 @@ def test_gpu_scorer_ticks_with_the_queue_equal_static_rows(cuda, monkeypatch):
     R = S * M
     h, b, c = C.synth_fleet(S, M, T, 5, 10, 0, device=cuda, fault_rate=0.2)
     sc = CanaryScorer(ALIASES, device=cuda)
-    assert sc._front_cached_fn == "fm_tick_front_dyn" and sc._pqueue.numel() == sc._q_ranges * 32
+    assert sc._q_ranges > 0 and sc._pqueue.numel() == sc._q_ranges * 32
     monkeypatch.setenv("FM_FRONT_DYN_Q", "0")
     ref_sc = CanaryScorer(ALIASES, device=cuda)
-    assert ref_sc._front_cached_fn == "fm_tick_front_cached" and ref_sc._pqueue is None
+    assert ref_sc._pqueue is None
     rm = torch.arange(R, dtype=torch.int32, device=cuda)
     ref = ref_sc.score_resident(HistView(h, h.stride(0), T, RowStatsCache(R, cuda)), rm, c, b)
     torch.cuda.synchronize()

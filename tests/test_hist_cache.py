@@ -93,9 +93,9 @@ def test_gpu_wrong_hint_is_still_correct(cuda, hint_miss):
     o = sc._alloc(R, c.shape[1])
 
     def front(miss, n_h):
-        LIB.call("fm_tick_front_cached", ptr(h), h.stride(0), T, R, ptr(o.hs), ptr(c), c.stride(0), c.shape[1],
+        LIB.call("fm_tick_front", ptr(h), h.stride(0), T, R, ptr(o.hs), ptr(c), c.stride(0), c.shape[1],
                  ptr(b), b.stride(0), b.shape[1], ptr(o.suff), 0, n_h, 2, 2, 2, ptr(o.pvals), ptr(o.pstats),
-                 ptr(sc._queue), None, ptr(cache.stats), ptr(cache.valid), miss, stream_of(h))
+                 ptr(sc._queue), None, ptr(cache.stats), ptr(cache.valid), miss, None, 0, stream_of(h))
     if hint_miss:
         front(1, 0)                              # fill
     for n_h in (0, 2, 700):                      # scan: 200 rows per workgroup, 300 (two passes), one
