@@ -2,8 +2,12 @@
 // complex sequence of N = Nr/2 points (z_j = x_2j + i x_2j+1), transformed by a
 // mixed-radix Stockham FFT (radices 2,3,4,5,7,9) that lives entirely in LDS
 // (one 256-thread workgroup per series; N <= 8192 complex = 64 KB), then
-// unpacked to the one-sided real spectrum.  The periodogram peak in a
-// [kmin, kmax] band gives the dominant seasonal period (docs/dynamic_autoscaling.md:5-30,
+// unpacked to the one-sided real spectrum.  (With the static reduction arrays
+// N = 8192 is just past 64 KB of LDS, and the phase profile below takes up
+// to 128 KB: gfx950 launches both as they are, no raised dynamic-LDS limit
+// needed; tests/test_series_edges.py runs N = 8192 and maxp = 16384.)  The
+// periodogram peak in a [kmin, kmax] band gives the dominant seasonal period
+// (docs/dynamic_autoscaling.md:5-30,
 // "Determine TPS seasonality & trend").
 //
 // 10,080 = 7 days at 60 s (metricsquery.go:93-97) -> N = 5040 = 7*4*9*4*5:
@@ -119,6 +123,10 @@ __device__ __forceinline__ void dft(f2 (&v)[R]) {
 }
 
 constexpr int kMaxN = 8192;
+// samples within 4 fp32 ulps of a line leave an rms of at most 4 * 2^-23 of the
+// line's magnitude; twice that covers the fp32 evaluation of the line here
+// (FLAT_RMS in ops/fft.py, docs/BRAIN_SPEC.md section 3)
+constexpr double kFlatRms = 9.5367431640625e-07;   // 2^-20
 constexpr int kThreads = 256;
 
 // Twiddles w^q, q = 0..R-1, for w = exp(2 pi i r), r in revolutions (v_sin_f32
@@ -252,8 +260,11 @@ struct FftPlan {
 
 // MAXN: compile-time bound on N (register arrays are sized by it); FN: the
 // compile-time N of a fixed plan (0: the run-time plan in `plan`).
+// The two run-time buckets that sit just under a register step (72 VGPRs, the
+// most for 7 waves per SIMD, and 128, the most for 4) are held there.
 template <int MAXN, int FN>
-__global__ __launch_bounds__(kThreads) void fft_seasonal_kernel(
+__global__ __launch_bounds__(kThreads)
+__attribute__((amdgpu_waves_per_eu(FN > 0 ? 1 : MAXN == 2048 ? 7 : MAXN == 5120 ? 4 : 1))) void fft_seasonal_kernel(
     const float* __restrict__ x, int64_t ld, int Nr, int64_t R, const float2* __restrict__ tw,
     const float2* __restrict__ tw2, FftPlan plan, int kmin, int kmax, float* __restrict__ power, int64_t ld_p,
     float2* __restrict__ spec, int64_t ld_s, int* __restrict__ period_bin, float* __restrict__ strength,
@@ -262,7 +273,7 @@ __global__ __launch_bounds__(kThreads) void fft_seasonal_kernel(
   (void)tw;   // twiddles are computed in-kernel (kept in the C ABI)
   __shared__ float redf[6][kThreads / 64];
   __shared__ int redi[kThreads / 64];
-  __shared__ float red5[5][kThreads / 64];
+  __shared__ float red5[6][kThreads / 64];
   const int64_t row = blockIdx.x;
   const int N = FN > 0 ? FN : Nr >> 1;
   const float* xr = x + row * ld;
@@ -301,15 +312,18 @@ __global__ __launch_bounds__(kThreads) void fft_seasonal_kernel(
     const float t = (float)(2 * eidx(e)) - tmid;
     return (f2){t, t + 1.f};
   };
-  f2 s2 = (f2){0.f, 0.f}, sx2 = (f2){0.f, 0.f};
+  // The sums are taken twice: a plain fp32 mean first, the pivot, then sum d
+  // and sum tc d of d = x - pivot.  d is exact for samples within a factor 2
+  // of the pivot, so the fp32 sums err by 2^-24 of the row's spread, not of
+  // its level: at a level of 1e4 over unit noise the one-pass sums left a
+  // line of 1e-3 in the detrended row (2e-2 of the rms spectrum at bins 0
+  // and 1), and a constant row a rounding-sized ramp instead of zeros.
+  f2 s2 = (f2){0.f, 0.f};
   bool bad = false;
 #pragma unroll
   for (int e = 0; e < NE; ++e) {
-    const f2 t2 = etime(e);
     const bool okx = isfinite(z[e].x), oky = isfinite(z[e].y);
-    const f2 xv = (f2){okx ? z[e].x : 0.f, oky ? z[e].y : 0.f};
-    s2 += xv;
-    sx2 += t2 * xv;
+    s2 += (f2){okx ? z[e].x : 0.f, oky ? z[e].y : 0.f};
     bad |= !(okx && oky);
   }
   // wave partials in fp32 (64 per-thread partials of 40 samples each), the
@@ -329,26 +343,42 @@ __global__ __launch_bounds__(kThreads) void fft_seasonal_kernel(
     stn = wave_sum(stn);
     sttn = wave_sum(sttn);
   }
-  const float ws = wave_sum(s2.x + s2.y), wsx = wave_sum(sx2.x + sx2.y);
-  if (lane_id() == 0) { red5[0][wv] = ws; red5[1][wv] = wsx; red5[2][wv] = cn; red5[3][wv] = stn; red5[4][wv] = sttn; }
+  const float ws = wave_sum(s2.x + s2.y);
+  if (lane_id() == 0) { red5[0][wv] = ws; red5[2][wv] = cn; red5[3][wv] = stn; red5[4][wv] = sttn; }
   __syncthreads();
-  double ds = 0.0, dsx = 0.0, dcn = 0.0, dstn = 0.0, dsttn = 0.0;
+  double ds = 0.0, dcn = 0.0, dstn = 0.0, dsttn = 0.0;
 #pragma unroll
   for (int w = 0; w < kThreads / 64; ++w) {
-    ds += red5[0][w]; dsx += red5[1][w]; dcn += red5[2][w]; dstn += red5[3][w]; dsttn += red5[4][w];
+    ds += red5[0][w]; dcn += red5[2][w]; dstn += red5[3][w]; dsttn += red5[4][w];
   }
   const double nr = (double)Nr;
   const double dc = nr - dcn;                                     // finite samples
   const double dst = -dstn;                                       // sum tc over all = 0
   const double dstt = nr * (nr * nr - 1.0) / 12.0 - dsttn;        // sum tc^2 over all
   const double cnt = dc > 0 ? dc : 1.0;
-  const double tbar = dst / cnt, xbar = ds / cnt;
+  const float piv = dc > 0 ? (float)(ds / cnt) : 0.f;
+  // second pass: z becomes d = x - piv (NaN / inf stay as they are)
+  f2 sd2 = (f2){0.f, 0.f}, sx2 = (f2){0.f, 0.f};
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    if (evalid(e)) z[e] = z[e] - piv;
+    const f2 dv = (f2){isfinite(z[e].x) ? z[e].x : 0.f, isfinite(z[e].y) ? z[e].y : 0.f};
+    sd2 += dv;
+    sx2 += etime(e) * dv;
+  }
+  const float wsd = wave_sum(sd2.x + sd2.y), wsx = wave_sum(sx2.x + sx2.y);
+  if (lane_id() == 0) { red5[1][wv] = wsx; red5[5][wv] = wsd; }
+  __syncthreads();
+  double dsd = 0.0, dsx = 0.0;
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) { dsx += red5[1][w]; dsd += red5[5][w]; }
+  const double tbar = dst / cnt, dbar = dsd / cnt;
   const double vt = dstt / cnt - tbar * tbar;
-  const double slope_d = vt > 0 ? (dsx / cnt - tbar * xbar) / vt : 0.0;
-  const float mu = dc > 0 ? (float)xbar : 0.f;
+  const double slope_d = vt > 0 ? (dsx / cnt - tbar * dbar) / vt : 0.0;
+  const float mu = dc > 0 ? (float)((double)piv + dbar) : 0.f;
   const float slope = (float)slope_d;
-  // e = x - mu - slope (tc - tbar) = x - c0 - slope tc
-  const float c0 = (float)((dc > 0 ? xbar : 0.0) - slope_d * tbar);
+  // e = x - mu - slope (tc - tbar) = d - c0 - slope tc
+  const float c0 = (float)((dc > 0 ? dbar : 0.0) - slope_d * tbar);
   // detrended samples (in place), with the Parseval terms: sum e^2, and
   // ex = (sum e_even, sum e_odd): X_0 = ex.x + ex.y, X_N = ex.x - ex.y
   f2 e2v = (f2){0.f, 0.f}, ex = (f2){0.f, 0.f};
@@ -439,8 +469,15 @@ __global__ __launch_bounds__(kThreads) void fft_seasonal_kernel(
     }
     // sum_{k=1..N} |X_k|^2 = (Nr sum e^2 - X_0^2 + X_N^2) / 2 (Parseval, real input)
     const float t = 0.5f * ((float)Nr * se - s0 * s0 + sn * sn);
+    // rounding floor: a row whose detrended samples have an rms of at most
+    // kFlatRms times the largest magnitude of its trend line is that line to
+    // fp32 rounding and has no season; what is left of it would otherwise
+    // read as one (the spectrum of a rounding-sized ramp falls as 1 / k^2:
+    // strength 0.152 at kmin = 2)
+    const double line = fabs((double)piv + (double)c0) + fabs((double)slope) * (double)tmid;
+    const bool flat = (double)se <= cnt * (kFlatRms * line) * (kFlatRms * line);
     period_bin[row] = k;
-    strength[row] = t > 0.f ? b / t : 0.f;
+    strength[row] = (t > 0.f && !flat) ? b / t : 0.f;
     mean_out[row] = mu;
     slope_out[row] = slope;
   }

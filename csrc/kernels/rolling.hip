@@ -23,6 +23,17 @@
 // keep enough rows in flight (a first version held full fp64 prefix rings,
 // 72 KB, two workgroups per CU: 2.45 TB/s).  HBM traffic: the row read once,
 // the two bands written once.
+//
+// Numerics: d = x - c is the only fp32 rounding of the samples (c itself from
+// fp64 sums).  Every sum of d and of d^2, the per-thread partials included,
+// is fp64, d^2 being exact there; the mean is c + fl32(s / n) and the
+// variance (n q - s^2) / n^2.  So mean and std are within 2^-24 max|x - c| of
+// exact plus their own fp32 rounding, wherever c lies relative to the window
+// (tests/test_series_edges.py states the bound).  What is left is the fp64
+// rounding of the tile prefixes, 2^-53 of up to 2048 d^2: on a window of
+// equal samples far from c it shows as a std of 5e-7 max|d| / sqrt(n) instead
+// of 0.  Windows of w <= 16 are summed straight from the ring and do not
+// carry it.
 #include "fm_common.h"
 
 using namespace fm;
@@ -39,26 +50,27 @@ struct Tri {
 
 __device__ __forceinline__ Tri tri_add(Tri a, Tri b) { return Tri{a.n + b.n, a.s + b.s, a.q + b.q}; }
 
-// inclusive block scan of one Tri per thread (256 threads); also returns the
-// block total.  scratch: 4 Tri in LDS.
-__device__ __forceinline__ Tri block_incl_scan(Tri v, Tri* scratch, Tri& total) {
+// inclusive block scan of one Tri per thread (256 threads); the last thread's
+// result is the block total.  scratch: 4 Tri in LDS.
+__device__ __forceinline__ Tri block_incl_scan(Tri v, Tri* scratch) {
   Tri w{wave_incl_sum(v.n), wave_incl_sum(v.s), wave_incl_sum(v.q)};
   const int wid = wave_id();
   if (lane_id() == 63) scratch[wid] = w;
   __syncthreads();
   Tri off{0.f, 0.0, 0.0};
   for (int i = 0; i < wid; ++i) off = tri_add(off, scratch[i]);
-  total = tri_add(tri_add(scratch[0], scratch[1]), tri_add(scratch[2], scratch[3]));
   __syncthreads();   // scratch is reused by the next tile
   return tri_add(w, off);
 }
 
-// contributions of one (shifted) sample: finite count, d, d^2
-__device__ __forceinline__ void contrib(float d, float& n, float& s, float& q) {
-  const bool f = isfinite(d);
+// contributions of one (shifted) sample that is ``in`` the sum: finite count
+// and d (0 when missing; selected in fp32, then widened).  Callers square d in
+// fp64, where the 48-bit product is exact: fl32(d^2) is off by 2^-24 d^2,
+// which a one-sample window showed as a std of 2.4e-4 |d|.
+__device__ __forceinline__ void contrib(float d, bool in, float& n, double& s) {
+  const bool f = isfinite(d) && in;
   n = f ? 1.f : 0.f;
-  s = f ? d : 0.f;
-  q = s * s;
+  s = (double)(f ? d : 0.f);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void rolling_stats_kernel(const float* __restrict__ x, int64_t ld_x, int T,
@@ -68,6 +80,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
   __shared__ float exn[2 * 256];                    // per-thread exclusive prefixes, two tiles
   __shared__ double exs[2 * 256], exq[2 * 256];
   __shared__ Tri scratch[4];
+  __shared__ Tri totals[2];                         // tile totals, by ring half (block-uniform: kept out of the VGPRs)
   __shared__ double red[4];
   const int64_t row = blockIdx.x;
   const float* __restrict__ xr = x + row * ld_x;
@@ -89,8 +102,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
   };
   const int r = (-w) & 7;                     // (t0 - w) mod 8, the same for every thread
   const int segback = (w + r) >> 3;           // owner segment of t0 - w is (own segment) - segback
+  const bool direct = segback <= 2;           // w <= 16: window 0 is summed from the ring samples
   float c = 0.f;
-  Tri prev_total{0.f, 0.0, 0.0};
   float nx[8];
   load8(0, nx);
   for (int tb = 0, tile = 0; tb < T; tb += kTile, ++tile) {
@@ -99,29 +112,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
     for (int k = 0; k < 8; ++k) d[k] = nx[k];
     if (tb + kTile < T) load8(tb + kTile, nx);   // in flight while this tile is scanned and written
     if (tile == 0) {
-      float ls = 0.f, lc = 0.f;
+      // summed in fp64, so that a constant row gets c = its value and d = 0 exactly
+      double ls = 0.0;
+      float lc = 0.f;
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        if (isfinite(d[k])) { ls += d[k]; lc += 1.f; }
-      const double s = block_sum<256>((double)ls, red);
+        if (isfinite(d[k])) { ls += (double)d[k]; lc += 1.f; }
+      const double s = block_sum<256>(ls, red);
       const double n = block_sum<256>((double)lc, red);
       c = n > 0 ? (float)(s / n) : 0.f;
     }
-    float an = 0.f, as = 0.f, aq = 0.f;
+    float an = 0.f;
+    double as = 0.0, aq = 0.0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       d[k] = d[k] - c;                        // NaN stays NaN
-      float n, s, q;
-      contrib(d[k], n, s, q);
-      an += n; as += s; aq = fmaf(s, s, aq);
+      float n;
+      double s;
+      contrib(d[k], true, n, s);
+      an += n; as += s; aq = fma(s, s, aq);
     }
     const int half = tile & 1;
     ring4[half * (kTile / 4) + 2 * tid] = make_float4(d[0], d[1], d[2], d[3]);
     ring4[half * (kTile / 4) + 2 * tid + 1] = make_float4(d[4], d[5], d[6], d[7]);
-    Tri total;
-    const Tri incl = block_incl_scan(Tri{an, (double)as, (double)aq}, scratch, total);
+    const Tri incl = block_incl_scan(Tri{an, as, aq}, scratch);
+    if (tid == 255) totals[half] = incl;
     const float en = incl.n - an;
-    const double es = incl.s - (double)as, eq = incl.q - (double)aq;
+    const double es = incl.s - as, eq = incl.q - aq;
     exn[half * 256 + tid] = en;
     exs[half * 256 + tid] = es;
     exq[half * 256 + tid] = eq;
@@ -130,7 +147,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
     // the 8 windows: positions g0 .. g0 + 7 (g0 = t0 - w)
     const int seg = (tb >> 3) + tid - segback;        // global owner segment of g0 (may be < 0)
     float lv[16];
-    double pn = 0.0, ps = 0.0, pq = 0.0;
+    // window 0 less its own first sample: P(t0) - P(g0), or, for w <= 16, the
+    // w - 1 samples before t0 themselves
+    double wn = direct ? 0.0 : (double)en, ws = direct ? 0.0 : es, wq = direct ? 0.0 : eq;
     if (seg + 1 >= 0) {
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -144,18 +163,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
         lv[8 * h + 0] = a.x; lv[8 * h + 1] = a.y; lv[8 * h + 2] = a.z; lv[8 * h + 3] = a.w;
         lv[8 * h + 4] = b.x; lv[8 * h + 5] = b.y; lv[8 * h + 6] = b.z; lv[8 * h + 7] = b.w;
       }
-      if (seg >= 0) {
+      if (direct) {
+        // lv[r + 1 .. 8 segback - 1], summed as they are and not as a
+        // difference of two tile prefixes, which carries 2^-53 of a prefix of
+        // up to 2048 d^2: under the square root that is 5e-7 max|d| on a
+        // window of (nearly) equal samples, w = 1 included
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          float n;
+          double s;
+          contrib(lv[i], i > r && i < 8 * segback, n, s);
+          wn += n; ws += s; wq = fma(s, s, wq);
+        }
+      } else if (seg >= 0) {
         const int eh = ((seg >> 8) & 1) * 256 + (seg & 255);
-        pn = exn[eh]; ps = exs[eh]; pq = exq[eh];
-        float sn = 0.f, ss = 0.f, sq = 0.f;
+        double pn = exn[eh], ps = exs[eh], pq = exq[eh];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          float n, s, q;
-          contrib(lv[i], n, s, q);
-          if (i <= r) { sn += n; ss += s; sq = fmaf(s, s, sq); }
+          float n;
+          double s;
+          contrib(lv[i], i <= r, n, s);
+          pn += n; ps += s; pq = fma(s, s, pq);
         }
-        pn += sn; ps += ss; pq += sq;
-        if ((seg >> 8) != tile) { pn -= prev_total.n; ps -= prev_total.s; pq -= prev_total.q; }
+        if ((seg >> 8) != tile) {
+          const Tri pt = totals[half ^ 1];
+          pn -= pt.n; ps -= pt.s; pq -= pt.q;
+        }
+        wn -= pn; ws -= ps; wq -= pq;
       }
     } else {
 #pragma unroll
@@ -170,26 +204,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
       FM_ROT(0) FM_ROT(1) FM_ROT(2) FM_ROT(3) FM_ROT(4) FM_ROT(5) FM_ROT(6) FM_ROT(7)
 #undef FM_ROT
     }
-    // window 0 = P(t0) - P(g0); window k = window k-1 + own d[k] - leaving out[k-1]
-    double wn = (double)en - pn, ws = es - ps, wq = eq - pq;
+    // window k = window k-1 + own d[k] - leaving out[k-1]
     float om[8], os[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float n, s, q;
-      contrib(d[k], n, s, q);
-      wn += n; ws += s; wq += q;
+      float n;
+      double s;
+      contrib(d[k], true, n, s);
+      wn += n; ws += s; wq = fma(s, s, wq);
       if (k > 0) {
-        contrib(out[k - 1], n, s, q);
-        wn -= n; ws -= s; wq -= q;
+        contrib(out[k - 1], true, n, s);
+        wn -= n; ws -= s; wq = fma(-s, s, wq);
       }
       if (wn >= (double)min_count && wn > 0.5) {
-        // wn is an integer <= 2048: a 1-ulp fp32 reciprocal is exact enough,
-        // and the moments stay fp64 until the variance is formed (no fp64
-        // divide / sqrt sequences per output)
-        const double inv = (double)__builtin_amdgcn_rcpf((float)wn);
+        // 1 / wn: the 1-ulp fp32 reciprocal and one Newton step in fp64 (no
+        // fp64 divide sequence per output).  The seed alone is not enough: m
+        // is a mean about c, which may lie far from the window (a row that
+        // starts with missing samples or changes level), and c + m would
+        // carry 2^-23 |m|.
+        const double i0 = (double)__builtin_amdgcn_rcpf((float)wn);
+        const double inv = i0 * fma(-wn, i0, 2.0);
         const double m = ws * inv;
         om[k] = c + (float)m;
-        os[k] = sqrtf((float)fmax(fma(-m, m, wq * inv), 0.0));
+        // variance as (n q - s^2) / n^2, not q / n - m^2: either product
+        // carries 2^-53 of itself and the reciprocal only scales the result,
+        // whereas its error in m^2 alone, 2 eps m^2, comes out of the square
+        // root as |m| sqrt(2 eps)
+        os[k] = sqrtf((float)(fmax(fma(wn, wq, -(ws * ws)), 0.0) * (inv * inv)));
       } else {
         om[k] = NaNf;
         os[k] = NaNf;
@@ -206,7 +247,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void r
       for (int k = 0; k < 8; ++k)
         if (t0 + k < T) { mr[t0 + k] = om[k]; sr[t0 + k] = os[k]; }
     }
-    prev_total = total;
     // the next tile overwrites the ring half this tile read as "previous"
     __syncthreads();
   }

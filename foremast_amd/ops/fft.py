@@ -73,13 +73,16 @@ class Seasonality:
     mean: torch.Tensor         # [R]
     power: torch.Tensor | None  # [R, Nr/2+1]
     slope: torch.Tensor | None = None  # [R] linear trend per sample (removed before the FFT)
+    spectrum: torch.Tensor | None = None  # [R, Nr/2+1] complex64 one-sided spectrum of the detrended row
 
 
 def fft_seasonal(x: torch.Tensor, nr: int | None = None, min_period: float = 30.0, max_period: float | None = None,
-                 return_power: bool = False) -> Seasonality:
+                 return_power: bool = False, return_spectrum: bool = False) -> Seasonality:
     """Dominant seasonal period of each row from the periodogram of the
-    mean-removed series (NaN -> mean).  Periods searched in
-    [min_period, max_period] samples (default up to nr/2)."""
+    detrended series (NaN -> trend line).  Periods searched in
+    [min_period, max_period] samples (default up to nr/2).  A row that is a
+    line to fp32 rounding has strength 0 (FLAT_RMS).  ``return_spectrum``
+    adds the complex one-sided spectrum of the detrended row."""
     check(x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1, "x must be [R, Nr] float32")
     R = x.shape[0]
     nr = x.shape[1] if nr is None else int(nr)
@@ -87,11 +90,13 @@ def fft_seasonal(x: torch.Tensor, nr: int | None = None, min_period: float = 30.
     max_period = nr / 2 if max_period is None else max_period
     kmin = max(1, int(np.ceil(nr / max_period)))
     kmax = min(nr // 2, int(np.floor(nr / min_period)))
+    check(kmin <= kmax, f"no spectral bin of length {nr} has a period in [{min_period}, {max_period}]")
     if not x.is_cuda:
-        pb, st, mu, pw, sl = ref_fft_seasonal(x.numpy()[:, :nr], kmin, kmax)
+        pb, st, mu, pw, sl, X = ref_fft_seasonal(x.numpy()[:, :nr], kmin, kmax, return_spectrum=True)
         t = torch.from_numpy
         return Seasonality(t(pb), t((nr / np.maximum(pb, 1)).astype(np.float32)), t(st), t(mu),
-                           t(pw) if return_power else None, t(sl))
+                           t(pw) if return_power else None, t(sl),
+                           t(X.astype(np.complex64)) if return_spectrum else None)
     require_native(x)
     check(x.stride(0) % 2 == 0, "row stride must be even")
     d = x.device
@@ -105,31 +110,57 @@ def fft_seasonal(x: torch.Tensor, nr: int | None = None, min_period: float = 30.
     mu = torch.empty((R,), dtype=torch.float32, device=d)
     sl = torch.empty((R,), dtype=torch.float32, device=d)
     pw = torch.empty((R, nr // 2 + 1), dtype=torch.float32, device=d) if return_power else None
+    sp = torch.empty((R, nr // 2 + 1), dtype=torch.complex64, device=d) if return_spectrum else None
     LIB.call("fm_fft_seasonal", ptr(x), x.stride(0), nr, R, ptr(tw), ptr(tw2), ctypes.cast(rad_c, ctypes.c_void_p),
-             len(rad), kmin, kmax, ptr(pw), 0 if pw is None else pw.stride(0), None, 0, ptr(pb), ptr(st), ptr(mu),
-             ptr(sl), stream_of(x))
+             len(rad), kmin, kmax, ptr(pw), 0 if pw is None else pw.stride(0), ptr(sp),
+             0 if sp is None else sp.stride(0), ptr(pb), ptr(st), ptr(mu), ptr(sl), stream_of(x))
     period = nr / pb.clamp(min=1).to(torch.float32)
-    return Seasonality(pb, period, st, mu, pw, sl)
+    return Seasonality(pb, period, st, mu, pw, sl, sp)
 
 
-def ref_fft_seasonal(x: np.ndarray, kmin: int, kmax: int):
+# A row whose detrended finite samples have an rms of at most FLAT_RMS times
+# the largest magnitude of its trend line has no season (strength 0): what
+# is left of it is the rounding of the samples and of the fit, and the
+# spectrum of a rounding-sized ramp falls as 1 / k^2, which would read as a
+# strong peak at the lowest bin of the band.  Samples within 4 fp32 ulps of a
+# line leave an rms of at most 4 * 2^-23 of that magnitude about the fitted
+# line; the factor 2 on top covers the fp32 evaluation of the line in the
+# kernel (docs/BRAIN_SPEC.md, section 3).
+FLAT_RMS = 2.0 ** -20
+
+
+def ref_detrend(x: np.ndarray):
+    """Least-squares line through the finite samples of each row, in fp64 ->
+    (detrended row with 0 at the missing samples, mean, slope, flat), ``flat``
+    by the FLAT_RMS rule."""
     x = np.asarray(x, dtype=np.float64)
     ok = np.isfinite(x)
-    t = np.arange(x.shape[1], dtype=np.float64)[None, :]
+    nr = x.shape[1]
+    t = np.arange(nr, dtype=np.float64)[None, :]
     n = np.maximum(ok.sum(1), 1)
-    mu = np.where(ok, x, 0).sum(1) / n
+    xz = np.where(ok, x, 0.0)
+    mu = xz.sum(1) / n
     tbar = np.where(ok, t, 0).sum(1) / n
     vt = np.where(ok, (t - tbar[:, None]) ** 2, 0).sum(1) / n
-    cov = np.where(ok, (t - tbar[:, None]) * (x - mu[:, None]), 0).sum(1) / n
+    cov = np.where(ok, (t - tbar[:, None]) * (xz - mu[:, None]), 0).sum(1) / n
     sl = np.where(vt > 0, cov / np.where(vt > 0, vt, 1), 0.0)
-    xc = np.where(ok, x - mu[:, None] - sl[:, None] * (t - tbar[:, None]), 0.0)
+    xc = np.where(ok, xz - mu[:, None] - sl[:, None] * (t - tbar[:, None]), 0.0)
+    tmid = 0.5 * (nr - 1)
+    line = np.abs(mu + sl * (tmid - tbar)) + np.abs(sl) * tmid      # max |line| over the row
+    flat = (xc * xc).sum(1) <= n * (FLAT_RMS * line) ** 2
+    return xc, mu, sl, flat
+
+
+def ref_fft_seasonal(x: np.ndarray, kmin: int, kmax: int, return_spectrum: bool = False):
+    xc, mu, sl, flat = ref_detrend(x)
     X = np.fft.rfft(xc, axis=1)
     pw = (X.real ** 2 + X.imag ** 2)
     band = pw[:, kmin:kmax + 1]
     pb = (np.argmax(band, axis=1) + kmin).astype(np.int32)
     tot = pw[:, 1:].sum(1)
-    st = np.where(tot > 0, band.max(1) / np.where(tot > 0, tot, 1), 0).astype(np.float32)
-    return pb, st, mu.astype(np.float32), pw.astype(np.float32), sl.astype(np.float32)
+    st = np.where((tot > 0) & ~flat, band.max(1) / np.where(tot > 0, tot, 1), 0).astype(np.float32)
+    out = (pb, st, mu.astype(np.float32), pw.astype(np.float32), sl.astype(np.float32))
+    return out + (X,) if return_spectrum else out
 
 
 def phase_profile(x: torch.Tensor, T: int, period: torch.Tensor, mean: torch.Tensor, maxp: int,
@@ -158,7 +189,8 @@ def ref_phase_profile(x, period, mean, maxp, slope=None):
         p = int(period[r])
         if p <= 0 or p > maxp:
             continue
-        v = x[r] - mean[r] - (0.0 if slope is None else slope[r]) * (np.arange(T) - tb)
+        # fp64 throughout: fp32 rows and means would round x - mean to fp32 first
+        v = x[r].astype(np.float64) - float(mean[r]) - (0.0 if slope is None else float(slope[r])) * (np.arange(T) - tb)
         ok = np.isfinite(v)
         ph = np.arange(T) % p
         s = np.bincount(ph[ok], weights=v[ok], minlength=p)
