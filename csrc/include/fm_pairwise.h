@@ -185,10 +185,27 @@ __device__ __forceinline__ void pw_load(const float* __restrict__ c, const float
 // row (tick_front.hip requests its next row index): loaded() runs once every
 // loaded sample has been consumed into registers (no load outstanding, the
 // sorts still ahead), done() after the last reduction, before the row's
-// stores.  The default does nothing.
+// stores.  store() is the row's sink: it gets the 14 statistics as they stand
+// after the reductions (wave-uniform integers and floats) and decides where
+// they go.  The default does nothing in loaded() / done() and has lane 0
+// convert them to the doubles of `o` (pw_store_suff).
+__device__ __forceinline__ void pw_store_suff(double* __restrict__ o, int n1, int n2, int nw, unsigned r1s,
+                                              unsigned tie, int dnum, unsigned rps, unsigned tiew, float m1, float m2,
+                                              float q1, float q2, int npos, int nzero) {
+  o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * (double)r1s; o[4] = (double)tie;
+  o[5] = (n1 > 0 && n2 > 0) ? (double)dnum / ((double)n1 * n2) : 0.0;
+  o[6] = 0.5 * (double)rps; o[7] = (double)tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
+  o[12] = npos; o[13] = nzero;
+}
+
 struct PwNoHook {
   __device__ __forceinline__ void loaded() const {}
   __device__ __forceinline__ void done() const {}
+  __device__ __forceinline__ void store(double* __restrict__ o, int n1, int n2, int nw, unsigned r1s, unsigned tie,
+                                        int dnum, unsigned rps, unsigned tiew, float m1, float m2, float q1, float q2,
+                                        int npos, int nzero) const {
+    if (lane_id() == 0) pw_store_suff(o, n1, n2, nw, r1s, tie, dnum, rps, tiew, m1, m2, q1, q2, npos, nzero);
+  }
 };
 
 template <int K, bool SPLIT = false, class Hook = PwNoHook>
@@ -326,12 +343,7 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
   // Per-row sufficient statistics; p-values are evaluated one row per THREAD
   // by pvalue_kernel (the double-precision special functions would otherwise
   // run on lane 0 with 63 lanes idle).
-  if (lane == 0) {
-    o[0] = n1; o[1] = n2; o[2] = nw; o[3] = 0.5 * (double)r1s; o[4] = (double)tie;
-    o[5] = (n1 > 0 && n2 > 0) ? (double)dnum / ((double)n1 * n2) : 0.0;
-    o[6] = 0.5 * (double)rps; o[7] = (double)tiew; o[8] = m1; o[9] = m2; o[10] = q1; o[11] = q2;
-    o[12] = npos; o[13] = nzero;
-  }
+  hook.store(o, n1, n2, nw, r1s, tie, dnum, rps, tiew, m1, m2, q1, q2, npos, nzero);
 }
 
 // ---------------------------------------------------------------------------

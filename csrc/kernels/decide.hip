@@ -17,7 +17,168 @@
 // ---------------------------------------------------------------------------
 // MAXM: metric slots in registers; EXACT: M == MAXM (no per-metric guards);
 // ONE: n_cur <= 64 (the current window is one wave-wide chunk).  The
-// specialised forms roughly halve the instruction count of the generic one.
+// specialised forms (EXACT and ONE, M = 8 or 4) take decide_service_lanes
+// below, the generic ones the loop in the kernel.
+
+// v with lane `l` (a constant) replaced by the wave-uniform s: v_writelane_b32.
+// This toolchain has no clang builtin for it, so the LLVM intrinsic is
+// declared by name; the compiler then sees a real VALU instruction and places
+// the wait states an SGPR written by a v_cmp needs before it.
+extern "C" __device__ int fm_llvm_writelane_i32(int s, int l, int v) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ int lane_put(int v, int l, int s) { return fm_llvm_writelane_i32(s, l, v); }
+
+// One level of a transposing max-reduction: a and b each hold 64 per-lane
+// candidates of their own metric; afterwards the lower lanes of every swapped
+// span hold a's pairwise maxima and the upper lanes b's (v_permlane32_swap:
+// halves of the wave, v_permlane16_swap: rows 0/1 and 2/3), so two registers
+// become one per swap + max.
+template <int S>
+__device__ __forceinline__ float max_fold(float a, float b) {
+  float lo, hi;
+  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+  if constexpr (S == 32) {
+    const auto r = __builtin_amdgcn_permlane32_swap(ua, ub, false, false);
+    lo = __uint_as_float((unsigned)r[0]); hi = __uint_as_float((unsigned)r[1]);
+  } else {
+    static_assert(S == 16, "permlane swap strides");
+    const auto r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);
+    lo = __uint_as_float((unsigned)r[0]); hi = __uint_as_float((unsigned)r[1]);
+  }
+  return lo > hi ? lo : hi;
+}
+
+// The specialised decision (M metrics exactly, n_cur <= 64).  Everything that
+// is one value per metric lives in lane m and is computed there once for all
+// metrics: the band (up, lo, inv, has_hist) from lane m's own loads, the
+// "distribution differs" bit from one scalar mask.  The per-metric loop only
+// broadcasts what the per-point compare needs (up, lo, inv and three
+// condition bits: four readlanes), its counts and flag ballots are scalars
+// written into lane m (v_writelane), and the M per-lane maxima are reduced
+// together (max_fold) instead of by M butterflies.  The expressions are those
+// of the generic loop, term for term: the outputs are the same bits.
+template <int M>
+__device__ __forceinline__ void decide_service_lanes(
+    const int64_t svc, const float* __restrict__ hs, const float* __restrict__ cur, int64_t ld_c, int n_cur,
+    const float* __restrict__ thr, const int* __restrict__ bound, const float* __restrict__ minlb, float pair_factor,
+    const float* __restrict__ pvals, int test_mask, int combine_any, float p_thr, int min_hist,
+    float* __restrict__ out_stats, unsigned long long* __restrict__ out_flags, int NW, int* __restrict__ out_count,
+    float* __restrict__ out_score, int* __restrict__ out_valid, int8_t* __restrict__ out_diff,
+    float* __restrict__ packed) {
+  static_assert(M == 8 || M == 4, "the reduction below folds 8 or 4 registers");
+  const int lane = lane_id();
+  const float NaNf = __builtin_nanf("");
+  // every load of the service up front (clamped, unpredicated)
+  const int li = lane < n_cur ? lane : n_cur - 1;
+  const int lp = lane < N_TESTS ? lane : N_TESTS - 1;
+  const int lm = lane < M ? lane : M - 1;
+  float xs[M], pv[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const int64_t row = svc * M + m;
+    xs[m] = cur[row * ld_c + li];
+    pv[m] = pvals != nullptr ? pvals[row * N_TESTS + lp] : NaNf;
+  }
+  const float* h = hs + (svc * M + lm) * 3;
+  const float mf = h[0], sd = h[1];
+  const int n = (int)h[2];
+  float th = thr[lm];
+  const int bd = bound[lm];
+  const float mlb = minlb[lm];
+  // bit m: the p-values of metric m say "differs"
+  unsigned dmask = 0u;
+  if (pvals != nullptr) {
+    const bool use = lane < N_TESTS && ((test_mask >> lane) & 1);
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+      const bool sel = use && !isnan(pv[m]);
+      const unsigned long long app = __builtin_amdgcn_ballot_w64(sel), sig = __builtin_amdgcn_ballot_w64(sel && pv[m] < p_thr);
+      const bool differs = app != 0ull && (combine_any ? sig != 0ull : sig == app);
+      dmask |= (differs ? 1u : 0u) << m;
+    }
+  }
+  // lane m: the band of metric m
+  const bool differs = (dmask >> lm) & 1u;
+  if (differs) th *= pair_factor;
+  const float up = mf + th * sd;
+  float lo = mf - th * sd;
+  if (lo < mlb) lo = mlb;
+  const bool has_hist = n >= min_hist && n > 0;
+  const float inv = sd > 0.f ? __builtin_amdgcn_rcpf(sd) : 0.f;   // z-score scale, 1-ulp rcp
+  const int cfg = (has_hist ? (bd & 3) : 0) | (sd > 0.f ? 4 : 0) | (has_hist ? 8 : 0);
+
+  int tot = 0, mask = 0, o_cnt = 0, f_lo = 0, f_hi = 0;
+  unsigned seen = 0u;   // bit m: metric m has an observed point
+  bool unknown = false;
+  float bestm[M];
+#pragma unroll
+  for (int m = 0; m < M; ++m) {
+    const float up_m = lane_bcast(up, m), lo_m = lane_bcast(lo, m), inv_m = lane_bcast(inv, m);
+    const int cfg_m = lane_bcast(cfg, m);
+    const float x = xs[m];
+    const bool obs = lane < n_cur && isfinite(x);
+    const bool hi = (cfg_m & 1) && obs && x > up_m;
+    const bool lw = (cfg_m & 2) && obs && x < lo_m;
+    const bool f = hi || lw;
+    const float z = (cfg_m & 4) ? (hi ? x - up_m : lo_m - x) * inv_m : 1e30f;
+    bestm[m] = f && z > 0.f ? z : 0.f;
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(f);
+    const int acnt = __popcll(bal);
+    const bool any_obs = __builtin_amdgcn_ballot_w64(obs) != 0ull;
+    o_cnt = lane_put(o_cnt, m, acnt);
+    f_lo = lane_put(f_lo, m, (int)(unsigned)bal);
+    f_hi = lane_put(f_hi, m, (int)(unsigned)(bal >> 32));
+    seen |= (any_obs ? 1u : 0u) << m;
+    tot += acnt;
+    if (acnt > 0) mask |= 1 << m;
+    if (!((cfg_m & 8) && any_obs)) unknown = true;
+  }
+  // fold the M registers into one whose 64 / M-lane groups each hold one
+  // metric's candidates: group g = 2 r + h (M = 8: row r, half-row h) or row r
+  // (M = 4) holds metric 4 h + rev(r), rev = {0, 2, 1, 3}
+  float e;
+  if constexpr (M == 8) {
+    const float d0 = max_fold<16>(max_fold<32>(bestm[0], bestm[1]), max_fold<32>(bestm[2], bestm[3]));
+    const float d1 = max_fold<16>(max_fold<32>(bestm[4], bestm[5]), max_fold<32>(bestm[6], bestm[7]));
+    const bool upper = (lane & 8) != 0;
+    const float keep = upper ? d1 : d0, send = upper ? d0 : d1;
+    const float got = dpp_mov_all<0x128>(send);   // row_ror:8: the other half-row
+    e = keep > got ? keep : got;
+  } else {
+    e = max_fold<16>(max_fold<32>(bestm[0], bestm[1]), max_fold<32>(bestm[2], bestm[3]));
+    const float got = dpp_mov<0x118>(e, e);       // row_shr:8 (lanes 0-7 of a row keep their own)
+    e = e > got ? e : got;
+  }
+  // inside a group: after row_shr 4, 2, 1 its last lane holds the maximum
+  { const float g = dpp_mov<0x114>(e, e); e = e > g ? e : g; }
+  { const float g = dpp_mov<0x112>(e, e); e = e > g ? e : g; }
+  { const float g = dpp_mov<0x111>(e, e); e = e > g ? e : g; }
+  // lane m fetches metric m's maximum from the last lane of its group
+  const int q = lm & 3, rev = ((q & 1) << 1) | (q >> 1);
+  const int src = M == 8 ? ((2 * rev + (lm >> 2)) * 8 + 7) : (rev * 16 + 15);
+  float o_score = __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(e)));
+  if (lane >= M) o_score = 0.f;
+  // the service maximum, into lane 0 (row_shl 4, 2, 1 over lanes 0 .. M-1)
+  float sbest = o_score;
+  if constexpr (M == 8) { const float g = dpp_mov<0x104>(sbest, sbest); sbest = sbest > g ? sbest : g; }
+  { const float g = dpp_mov<0x102>(sbest, sbest); sbest = sbest > g ? sbest : g; }
+  { const float g = dpp_mov<0x101>(sbest, sbest); sbest = sbest > g ? sbest : g; }
+  if (lane < M) {
+    const int64_t row = svc * M + lane;
+    reinterpret_cast<float4*>(out_stats)[row] = make_float4(mf, sd, up, lo);
+    out_count[row] = o_cnt;
+    out_valid[row] = (has_hist ? 1 : 0) | (((seen >> lane) & 1u) ? 2 : 0);
+    out_score[row] = o_score;
+    out_flags[row * NW] = ((unsigned long long)(unsigned)f_hi << 32) | (unsigned)f_lo;
+    if (out_diff != nullptr && pvals != nullptr) out_diff[row] = (int8_t)(differs ? 1 : 0);
+  }
+  if (lane == 0) {
+    packed[svc * 4 + 0] = (float)(tot > 0 ? 1 : (unknown ? 2 : 0));
+    packed[svc * 4 + 1] = sbest;
+    packed[svc * 4 + 2] = (float)mask;
+    packed[svc * 4 + 3] = (float)tot;
+  }
+}
+
 template <int MAXM, bool EXACT, bool ONE>
 __global__ __launch_bounds__(256) void decide_service_kernel(
     const float* __restrict__ hs, const float* __restrict__ cur, int64_t ld_c, int n_cur, int64_t S, int M,
@@ -29,6 +190,12 @@ __global__ __launch_bounds__(256) void decide_service_kernel(
   if (EXACT) M = MAXM;
   const int64_t svc = (int64_t)blockIdx.x * 4 + wave_id();
   if (svc >= S) return;
+  if constexpr (EXACT && ONE && (MAXM == 8 || MAXM == 4)) {
+    decide_service_lanes<MAXM>(svc, hs, cur, ld_c, n_cur, thr, bound, minlb, pair_factor, pvals, test_mask,
+                               combine_any, p_thr, min_hist, out_stats, out_flags, NW, out_count, out_score,
+                               out_valid, out_diff, packed);
+    return;
+  }
   const int lane = lane_id();
   const float NaNf = __builtin_nanf("");
   // phase 1: every load of the service up front (clamped, unpredicated)

@@ -192,10 +192,20 @@ struct FrontDyn {
 // uniform) after the last reduction, ahead of the row's stores.  The empty asm
 // pins that read: without it the compiler hoists the readfirstlane, and with it
 // a vmcnt(0), to right behind the fetch-add.
+//
+// The row's sink (store) keeps the fp64 out of the row: lane 0 puts the 14
+// statistics, as the raw integer / float words the reductions left, into the
+// row's 64-byte LDS slot (no conversion, no division, no global store), and
+// the workgroup turns its slots into the doubles of `suff` one row per thread
+// behind its barrier (front_raw_to_suff).  A one-lane instruction costs the
+// SIMD a full issue slot, and the conversions with their IEEE division were
+// 35-40 of them per row.
+constexpr int kRawWords = 16;   // one slot: the 14 words + 2 of padding
 struct PwGrab {
   unsigned* ctr;
   bool want;        // wave-uniform
   unsigned& next;   // out (wave-uniform), when want
+  unsigned* raw;    // the row's LDS slot (kRawWords words, 16-byte aligned)
   unsigned idx = 0;
   __device__ __forceinline__ void loaded() {
     if (want && lane_id() == 0) idx = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -206,23 +216,43 @@ struct PwGrab {
       next = (unsigned)__builtin_amdgcn_readfirstlane((int)idx);
     }
   }
+  __device__ __forceinline__ void store(double*, int n1, int n2, int nw, unsigned r1s, unsigned tie, int dnum,
+                                        unsigned rps, unsigned tiew, float m1, float m2, float q1, float q2, int npos,
+                                        int nzero) const {
+    if (lane_id() == 0) {
+      uint4* s = reinterpret_cast<uint4*>(raw);
+      s[0] = make_uint4((unsigned)n1, (unsigned)n2, (unsigned)nw, r1s);
+      s[1] = make_uint4(tie, (unsigned)dnum, rps, tiew);
+      s[2] = make_uint4(__float_as_uint(m1), __float_as_uint(m2), __float_as_uint(q1), __float_as_uint(q2));
+      *reinterpret_cast<uint2*>(raw + 12) = make_uint2((unsigned)npos, (unsigned)nzero);
+    }
+  }
 };
 
-// pw_row with the request for the wave's next row inside it.
+// One raw slot -> the row's 14 doubles, exactly pw_store_suff's operations.
+__device__ __forceinline__ void front_raw_to_suff(const unsigned* __restrict__ raw, double* __restrict__ o) {
+  const uint4 a = reinterpret_cast<const uint4*>(raw)[0], b = reinterpret_cast<const uint4*>(raw)[1];
+  const uint4 c = reinterpret_cast<const uint4*>(raw)[2];
+  const uint2 d = *reinterpret_cast<const uint2*>(raw + 12);
+  pw_store_suff(o, (int)a.x, (int)a.y, (int)a.z, a.w, b.x, (int)b.y, b.z, b.w, __uint_as_float(c.x),
+                __uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w), (int)d.x, (int)d.y);
+}
+
+// pw_row with the request for the wave's next row inside it; the row's
+// statistics go to its LDS slot `raw`.
 template <int K>
 __device__ __forceinline__ void pw_row_grab(const float* __restrict__ c, const float* __restrict__ b, int n_cur,
-                                            int n_base, double* __restrict__ o, bool want, unsigned* ctr,
-                                            unsigned& next) {
+                                            int n_base, unsigned* raw, bool want, unsigned* ctr, unsigned& next) {
   PwIn<K> in;
   if constexpr (K == 2) {
     if (n_cur <= 64 && n_base <= 64) {
       pw_load<K, true>(c, b, n_cur, n_base, in);
-      pw_compute<K, true>(in, n_cur, n_base, o, PwGrab{ctr, want, next});
+      pw_compute<K, true>(in, n_cur, n_base, nullptr, PwGrab{ctr, want, next, raw});
       return;
     }
   }
   pw_load<K>(c, b, n_cur, n_base, in);
-  pw_compute<K, false>(in, n_cur, n_base, o, PwGrab{ctr, want, next});
+  pw_compute<K, false>(in, n_cur, n_base, nullptr, PwGrab{ctr, want, next, raw});
 }
 
 // The p-value phase of a pairwise workgroup, after the barrier behind its
@@ -293,6 +323,7 @@ template <int K>
 __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const FrontDyn& dq, const int pb) {
   __shared__ int s_rows[4][kRowCap];
   __shared__ int s_cnt[4];
+  __shared__ __attribute__((aligned(16))) unsigned s_raw[4][kRowCap][kRawWords];   // 16 KB: the rows' raw statistics
   const int w = wave_id(), lane = lane_id();
   const int nP = a.nP, W = nP * 4, Q = dq.q;
   const int x = (pb + pb / Q) % Q;
@@ -333,23 +364,34 @@ __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const Fro
     // the next index is requested only when the list will have room for its
     // row: every index drawn below nx is ranked by the wave that drew it
     const bool want = nx != 0u && i + 1 >= dq.s && i + 1 < kRowCap;
-    pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base,
-                   a.suff + (int64_t)row * kSuff, want, ctr, next);
+    pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base, s_raw[w][i],
+                   want, ctr, next);
     pending = want;
     if (lane == 0) s_rows[w][i] = row;
     ++i;
   }
   __builtin_amdgcn_s_setprio(0);
   if (lane == 0) s_cnt[w] = i;
-  __syncthreads();   // this workgroup's suff rows and row lists are visible to all its waves
+  __syncthreads();   // this workgroup's raw rows and row lists are visible to all its waves
   FM_FT_MARK(2);
   // local row j: the four waves' lists, concatenated
   const int c0 = s_cnt[0], c1 = c0 + s_cnt[1], c2 = c1 + s_cnt[2], nr = c2 + s_cnt[3];
   FM_FT_ROWS(nr);
+  auto listed = [&](int j, int& ww, int& k) {   // local row j is entry k of wave ww's list
+    ww = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
+    k = j - (ww == 0 ? 0 : (ww == 1 ? c0 : (ww == 2 ? c1 : c2)));
+  };
+  // raw words -> the doubles of suff, one row per thread (nr <= 4 kRowCap = 256)
+  if ((int)threadIdx.x < nr) {
+    int ww, k;
+    listed((int)threadIdx.x, ww, k);
+    front_raw_to_suff(s_raw[ww][k], a.suff + (int64_t)s_rows[ww][k] * kSuff);
+  }
+  __syncthreads();   // this workgroup's suff rows are visible to all its waves
   front_pvalues(a, nr, (w + pb) & 3, [&](int j) {
-    const int ww = (j >= c0 ? 1 : 0) + (j >= c1 ? 1 : 0) + (j >= c2 ? 1 : 0);
-    const int j0 = ww == 0 ? 0 : (ww == 1 ? c0 : (ww == 2 ? c1 : c2));
-    return (int64_t)s_rows[ww][j - j0];
+    int ww, k;
+    listed(j, ww, k);
+    return (int64_t)s_rows[ww][k];
   });
   // every wave of this workgroup made its last grab before the barrier above
   if (nx != 0u && threadIdx.x == 0) {

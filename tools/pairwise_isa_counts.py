@@ -13,6 +13,13 @@ divergent ifs stay inside a piece).  A piece with at least ten
 layout (each sample <= 64 values; the smaller piece, its tags join only for the
 last merge) and the pooled one.  Counts are static, one pass of the body = one
 row.
+
+``--loop`` (first argument) counts the whole row loop instead: every block of
+the outermost loop that holds the permlane swaps, i.e. both layouts plus what
+they share (a row's tail behind the last wave-uniform branch -- the queue
+kernel's read-back of its next index -- is cut off the row-body pieces above,
+and the compiler may merge the two layouts' tails into one).  It adds the
+fp64, global-store and LDS-write counts of that loop.
 """
 from __future__ import annotations
 
@@ -65,7 +72,40 @@ def hist(ins: list[str]) -> dict:
     }
 
 
+def row_loop(body: str) -> list[str]:
+    """Instructions of the outermost loop that holds the permlane swaps."""
+    blocks, cur = [], None
+    for raw in body.split("\n"):
+        if re.match(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)", raw):
+            cur = (raw, [])
+            blocks.append(cur)
+            continue
+        ln = raw.strip()
+        if cur is not None and ln and not ln.startswith((".", ";")):
+            cur[1].append(ln)
+    heads: dict[str, int] = {}
+    for hdr, ins in blocks:
+        m = re.search(r"Header=(BB\d+_\d+) Depth=1", hdr)
+        if m:
+            heads[m.group(1)] = heads.get(m.group(1), 0) + sum(i.startswith("v_permlane") for i in ins)
+    if not heads:
+        return []
+    head = max(heads, key=heads.get)
+    return [i for hdr, ins in blocks if f"Header={head} " in hdr or hdr.startswith(f".L{head}:") for i in ins]
+
+
 def main() -> None:
+    if sys.argv[1] == "--loop":
+        text = open(sys.argv[2]).read()
+        for name, body in kernel_body(text, sys.argv[3]):
+            ins = row_loop(body)
+            h = hist(ins)
+            h["fp64"] = sum("f64" in i.split()[0] for i in ins)
+            h["global_store"] = sum(i.startswith("global_store") for i in ins)
+            h["ds_write"] = sum(i.startswith("ds_write") for i in ins)
+            print(name)
+            print("  row loop (both layouts + shared tail): " + "  ".join(f"{a}={b}" for a, b in h.items()))
+        return
     text = open(sys.argv[1]).read()
     sub = sys.argv[2] if len(sys.argv) > 2 else "pairwise_kernelILi2E"
     for name, body in kernel_body(text, sub):
