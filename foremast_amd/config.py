@@ -64,6 +64,13 @@ class BrainConfig:
     min_wilcoxon: int = 20                   # MIN_WILCOXON_DATA_POINTS
     min_kruskal: int = 5                     # MIN_KRUSKAL_DATA_POINTS
     pairwise_threshold_factor: float = 0.8   # [inferred] "lower threshold" factor (design.md:35)
+    # effect-size gate of the pairwise verdict (docs/BRAIN_SPEC.md, K19; all 0 / off = verdict from p-values alone):
+    # a row counts as "different" only if |Cliff's delta| >= min_effect, the Hodges-Lehmann shift is at least
+    # min_shift * |baseline median| + min_shift_abs, and (directional) the shift points at the judged bound
+    pairwise_min_effect: float = 0.0         # ML_PAIRWISE_MIN_EFFECT (0..1)
+    pairwise_min_shift: float = 0.0          # ML_PAIRWISE_MIN_SHIFT (fraction of the baseline median)
+    pairwise_min_shift_abs: float = 0.0      # ML_PAIRWISE_MIN_SHIFT_ABS (metric units)
+    pairwise_directional: bool = False       # ML_PAIRWISE_DIRECTIONAL
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -201,6 +208,11 @@ class BrainConfig:
         c.min_wilcoxon = _i(env, "MIN_WILCOXON_DATA_POINTS", c.min_wilcoxon)
         c.min_kruskal = _i(env, "MIN_KRUSKAL_DATA_POINTS", c.min_kruskal)
         c.pairwise_threshold_factor = _f(env, "ML_PAIRWISE_THRESHOLD_FACTOR", c.pairwise_threshold_factor)
+        c.pairwise_min_effect = _f(env, "ML_PAIRWISE_MIN_EFFECT", c.pairwise_min_effect)
+        c.pairwise_min_shift = _f(env, "ML_PAIRWISE_MIN_SHIFT", c.pairwise_min_shift)
+        c.pairwise_min_shift_abs = _f(env, "ML_PAIRWISE_MIN_SHIFT_ABS", c.pairwise_min_shift_abs)
+        c.pairwise_directional = str(env.get("ML_PAIRWISE_DIRECTIONAL", "") or "").strip().lower() in (
+            "1", "true", "yes", "on") or c.pairwise_directional
         if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
         c.multivariate_reject = _f(env, "ML_MULTIVARIATE_REJECT", c.multivariate_reject)

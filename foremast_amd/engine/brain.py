@@ -258,6 +258,9 @@ class Brain(BrainStateMixin):
             _, _, diff = torch.ops.foremast.pairwise_tests(
                 cur, base, self.cfg.pairwise_algorithm, float(self.cfg.pairwise_threshold),
                 int(self.cfg.min_mann_white), int(self.cfg.min_wilcoxon), int(self.cfg.min_kruskal))
+            # effect-size gate (K19, off by default): rows are in no fixed
+            # metric order here, so every row brings its own bound code
+            diff = C.gate_diff(diff, cur, base, C.EffectGate.from_config(self.cfg), tables.bound, R)
         # Model dispatch: rows are grouped by their metric type's algorithm
         # (ml_algorithmN, else ML_ALGORITHM) and each group is ONE batched zoo
         # call over its rows (per-series model selection as a

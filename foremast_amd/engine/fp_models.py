@@ -280,6 +280,11 @@ class ModelsMixin:
             pcfg = C.PairwiseConfig(cfg.pairwise_algorithm, cfg.pairwise_threshold, cfg.min_mann_white,
                                     cfg.min_wilcoxon, cfg.min_kruskal)
             _, _, diff = C.pairwise_tests(ga.cur_dev, ga.base_d, pcfg)
+            gate = C.EffectGate.from_config(cfg)
+            if gate.enabled:
+                # effect-size gate (K19): a verdict the tests set is kept only where the difference is large enough
+                bound = torch.tensor([cfg.rule_for(a).bound for a in p0.aliases], dtype=torch.int32, device=dev)
+                diff = C.gate_diff(diff, ga.cur_dev, ga.base_d, gate, bound, M)
         NW = max(1, (n + 63) // 64)
         single = len(md.subs) == 1
         hpa_algo = zoo.canonical(cfg.hpa_forecast_algorithm) if (p0.hpa and cfg.hpa_forecast_algorithm) else None

@@ -36,6 +36,11 @@ class CanaryOutputs:
     decide: C.DecideResult
     packed: torch.Tensor        # [S, 4]
     hs: torch.Tensor | None = None   # [R, 3] history mean, std, count (two-stream path)
+    # effect-size gate (K19), None when it is off or the tick has no baseline
+    effect: torch.Tensor | None = None          # [R, 4] Cliff's delta, Hodges-Lehmann shift, baseline median, N
+    effect_counts: torch.Tensor | None = None   # [R, 2] int32 #{d > 0}, #{d < 0}
+    effect_passed: torch.Tensor | None = None   # [R] int8
+    pvals_gated: torch.Tensor | None = None     # [R, 6] what the decision reads: pvals, NaN where the gate failed
 
 
 MODES = ("front", "fused", "overlap", "serial")
@@ -84,6 +89,14 @@ class CanaryScorer:
       slower on MI355X (profiles/tick_breakdown_1gpu.json: the 160-VGPR row
       image leaves 2 waves/SIMD, too few to keep HBM busy), kept for A/B;
     * ``serial`` — pairwise, then the fused stats+decide kernel.
+
+    Effect gate (``cfg.pairwise_min_effect`` / ``_min_shift`` / ``_min_shift_abs``
+    / ``_directional``, all off by default): when any is set and the tick has a
+    baseline, K19 (``fm_pairwise_effect``) runs on the tick's stream between
+    the p-values and the decision, and the decision combines the gated copy of
+    the p-values; ``CanaryOutputs.effect`` / ``effect_counts`` /
+    ``effect_passed`` report it.  A gated scorer ticks through ``score`` and
+    ``score_resident`` only.
     """
 
     def __init__(self, aliases: list[str], cfg: BrainConfig | None = None, device="cpu", overlap: bool = True,
@@ -115,6 +128,10 @@ class CanaryScorer:
         self.robust = model == "robust_moving_average_all"
         if self.robust and self.mode == "fused":
             raise ValueError("mode='fused' reads mean/std off the row image: not available for the robust model")
+        self.gate = C.EffectGate.from_config(cfg or BrainConfig())
+        if self.gate.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the pairwise effect gate (ML_PAIRWISE_MIN_EFFECT / "
+                             "_MIN_SHIFT / _MIN_SHIFT_ABS / _DIRECTIONAL) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -196,7 +213,49 @@ class CanaryScorer:
                 decide=C.alloc_decide(R, n_cur, d),
                 packed=torch.empty((R // self.M, 4), dtype=torch.float32, device=d),
             )
+            if self.gate.enabled:
+                e = C.alloc_effect(R, d)
+                o = self._out[key]
+                o.effect, o.effect_counts, o.effect_passed, o.pvals_gated = e.effect, e.counts, e.passed, e.pvals_gated
         return self._out[key]
+
+    # -- effect-size gate (K19) ----------------------------------------------
+    def _no_gate(self, what: str) -> None:
+        if self.gate.enabled:
+            raise ValueError(f"{what} is not available with the pairwise effect gate enabled "
+                             "(it ticks through score / score_resident only)")
+
+    def _gate_into(self, cur, base, o: CanaryOutputs) -> CanaryOutputs:
+        """K19 on the current stream, after the p-values of ``o`` exist and
+        before the decision reads them: fills the gate buffers of ``o``
+        (``pvals_gated`` is what ``_decide_call_args`` then hands on).
+        Returns ``o``, or its copy without gate outputs when the tick has no
+        gate or no baseline."""
+        if not self.gate.enabled:
+            return o
+        if base is None or base.shape[1] == 0:
+            return dataclasses.replace(o, effect=None, effect_counts=None, effect_passed=None, pvals_gated=None)
+        buf = C.EffectResult(o.effect, o.effect_counts, o.effect_passed, o.pvals_gated)
+        r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, o.pvals, out=buf)
+        if r is not buf:                      # padded wider than C.PAIRWISE_MAX: bucketed, its own tensors
+            o.effect.copy_(r.effect)
+            o.effect_counts.copy_(r.counts)
+            o.effect_passed.copy_(r.passed)
+            o.pvals_gated.copy_(r.pvals_gated)
+        return o
+
+    def _gate_cpu(self, cur, base, pv, df):
+        """CPU branches: (diff & passed, EffectResult or None)."""
+        if not self.gate.enabled or base is None or base.shape[1] == 0:
+            return df, None
+        r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, pv.contiguous())
+        return df & r.passed, r
+
+    @staticmethod
+    def _with_effect(o: CanaryOutputs, r) -> CanaryOutputs:
+        if r is not None:
+            o.effect, o.effect_counts, o.effect_passed, o.pvals_gated = r.effect, r.counts, r.passed, r.pvals_gated
+        return o
 
     def score(self, hist: torch.Tensor, base: torch.Tensor | None, cur: torch.Tensor,
               n_hist: int | None = None, packed_out: torch.Tensor | None = None) -> CanaryOutputs:
@@ -213,16 +272,19 @@ class CanaryScorer:
                 pv = torch.full((R, C.N_TESTS), float("nan"))
                 ps = pv.clone()
                 df = torch.zeros((R,), dtype=torch.int8)
+            df, eff = self._gate_cpu(cur, base, pv, df)
             dec = C.stats_decide(hist, cur, n_hist, self.M, self.thr, self.bound, self.minlb, df,
                                  self.cfg.pairwise_threshold_factor, self.cfg.min_historical_points)
             packed = C.service_reduce(dec.count, dec.score, dec.valid, self.M)
-            return CanaryOutputs(pv, ps, df, None, dec, packed)
+            return self._with_effect(CanaryOutputs(pv, ps, df, None, dec, packed), eff)
         o = self._alloc(R, cur.shape[1])
         if packed_out is not None:
             C.check(packed_out.shape == o.packed.shape and packed_out.is_contiguous()
                     and packed_out.dtype == torch.float32, "packed_out must be a contiguous fp32 [S, 4] tensor")
             o = dataclasses.replace(o, packed=packed_out)
         has_base = base is not None and base.shape[1] > 0
+        if not has_base:
+            o = self._gate_into(cur, None, o)
         if self.mode == "front" and has_base and cur.shape[1] + base.shape[1] <= 256:
             self._front(hist, base, cur, n_hist, o)
             return o
@@ -232,6 +294,10 @@ class CanaryScorer:
         elif self.mode == "serial":
             if has_base:
                 self._pairwise_into(cur, base, o)
+                if self.gate.enabled:
+                    # this mode's decision kernel reads `diff`, not the p-values
+                    self._gate_into(cur, base, o)
+                    o.diff.mul_(o.effect_passed)
             C.stats_decide(hist, cur, n_hist, self.M, self.thr, self.bound, self.minlb,
                            o.diff if has_base else None, self.cfg.pairwise_threshold_factor,
                            self.cfg.min_historical_points, out=o.decide)
@@ -259,6 +325,7 @@ class CanaryScorer:
                      stream_of(hist))
             if has_base:
                 main.wait_stream(side)
+                self._gate_into(cur, base, o)
             self._decide_services(cur, o, has_base)
             return o
         C.service_reduce(o.decide.count, o.decide.score, o.decide.valid, self.M, out=o.packed)
@@ -287,7 +354,8 @@ class CanaryScorer:
         C.check(rowmap.dtype == torch.int32 and rowmap.numel() == R and rowmap.is_cuda, "rowmap must be int32 [R]")
         C.check(hview.ld % 4 == 0 and hview.hist.data_ptr() % 16 == 0, "history rows must be 16-B aligned")
         C.check(self.M <= 16, "resident tick supports up to 16 metrics per service")
-        o = self._alloc(R, cur.shape[1], slot)
+        o = self._gate_into(cur, None, self._alloc(R, cur.shape[1], slot)) if not has_base \
+            else self._alloc(R, cur.shape[1], slot)
         st = stream_of(cur)
         n = cur.shape[1] + (base.shape[1] if has_base else 0)
         if self.robust:
@@ -316,6 +384,8 @@ class CanaryScorer:
                 o.pstats.copy_(s_)
         if cache is not None:
             cache.ticked(hview.T)
+        if has_base:
+            self._gate_into(cur, base, o)
         self._decide_services(cur, o, has_base)
         return o
 
@@ -336,6 +406,7 @@ class CanaryScorer:
                 pv = torch.full((R, C.N_TESTS), float("nan"))
                 ps = pv.clone()
                 df = torch.zeros((R,), dtype=torch.int8)
+            df, eff = self._gate_cpu(cur, base if has_base else None, pv, df)
             c, s, n = ref_robust_stats(hist.numpy(), T)
             x = cur.numpy()
             with np.errstate(invalid="ignore", over="ignore"):
@@ -351,7 +422,8 @@ class CanaryScorer:
             valid = has.to(torch.int32) | (torch.from_numpy(np.isfinite(x).any(1)).to(torch.int32) << 1)
             stats = torch.stack([torch.from_numpy(c), torch.from_numpy(s), up[:, 0], lo[:, 0]], 1)
             dec = C.DecideResult(stats, flags, cnt, sc, valid)
-            return CanaryOutputs(pv, ps, df, None, dec, C.service_reduce(cnt, sc, valid, self.M))
+            return self._with_effect(CanaryOutputs(pv, ps, df, None, dec, C.service_reduce(cnt, sc, valid, self.M)),
+                                     eff)
         from ..ops._lib import LIB, ptr, stream_of
         C.check(hist.dim() == 2 and hist.dtype == torch.float32 and (hist.stride(1) == 1 or hist.shape[1] <= 1)
                 and hist.shape[0] == R and 0 <= T <= hist.shape[1],
@@ -364,6 +436,7 @@ class CanaryScorer:
         LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), T, R, ptr(o.hs), stream_of(cur))
         if has_base:
             self._pairwise_wide(cur, base, o)
+        o = self._gate_into(cur, base if has_base else None, o)
         self._decide_services(cur, o, has_base)
         return o
 
@@ -401,6 +474,7 @@ class CanaryScorer:
         # invalid tag, whose row it would fill with mean / std)
         if base is not None:
             self._pairwise_wide(cur, base, o)
+        o = self._gate_into(cur, base, o)
         self._decide_services(cur, o, base is not None)
         if cache is not None:
             cache.ticked(T)
@@ -470,6 +544,7 @@ class CanaryScorer:
         in-flight step, the decision of tick k can run on another stream
         while tick k+1's front kernel runs."""
         self._no_robust("front_only")
+        self._no_gate("front_only")
         C.check(cur.is_cuda and self.mode == "front" and base is not None and base.shape[1] > 0
                 and cur.shape[1] + base.shape[1] <= 256, "front_only needs a GPU front-mode tick with a baseline")
         o = self._alloc(cur.shape[0], cur.shape[1], slot)
@@ -497,6 +572,7 @@ class CanaryScorer:
         the cache, with a launch of its own ahead of the graph, and stream the
         rows again; for writes torch does not see, :meth:`invalidate_history`."""
         self._no_robust("capture_front")
+        self._no_gate("capture_front")
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)   # warm / allocate
         torch.cuda.synchronize(cur.device)
         bh = self._bind(hist)
@@ -535,9 +611,11 @@ class CanaryScorer:
         from ..ops._lib import ptr
         mask, anyc = self.pcfg.mask_and_combine()
         d = o.decide
+        # with the effect gate on, the decision combines the gated copy (NaN rows: "no test applies")
+        pv = o.pvals if o.pvals_gated is None else o.pvals_gated
         return (ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1], cur.shape[0] // self.M,
                 self.M, ptr(self.thr), ptr(self.bound), ptr(self.minlb), float(self.cfg.pairwise_threshold_factor),
-                ptr(o.pvals) if has_base else None, mask, anyc, float(self.pcfg.p_threshold),
+                ptr(pv) if has_base else None, mask, anyc, float(self.pcfg.p_threshold),
                 int(self.cfg.min_historical_points), ptr(d.stats), ptr(d.flags), d.flags.shape[1], ptr(d.count),
                 ptr(d.score), ptr(d.valid), ptr(o.diff) if has_base else None, ptr(o.packed))
 
@@ -549,6 +627,7 @@ class CanaryScorer:
         LIB.call("fm_tick_front", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, None, True),
                  stream_of(cur))
         if decide:
+            self._gate_into(cur, base, o)
             self._decide_services(cur, o, True)
 
     def split_launchers(self, hist, base, cur, n_hist=None, packed_out=None, slot: int = 0,
@@ -568,6 +647,7 @@ class CanaryScorer:
         torch does not see, :meth:`invalidate_history`."""
         from ..ops._lib import LIB, ptr
         self._no_robust("split_launchers")
+        self._no_gate("split_launchers")
         o = self.front_only(hist, base, cur, n_hist, packed_out, slot)    # validate / allocate / warm
         torch.cuda.synchronize(cur.device)
         T = hist.shape[1] if n_hist is None else int(n_hist)
@@ -639,6 +719,7 @@ class CanaryScorer:
         captured after the tick (e.g. the verdict all-gather and the host
         copy), so a whole brain step is a single graph launch."""
         self._no_robust("capture")
+        self._no_gate("capture")
         assert cur.is_cuda
         o = self.score(hist, base, cur, n_hist, packed_out)  # warm / allocate
         if epilogue is not None:

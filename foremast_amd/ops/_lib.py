@@ -31,6 +31,10 @@ c_float = ctypes.c_float
 _SIGS: dict[str, list] = {
     "fm_pairwise_tests": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_float, c_int,
                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # cur ld_c n_cur base ld_b n_base R min_effect min_shift min_shift_abs directional bound M pvals_in effect counts
+    # passed pvals_gated stream (bound, pvals_in / pvals_gated may be null)
+    "fm_pairwise_effect": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_float, c_float, c_float, c_int,
+                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

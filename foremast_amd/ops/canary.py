@@ -136,6 +136,146 @@ def _pairwise_bucketed(cur: torch.Tensor, base: torch.Tensor, cfg: PairwiseConfi
     return pv, st, df
 
 
+@dataclass(frozen=True)
+class EffectGate:
+    """Effect-size gate of the pairwise verdict (K19, docs/BRAIN_SPEC.md): a row
+    whose tests say "different" keeps that verdict only if the difference is
+    also large enough.  All zero / false = off."""
+
+    min_effect: float = 0.0         # ML_PAIRWISE_MIN_EFFECT: |Cliff's delta| below this fails
+    min_shift: float = 0.0          # ML_PAIRWISE_MIN_SHIFT: |Hodges-Lehmann shift| as a fraction of |baseline median|
+    min_shift_abs: float = 0.0      # ML_PAIRWISE_MIN_SHIFT_ABS: the same in metric units (added to the fraction)
+    directional: bool = False       # ML_PAIRWISE_DIRECTIONAL: a shift away from a one-sided bound fails
+
+    def __post_init__(self):
+        if not 0.0 <= float(self.min_effect) <= 1.0:      # (NaN fails the comparison too)
+            raise ValueError(f"min_effect must be within [0, 1], got {self.min_effect!r}")
+        for name in ("min_shift", "min_shift_abs"):
+            v = float(getattr(self, name))
+            if not (v >= 0.0 and v != float("inf")):
+                raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return bool(self.min_effect or self.min_shift or self.min_shift_abs or self.directional)
+
+    @classmethod
+    def from_config(cls, cfg) -> "EffectGate":
+        """The gate of a ``BrainConfig`` (its four ``pairwise_*`` effect settings)."""
+        return cls(float(cfg.pairwise_min_effect), float(cfg.pairwise_min_shift), float(cfg.pairwise_min_shift_abs),
+                   bool(cfg.pairwise_directional))
+
+
+@dataclass
+class EffectResult:
+    effect: torch.Tensor                 # [R, 4] fp32: Cliff's delta, Hodges-Lehmann shift, baseline median, N
+    counts: torch.Tensor                 # [R, 2] int32: #{d > 0}, #{d < 0}
+    passed: torch.Tensor                 # [R] int8
+    pvals_gated: torch.Tensor | None     # [R, 6] fp32: pvals where passed, NaN elsewhere (None without pvals)
+
+
+def alloc_effect(R: int, device, with_pvals: bool = True) -> EffectResult:
+    return EffectResult(
+        effect=torch.empty((R, 4), dtype=torch.float32, device=device),
+        counts=torch.empty((R, 2), dtype=torch.int32, device=device),
+        passed=torch.empty((R,), dtype=torch.int8, device=device),
+        pvals_gated=torch.empty((R, N_TESTS), dtype=torch.float32, device=device) if with_pvals else None,
+    )
+
+
+def pairwise_effect(cur: torch.Tensor, base: torch.Tensor, gate: EffectGate = EffectGate(),
+                    bound: torch.Tensor | None = None, M: int = 1, pvals: torch.Tensor | None = None,
+                    out: EffectResult | None = None) -> EffectResult:
+    """Effect size of current vs baseline per row and the gate's verdict on it.
+
+    ``bound`` (int32 [M], the bound code of metric r % M; needed when the gate
+    is directional) and ``pvals`` ([R, 6] fp32, optional: ``pvals_gated`` is
+    its copy with the failing rows set to NaN, which ``fm_decide_services``
+    reads as "no test applies").  CPU tensors run the numpy reference, GPU
+    tensors K19 (wider than PAIRWISE_MAX pooled: bucketed by used width like
+    the pairwise tests)."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(M >= 1, "M must be >= 1")
+    check(not gate.directional or (bound is not None and bound.numel() == M),
+          "a directional gate needs the per-metric bound codes [M]")
+    if pvals is not None:
+        check(pvals.shape == (R, N_TESTS) and pvals.dtype == torch.float32 and pvals.is_contiguous()
+              and pvals.device == cur.device, "pvals must be a contiguous fp32 [R, 6] tensor on the samples' device")
+    if not cur.is_cuda:
+        eff, cnt = ref.pairwise_effect(cur.numpy(), base.numpy())
+        bpr = None if bound is None else bound.numpy()[np.arange(R) % M]
+        ps = ref.effect_gate(eff, bpr, gate.min_effect, gate.min_shift, gate.min_shift_abs, gate.directional)
+        pg = None
+        if pvals is not None:
+            pg = torch.from_numpy(np.where(ps[:, None] != 0, pvals.numpy(), np.float32(np.nan)).astype(np.float32))
+        return EffectResult(torch.from_numpy(eff), torch.from_numpy(cnt), torch.from_numpy(ps), pg)
+    require_native(cur)
+    n_cur, n_base = cur.shape[1], base.shape[1]
+    if n_cur + n_base > PAIRWISE_MAX:
+        return _effect_bucketed(cur, base, gate, bound, M, pvals)
+    o = out if out is not None else alloc_effect(R, cur.device, pvals is not None)
+    if bound is not None:
+        check(bound.is_cuda and bound.dtype == torch.int32 and bound.is_contiguous(), "bound must be a device int32 [M]")
+    check(pvals is None or o.pvals_gated is not None, "out has no pvals_gated buffer")
+    LIB.call("fm_pairwise_effect", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, float(gate.min_effect),
+             float(gate.min_shift), float(gate.min_shift_abs), int(gate.directional), ptr(bound), M, ptr(pvals),
+             ptr(o.effect), ptr(o.counts), ptr(o.passed), ptr(o.pvals_gated) if pvals is not None else None,
+             stream_of(cur))
+    return o
+
+
+def gate_diff(diff: torch.Tensor, cur: torch.Tensor, base: torch.Tensor, gate: EffectGate, bound: torch.Tensor,
+              M: int) -> torch.Tensor:
+    """``diff & passed`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``; row r is judged by bound code ``bound[r % M]``)."""
+    if not gate.enabled:
+        return diff
+    return diff & pairwise_effect(cur, base, gate, bound.contiguous(), M).passed
+
+
+def _effect_bucketed(cur, base, gate: EffectGate, bound, M: int, pvals) -> EffectResult:
+    """A batch padded wider than PAIRWISE_MAX pooled columns: rows bucketed by
+    their own used widths exactly as ``_pairwise_bucketed`` does; rows that
+    fit run K19 on a narrowed copy, only really wider rows the CPU oracle.
+    The gate is per row, so it is evaluated once over the assembled effects
+    (bound codes follow the ORIGINAL row index r % M)."""
+    R = cur.shape[0]
+    dev = cur.device
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    fit = (lc + lb) <= PAIRWISE_MAX
+    if fit.any() and int(lc[fit].max()) + int(lb[fit].max()) > PAIRWISE_MAX:
+        fit &= (lc <= PAIRWISE_MAX // 2) & (lb <= PAIRWISE_MAX // 2)
+    eff = torch.empty((R, 4), dtype=torch.float32, device=dev)
+    cnt = torch.empty((R, 2), dtype=torch.int32, device=dev)
+    k = torch.nonzero(fit).flatten()
+    if len(k):
+        a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+        kd = k.to(dev)
+        r1 = pairwise_effect(cur.index_select(0, kd)[:, :a].contiguous(), base.index_select(0, kd)[:, :b].contiguous())
+        eff.index_copy_(0, kd, r1.effect)
+        cnt.index_copy_(0, kd, r1.counts)
+    w = torch.nonzero(~fit).flatten()
+    if len(w):
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        e2, c2 = ref.pairwise_effect(cur.index_select(0, wd)[:, :a].cpu().numpy(),
+                                     base.index_select(0, wd)[:, :b].cpu().numpy())
+        eff.index_copy_(0, wd, torch.from_numpy(e2).to(dev))
+        cnt.index_copy_(0, wd, torch.from_numpy(c2).to(dev))
+    # the gate over the assembled rows, on the host: this path already
+    # synchronises for the widths, and the arithmetic is the reference's fp32
+    bpr = None if bound is None else bound.cpu().numpy()[np.arange(R) % M]
+    ps = ref.effect_gate(eff.cpu().numpy(), bpr, gate.min_effect, gate.min_shift, gate.min_shift_abs,
+                         gate.directional)
+    passed = torch.from_numpy(ps).to(dev)
+    pg = None
+    if pvals is not None:
+        pg = torch.where(passed[:, None] != 0, pvals, torch.full_like(pvals, float("nan")))
+    return EffectResult(eff, cnt, passed, pg)
+
+
 @dataclass
 class DecideResult:
     stats: torch.Tensor     # [R, 4] mean, std, upper, lower

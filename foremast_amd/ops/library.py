@@ -53,6 +53,27 @@ def _(cur, base, algorithm, p_threshold, min_mann_white, min_wilcoxon, min_krusk
     return (cur.new_empty((R, C.N_TESTS)), cur.new_empty((R, C.N_TESTS)), cur.new_empty((R,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K19
+@custom_op(f"{NS}::pairwise_effect", mutates_args=())
+def pairwise_effect(cur: torch.Tensor, base: torch.Tensor, bound: torch.Tensor, min_effect: float, min_shift: float,
+                    min_shift_abs: float,
+                    directional: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(effect [R, 4] = Cliff's delta, Hodges-Lehmann shift, baseline median, N;
+    counts [R, 2] int32 = #{d > 0}, #{d < 0}; passed [R] int8) of current vs
+    baseline; row r is judged by bound code ``bound[r % len(bound)]`` (K19)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(bound.dim() == 1 and bound.numel() >= 1 and bound.dtype == torch.int32, "bound must be int32 [M]")
+    gate = C.EffectGate(min_effect, min_shift, min_shift_abs, directional)
+    r = C.pairwise_effect(cur.contiguous(), base.contiguous(), gate, bound.contiguous(), bound.numel())
+    return r.effect.clone(), r.counts.clone(), r.passed.clone()
+
+
+@register_fake(f"{NS}::pairwise_effect")
+def _(cur, base, bound, min_effect, min_shift, min_shift_abs, directional):
+    R = cur.shape[0]
+    return (cur.new_empty((R, 4)), cur.new_empty((R, 2), dtype=torch.int32), cur.new_empty((R,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -179,5 +200,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

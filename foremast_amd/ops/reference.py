@@ -305,3 +305,89 @@ def synth_fleet(S, M, T, P, W, svc0, seed, fault_rate, fault_mag, ldh):
     shift = level * np.float32(fault_mag) * (np.float32(1.0) + amp_d + amp_w)
     cur = np.where(faulty, cur + shift, cur).astype(np.float32)
     return hist, base.astype(np.float32), cur
+
+
+# ---------------------------------------------------------------------------
+# effect size of current vs baseline (K19), straight from the definitions in
+# docs/BRAIN_SPEC.md: every pair difference materialised in fp32 and sorted
+
+
+def _mid_sorted(xs, n):
+    """Median of the first n entries of every ascending row of xs (fp32):
+    the middle one, or 0.5 * lo + 0.5 * up of the two middle ones; NaN if n == 0."""
+    f = np.float32
+    R = xs.shape[0]
+    out = np.full(R, np.nan, dtype=np.float32)
+    ok = n > 0
+    if xs.shape[1] and ok.any():
+        r = np.nonzero(ok)[0]
+        lo = xs[r, (n[r] - 1) // 2].astype(np.float32)
+        up = xs[r, n[r] // 2].astype(np.float32)
+        with np.errstate(invalid="ignore", over="ignore"):
+            out[r] = f(0.5) * lo + f(0.5) * up
+    return out
+
+
+def pairwise_effect(cur, base, chunk_elems: int = 1 << 22):
+    """(effect [R, 4] fp32 = (Cliff's delta, Hodges-Lehmann shift, baseline
+    median, N), counts [R, 2] int32 = (#{d > 0}, #{d < 0})) over the
+    N = n1 * n2 differences d = fl32(x_i - y_j) of the finite samples of each
+    row.  NaN / +-inf samples are missing; N == 0 gives NaN and zero counts."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    R, nc = cur.shape
+    nb = base.shape[1]
+    effect = np.full((R, 4), np.nan, dtype=np.float32)
+    counts = np.zeros((R, 2), dtype=np.int32)
+    effect[:, 3] = 0.0
+    if R == 0:
+        return effect, counts
+    x = np.where(np.isfinite(cur), cur, np.float32(np.nan))
+    y = np.where(np.isfinite(base), base, np.float32(np.nan))
+    n1 = np.isfinite(cur).sum(1).astype(np.int64)
+    n2 = np.isfinite(base).sum(1).astype(np.int64)
+    N = n1 * n2
+    effect[:, 3] = N.astype(np.float32)
+    if nc == 0 or nb == 0:
+        return effect, counts
+    bmed = _mid_sorted(np.sort(y, axis=1), n2)          # NaN sorts last
+    step = max(1, chunk_elems // (nc * nb))
+    for r0 in range(0, R, step):
+        r1 = min(R, r0 + step)
+        with np.errstate(invalid="ignore", over="ignore"):
+            d = (x[r0:r1, :, None] - y[r0:r1, None, :]).reshape(r1 - r0, nc * nb)
+        counts[r0:r1, 0] = (d > 0).sum(1)
+        counts[r0:r1, 1] = (d < 0).sum(1)
+        d.sort(axis=1)
+        effect[r0:r1, 1] = _mid_sorted(d, N[r0:r1])
+    ok = N > 0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        delta = (counts[:, 0] - counts[:, 1]).astype(np.float32) / N.astype(np.float32)
+    effect[:, 0] = np.where(ok, delta, np.float32(np.nan))
+    effect[:, 2] = np.where(ok, bmed, np.float32(np.nan))
+    return effect, counts
+
+
+def effect_gate(effect, bound_per_row, min_effect, min_shift, min_shift_abs, directional):
+    """passed [R] int8 of the effect-size gate: 0 where the row's difference is
+    too small (|delta| < min_effect, or the shift is zero or below
+    min_shift * |base_med| + min_shift_abs, all fp32) or, with ``directional``,
+    points away from the only bound the metric judges (bound 1: shift <= 0,
+    bound 2: shift >= 0).  A row with NaN delta / shift passes: the gate never
+    sets a verdict, it only clears one."""
+    f = np.float32
+    e = np.asarray(effect, dtype=np.float32)
+    delta, shift, bmed = e[:, 0], e[:, 1], e[:, 2]
+    me, ms, ma = f(min_effect), f(min_shift), f(min_shift_abs)
+    fail = np.zeros(e.shape[0], dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if me > 0:
+            fail |= np.abs(delta) < me
+        if ms > 0 or ma > 0:
+            a = np.abs(shift)
+            fail |= ~((a > 0) & (a >= ms * np.abs(bmed) + ma))
+        if directional:
+            b = np.asarray(bound_per_row)
+            fail |= ((b == 1) & (shift <= 0)) | ((b == 2) & (shift >= 0))
+    fail &= ~(np.isnan(delta) | np.isnan(shift))
+    return (~fail).astype(np.int8)
