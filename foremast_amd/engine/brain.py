@@ -336,9 +336,19 @@ class Brain(BrainStateMixin):
             return {}
         return {"block": self.cfg.trend_block_for(self.step), "trend_min_blocks": self.cfg.trend_min_blocks}
 
+    def _seasonal_trend_args(self, algorithm: str) -> dict:
+        """``period`` / ``smooth`` / ``trend_min_blocks`` of a zoo call:
+        SEASONAL_PERIOD, SEASONAL_SMOOTH and TREND_MIN_BLOCKS for
+        ``seasonal_trend_robust``, nothing for any other model."""
+        if zoo.canonical(algorithm) != "seasonal_trend_robust":
+            return {}
+        return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth,
+                "trend_min_blocks": self.cfg.trend_min_blocks}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
-        return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm)}
+        return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
+                **self._seasonal_trend_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -871,7 +881,8 @@ class Brain(BrainStateMixin):
                                  lstm_model=self.lstm_model,
                                  cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_args(self.cfg.hpa_forecast_algorithm),
-                                 **self._trend_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._trend_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

@@ -24,6 +24,7 @@ robust_moving_average           median / MAD over the last ``window``   K13 (vie
 seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
 shift_robust                    median / MAD behind the last shift      K15 + band decide
 trend_robust                    repeated-median line + residual MAD     K16 + band decide
+seasonal_trend_robust           repeated-median line + phase profile    K20 + band decide
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -52,7 +53,7 @@ from ..ops import smoothing as SM
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
-              "trend_robust", "robust_multivariate")
+              "trend_robust", "robust_multivariate", "seasonal_trend_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -72,6 +73,8 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "shift_mad": "shift_robust",
            "trend_robust": "trend_robust", "robust_trend": "trend_robust", "trend_median": "trend_robust",
            "repeated_median": "trend_robust",
+           "seasonal_trend_robust": "seasonal_trend_robust", "trend_seasonal_robust": "seasonal_trend_robust",
+           "robust_seasonal_trend": "seasonal_trend_robust", "robust_stl": "seasonal_trend_robust",
            "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
            "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
@@ -148,7 +151,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     ``shift_threshold`` and ``min_blocks`` are ``shift_robust``'s block length
     in samples (default 1,440: a day at 60 s), score threshold and the blocks
     a new level must have held; ``trend_robust`` cuts its blocks by ``block``
-    too and fits a slope from ``trend_min_blocks`` non-empty ones.
+    too and fits a slope from ``trend_min_blocks`` non-empty ones, and
+    ``seasonal_trend_robust`` from as many non-empty cycles of ``period``.
     ``mvn_reject`` is ``robust_multivariate``'s rejection limit in MAD-sigmas
     (<= 0: nothing is rejected)."""
     algo = canonical(algorithm)
@@ -198,6 +202,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     if algo == "trend_robust":
         # gated on the finite count of the residuals the kernel modelled
         fc, sigma, nfin = _trend_robust(hist, T, H, block or 1440, trend_min_blocks)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "seasonal_trend_robust":
+        # gated on the finite count of the residuals the kernel modelled
+        fc, sigma, nfin = _seasonal_trend_robust(hist, T, H, period, smooth, trend_min_blocks)
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
@@ -269,11 +279,12 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
-FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust")
+FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust")
 
 
 def seasonal_start(T: int, period: int | None) -> int:
-    """First history column ``seasonal_robust`` reads when ``period`` is given:
+    """First history column ``seasonal_robust`` (and ``seasonal_trend_robust``,
+    whose span is the same) reads when ``period`` is given:
     the start of its span of whole cycles, or 0 when it falls back to the
     whole-history median (and when the period is still to be detected)."""
     from ..ops import misc as MI
@@ -317,6 +328,23 @@ def _trend_robust(hist, T, H, block, min_blocks):
     return center[:, None] + slope[:, None] * h[None, :], sigma, nfin
 
 
+def _seasonal_trend_robust(hist, T, H, period, smooth, min_blocks):
+    """Repeated-median line through the medians of the last whole cycles of
+    the history, a per-phase median profile of the residuals about it and
+    their MAD-sigma, K20 -> (forecast [R, H], sigma [R], finite count [R]).
+    The span is ``seasonal_robust``'s (:func:`seasonal_start`), ``period``
+    None is detected from the history, and so is the fallback: a history
+    shorter than two periods, or a period too long for the kernel's budget,
+    gets a constant forecast of the whole-history median with K13's sigma
+    (slope 0)."""
+    from ..ops import misc as MI
+    m = int(period or _detect_period(hist, T))
+    if MI.seasonal_cycles(T, m) >= 2:
+        return MI.seasonal_trend_robust(hist, T, m, H, smooth, int(min_blocks))[:3]
+    center, sigma, nfin = MI.robust_stats(hist, T)
+    return center[:, None].expand(-1, H), sigma, nfin
+
+
 def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | None = None,
              lstm_model=None, cache: CacheContext | None = None,
              smooth: int = 5, block: int | None = None,
@@ -351,6 +379,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return _seasonal_robust(hist, T, H, period, smooth)[:2]
     if algo == "trend_robust":
         return _trend_robust(hist, T, H, block or 1440, trend_min_blocks)[:2]
+    if algo == "seasonal_trend_robust":
+        return _seasonal_trend_robust(hist, T, H, period, smooth, trend_min_blocks)[:2]
     raise ValueError(f"{algorithm!r} is not a forecasting model ({', '.join(FORECASTERS)})")
 
 

@@ -103,6 +103,9 @@ _SIGS: dict[str, list] = {
     "fm_shift_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_float, c_int, c_void_p, c_void_p],
     # hist ld T R L J min_blocks out stream
     "fm_trend_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_void_p, c_void_p],
+    # hist ld T R m J k min_blocks H forecast ldf stats profile stream
+    "fm_seasonal_trend_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64,
+                                 c_void_p, c_void_p, c_void_p],
     "fm_hpa_score": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.c_double, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p],

@@ -739,6 +739,72 @@ def trend_robust(hist: torch.Tensor, T: int, L: int, min_blocks: int = 3):
     return out[:, 0], out[:, 1], out[:, 2].to(torch.int32), out[:, 3]
 
 
+# --------------------------------------------------------------------------- K20
+def ref_seasonal_trend_robust(hist, T: int, m: int, H: int, smooth: int = 5, min_blocks: int = 3):
+    """Robust trend + per-phase profile model of ``hist[r, :T]`` with period
+    ``m`` -> (forecast [R, H] f32, sigma [R] f32, n [R] int32, slope [R] f32,
+    nblocks [R] int32, profile [R, m] f32): :func:`ref_trend_robust` and
+    :func:`ref_seasonal_robust` composed, fp32 unless they say otherwise.
+
+    The span is the last ``N = J * m`` columns (:func:`seasonal_cycles`, ``J
+    >= 2``); a leading partial cycle is ignored.  ``slope`` and ``nblocks``
+    are those of ``ref_trend_robust(span, N, L=m, min_blocks)``: the blocks
+    are the cycles, so a cycle of any shape moves every block median alike.
+    The line is anchored at the last sample: ``r_i = x_i - (slope * float(i -
+    (N - 1)))``, the product rounded to fp32 and then the difference (no fused
+    multiply-add).  ``(_, sigma, n, profile)`` are ``ref_seasonal_robust(r, N,
+    m, H, smooth)``: the profile carries the level at the end of the history
+    plus the cycle, and ``n`` counts the finite residuals (an overflowed one
+    is missing).  ``forecast[:, h - 1] = profile[(h - 1) % m] + (slope *
+    float(h))``, the product rounded, then the sum; a NaN profile phase gives
+    a NaN forecast.  A row with ``slope == 0`` equals
+    :func:`ref_seasonal_robust` of the span as floats."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    T, m, H = int(T), int(m), int(H)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_trend_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    N = J * m
+    span = x[:, T - N:T]
+    _, _, _, slope, nblocks = ref_trend_robust(span, N, m, min_blocks)
+    with np.errstate(invalid="ignore", over="ignore"):
+        t = (np.arange(N, dtype=np.int64) - (N - 1)).astype(np.float32)
+        r = (span - (slope[:, None] * t[None, :]).astype(np.float32)).astype(np.float32)
+        fc0, sigma, n, profile = ref_seasonal_robust(r, N, m, H, smooth)
+        h = np.arange(1, H + 1, dtype=np.int64).astype(np.float32)
+        forecast = (fc0 + (slope[:, None] * h[None, :]).astype(np.float32)).astype(np.float32)
+    return forecast, sigma, n, slope, nblocks, profile
+
+
+def seasonal_trend_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: int = 5, min_blocks: int = 3,
+                          want_profile: bool = False):
+    """K20: (forecast [R, H], sigma [R], n [R] int32, slope [R]) of
+    :func:`ref_seasonal_trend_robust` over ``hist[:, :T]``, and the profile
+    [R, m] behind them when ``want_profile``.  ``hist`` may be any column view
+    with unit column stride: rows need 4-byte alignment only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, m, H, mb = int(T), int(m), int(H), int(min_blocks)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_trend_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    check(H >= 0, "H must be >= 0")
+    check(mb >= 2, "min_blocks must be >= 2")
+    if not hist.is_cuda:
+        ref = ref_seasonal_trend_robust(hist.numpy(), T, m, H, smooth, mb)
+        fc, sg, n, sl, _, pr = (torch.from_numpy(a) for a in ref)
+        return (fc, sg, n, sl, pr) if want_profile else (fc, sg, n, sl)
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    fc = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    stats = torch.empty((R, 4), dtype=torch.float32, device=hist.device)
+    prof = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    if R:
+        LIB.call("fm_seasonal_trend_robust", ptr(hist), hist.stride(0), T, R, m, J, seasonal_halfwidth(m, smooth), mb, H,
+                 ptr(fc), max(H, 1), ptr(stats), ptr(prof), stream_of(hist))
+    out = (fc, stats[:, 0], stats[:, 1].to(torch.int32), stats[:, 2])
+    return out + (prof,) if want_profile else out
+
+
 # --------------------------------------------------------------------------- K8
 SLA_HINTS = ("latency", "error", "5xx", "4xx", "sla")
 REASONS = {0: "hpa is holding", 1: "hpa is scaling up", 2: "hpa is scaling down",
