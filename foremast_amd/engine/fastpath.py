@@ -26,7 +26,8 @@ Per cycle (judgement sequence, .gitbook/assets/foremastjudgementsequencediagram.
    bulk update.
 
 Wide pairwise windows never fail a cycle: <= 256 points take the role-split
-kernel, <= 1024 the separate pairwise kernel, wider ones the fp64 CPU oracle;
+kernel, <= 1024 the separate pairwise kernel, <= 8192 the workgroup kernel K21
+(``ops/canary.py`` PAIRWISE_WIDE_MAX), wider ones the fp64 CPU oracle;
 a group whose scoring raises is re-scored job by job and a job that still
 fails is closed ``completed_unknown`` with the error as reason.
 
@@ -44,6 +45,7 @@ from __future__ import annotations
 
 import os
 
+from ..ops import canary as _canary_ops
 from .fp_arrays import ArraysMixin
 from .fp_fetch import FetchMixin
 from .fp_finish import FinishMixin
@@ -90,6 +92,7 @@ class FastPath(PlanMixin, FetchMixin, ArraysMixin, ModelsMixin, FinishMixin):
         self._es_plan = None      # (keys, cache lookup) a declined fused cycle hands to es_forecast
         self.fused_steps = 0
         self.robust_ticks = 0                       # static robust_moving_average_all groups ticked resident
+        self._routes0 = _canary_ops.route_rows()    # the process-wide pairwise route counts when this path began
         self.fused_declined: dict[str, int] = {}   # why a forecasting group's cycle took the op-by-op path
         self._col: dict = {}      # column-wise fetched windows of sliding groups (consumed by _arrays)
         self._ring = None         # merged sliding mode: host ring of the newest grid columns
@@ -147,3 +150,13 @@ class FastPath(PlanMixin, FetchMixin, ArraysMixin, ModelsMixin, FinishMixin):
         self._specs: dict = {}     # url -> RangeSpec | None of the claim being prepared
         self.evicted: set = set()  # job ids moved to the general path (take_evicted)
         self._algos: dict = {}     # alias tuple -> canonical algorithms
+
+    # pairwise rows that left the wave kernels since this path began (ops/canary.py route counter): windows
+    # of more than PAIRWISE_MAX pooled points on K21, of more than PAIRWISE_WIDE_MAX on the host oracle
+    @property
+    def pairwise_wide_rows(self) -> int:
+        return _canary_ops.route_rows()["wide"] - self._routes0["wide"]
+
+    @property
+    def pairwise_oracle_rows(self) -> int:
+        return _canary_ops.route_rows()["oracle"] - self._routes0["oracle"]

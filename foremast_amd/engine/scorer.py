@@ -338,8 +338,9 @@ class CanaryScorer:
         (engine/resident.py): logical row r reads history row ``rowmap[r]`` of
         ``hview.hist`` in place.  GPU: one role-split front launch when the
         pairwise windows fit a wave-sorted 256 (n_cur + n_base <= 256),
-        otherwise history stats || pairwise (<= C.PAIRWISE_MAX on the GPU,
-        wider on the CPU oracle) — then the decision kernel.  Rows are services x M.
+        otherwise history stats || pairwise (the wave kernel up to
+        C.PAIRWISE_MAX, the workgroup kernel K21 up to C.PAIRWISE_WIDE_MAX, the CPU
+        oracle beyond) — then the decision kernel.  Rows are services x M.
         A view that carries a row-statistics cache (a static store's) has only
         the rows written since their last tick reduced again; a hand-made
         ``HistView`` without one streams every row, as does ``hist_cache=False``."""
@@ -377,8 +378,9 @@ class CanaryScorer:
                 self._pairwise_into(cur, base, o, combine=False)
             elif has_base:
                 # padded wider than the register sort: rows bucketed by their
-                # own widths, only really wide rows (> C.PAIRWISE_MAX pooled
-                # points, rare) on the fp64 CPU oracle
+                # own widths, rows of more than C.PAIRWISE_MAX pooled points
+                # on K21, only those beyond C.PAIRWISE_WIDE_MAX on the fp64
+                # CPU oracle
                 p, s_, _ = C.pairwise_tests(cur, base, self.pcfg)
                 o.pvals.copy_(p)
                 o.pstats.copy_(s_)
@@ -441,8 +443,9 @@ class CanaryScorer:
         return o
 
     def _pairwise_wide(self, cur, base, o: CanaryOutputs) -> None:
-        """p-values of windows of any width: the pairwise kernels up to
-        C.PAIRWISE_MAX pooled points, the bucketed / fp64 CPU oracle above."""
+        """p-values of windows of any width: the wave kernels up to
+        C.PAIRWISE_MAX pooled points; above, rows bucketed by their used widths
+        (C.pairwise_tests): K21 up to C.PAIRWISE_WIDE_MAX, the fp64 CPU oracle beyond."""
         if cur.shape[1] + base.shape[1] <= C.PAIRWISE_MAX:
             self._pairwise_into(cur, base, o, combine=False)
         else:

@@ -119,6 +119,8 @@ _SIGS: dict[str, list] = {
     "fm_pvalues_only": [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "fm_pairwise_suff": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p],
     "fm_pairwise_suff_v": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_void_p],
+    # cur ld_c n_cur base ld_b n_base R suff stream (K21: n_cur + n_base <= canary.PAIRWISE_WIDE_MAX)
+    "fm_pairwise_suff_wide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p],
     "fm_hist_stats_capped": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p],
     "fm_pvalues": [c_void_p, c_i64, c_int, c_int, c_float, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                    c_void_p],

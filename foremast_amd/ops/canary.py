@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -56,10 +56,29 @@ def _rows(x: torch.Tensor) -> tuple[int, int]:
     return x.shape[0], x.stride(0)
 
 
-# widest pooled sample (n_cur + n_base) the GPU rank-test kernel sorts in
+# widest pooled sample (n_cur + n_base) the wave rank-test kernel sorts in
 # registers (16 values per lane: a 60-minute canary window of 8 pods per side
-# at a 1-minute step); wider rows take the fp64 CPU oracle
+# at a 1-minute step); wider rows take the workgroup kernel K21 up to
+# PAIRWISE_WIDE_MAX and the fp64 CPU oracle beyond
 PAIRWISE_MAX = 1024
+# widest pooled sample K21 (csrc/kernels/pairwise_wide.hip, kPairwiseWideMax)
+# ranks in LDS, any split between the sides.  Set to PAIRWISE_MAX, the tier is
+# off and every row the wave kernel cannot take goes to the oracle.
+PAIRWISE_WIDE_MAX = 8192
+
+# rows ``pairwise_tests`` has sent down each route since the last reset:
+# "wave" (K4, registers of one wave), "wide" (K21), "oracle" (numpy on the host)
+_ROUTE_ROWS = {"wave": 0, "wide": 0, "oracle": 0}
+
+
+def route_rows() -> dict[str, int]:
+    """Rows of GPU batches per pairwise route so far (a copy)."""
+    return dict(_ROUTE_ROWS)
+
+
+def reset_route_rows() -> None:
+    for k in _ROUTE_ROWS:
+        _ROUTE_ROWS[k] = 0
 
 
 def pairwise_tests(cur: torch.Tensor, base: torch.Tensor, cfg: PairwiseConfig = PairwiseConfig()):
@@ -80,6 +99,7 @@ def pairwise_tests(cur: torch.Tensor, base: torch.Tensor, cfg: PairwiseConfig = 
     n_cur, n_base = cur.shape[1], base.shape[1]
     if n_cur + n_base > PAIRWISE_MAX:
         return _pairwise_bucketed(cur, base, cfg)
+    _ROUTE_ROWS["wave"] += R
     pv = torch.empty((R, N_TESTS), dtype=torch.float32, device=cur.device)
     st = torch.empty_like(pv)
     df = torch.empty((R,), dtype=torch.int8, device=cur.device)
@@ -98,32 +118,84 @@ def used_width(x: torch.Tensor) -> torch.Tensor:
         torch.zeros(x.shape[0], dtype=torch.int64, device=x.device)
 
 
+def pairwise_suff_wide(cur: torch.Tensor, base: torch.Tensor) -> torch.Tensor:
+    """The 14 sufficient statistics of the pairwise tests per row ([R, 14]
+    fp64, ``reference.SUFF_NAMES``) for windows of up to PAIRWISE_WIDE_MAX
+    pooled columns: K21 on GPU tensors, ``reference.pairwise_suff`` on CPU
+    tensors.  ``fm_pvalues`` turns them into p-values."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    if not cur.is_cuda:
+        return torch.from_numpy(ref.pairwise_suff(cur.numpy(), base.numpy()))
+    require_native(cur)
+    n_cur, n_base = cur.shape[1], base.shape[1]
+    check(n_cur + n_base <= PAIRWISE_WIDE_MAX,
+          f"n_cur + n_base = {n_cur + n_base} columns, the workgroup rank kernel takes {PAIRWISE_WIDE_MAX}")
+    suff = torch.empty((R, SUFF), dtype=torch.float64, device=cur.device)
+    LIB.call("fm_pairwise_suff_wide", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, ptr(suff), stream_of(cur))
+    return suff
+
+
+def _pairwise_wide_tests(cur: torch.Tensor, base: torch.Tensor, cfg: PairwiseConfig):
+    """K21 + the p-value kernel on the stream of ``cur`` (CPU tensors: the oracle)."""
+    if not cur.is_cuda:
+        return pairwise_tests(cur, base, cfg)
+    R = cur.shape[0]
+    _ROUTE_ROWS["wide"] += R
+    mask, anyc = cfg.mask_and_combine()
+    suff = pairwise_suff_wide(cur, base)
+    pv = torch.empty((R, N_TESTS), dtype=torch.float32, device=cur.device)
+    st = torch.empty_like(pv)
+    df = torch.empty((R,), dtype=torch.int8, device=cur.device)
+    LIB.call("fm_pvalues", ptr(suff), R, mask, anyc, float(cfg.p_threshold), cfg.min_mann_white, cfg.min_wilcoxon,
+             cfg.min_kruskal, ptr(pv), ptr(st), ptr(df), stream_of(cur))
+    return pv, st, df
+
+
+def _bucket(lc: torch.Tensor, lb: torch.Tensor, among: torch.Tensor, cap: int) -> torch.Tensor:
+    """The rows of ``among`` a kernel that takes ``cap`` pooled columns can run
+    as ONE narrowed batch: those whose used widths fit the cap, and, if the
+    widest current and the widest baseline of them together break it, only
+    those within half the cap per side."""
+    fit = among & ((lc + lb) <= cap)
+    if fit.any() and int(lc[fit].max()) + int(lb[fit].max()) > cap:
+        fit &= (lc <= cap // 2) & (lb <= cap // 2)
+    return fit
+
+
 def _pairwise_bucketed(cur: torch.Tensor, base: torch.Tensor, cfg: PairwiseConfig):
     """A batch padded wider than the register sort (n_cur + n_base > PAIRWISE_MAX):
-    rows are bucketed by their own used widths.  Rows whose samples fit
-    (<= PAIRWISE_MAX / 2 per side, or <= PAIRWISE_MAX together when the whole bucket does) run the
-    GPU kernel on a narrowed copy; only rows that are really wider take the
-    fp64 CPU oracle.  One wide job never moves the whole batch off the GPU
-    and never fails it."""
+    rows are bucketed by their own used widths into three tiers.  Rows whose
+    samples fit the wave kernel (<= PAIRWISE_MAX / 2 per side, or <=
+    PAIRWISE_MAX together when the whole bucket does) run it on a narrowed
+    copy, exactly as they always have; of the rest, rows that fit
+    PAIRWISE_WIDE_MAX by the same rule run K21 + the p-value kernel on a
+    narrowed copy; only rows wider than that take the fp64 CPU oracle.  One
+    wide job never moves the whole batch off the GPU and never fails it
+    (ADVICE r1)."""
     R = cur.shape[0]
     lc, lb = used_width(cur).cpu(), used_width(base).cpu()
-    fit = (lc + lb) <= PAIRWISE_MAX
-    if fit.any() and int(lc[fit].max()) + int(lb[fit].max()) > PAIRWISE_MAX:
-        fit &= (lc <= PAIRWISE_MAX // 2) & (lb <= PAIRWISE_MAX // 2)
+    every = torch.ones((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, every, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~fit, PAIRWISE_WIDE_MAX) if PAIRWISE_WIDE_MAX > PAIRWISE_MAX else ~every
     pv = torch.full((R, N_TESTS), float("nan"), dtype=torch.float32, device=cur.device)
     st = torch.full_like(pv, float("nan"))
     df = torch.zeros((R,), dtype=torch.int8, device=cur.device)
-    k = torch.nonzero(fit).flatten()
-    if len(k):
-        a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
-        kd = k.to(cur.device)
-        p1, s1, d1 = pairwise_tests(cur.index_select(0, kd)[:, :a].contiguous(),
-                                    base.index_select(0, kd)[:, :b].contiguous(), cfg)
-        pv.index_copy_(0, kd, p1)
-        st.index_copy_(0, kd, s1)
-        df.index_copy_(0, kd, d1)
-    w = torch.nonzero(~fit).flatten()
+    for rows, run in ((fit, pairwise_tests), (wide, _pairwise_wide_tests)):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(cur.device)
+            p1, s1, d1 = run(cur.index_select(0, kd)[:, :a].contiguous(),
+                             base.index_select(0, kd)[:, :b].contiguous(), cfg)
+            pv.index_copy_(0, kd, p1)
+            st.index_copy_(0, kd, s1)
+            df.index_copy_(0, kd, d1)
+    w = torch.nonzero(~(fit | wide)).flatten()
     if len(w):
+        if cur.is_cuda:
+            _ROUTE_ROWS["oracle"] += len(w)
         a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
         wd = w.to(cur.device)
         mask, anyc = cfg.mask_and_combine()

@@ -172,6 +172,68 @@ def pairwise_tests(cur, base, mask, combine_any, p_thr, min_mw, min_wil, min_kru
     return P.astype(np.float32), S.astype(np.float32), diff
 
 
+SUFF_NAMES = ("n1", "n2", "nw", "r1", "tie", "D", "rplus", "tiew", "m1", "m2", "q1", "q2", "npos", "nzero")
+
+
+def pairwise_suff(cur, base):
+    """The 14 sufficient statistics per row that the GPU rank-test kernels hand
+    to the p-value kernel ([R, 14] fp64, SUFF_NAMES order), from the same
+    sorts and ranks as ``pairwise_tests``:
+
+    n1, n2 finite samples per side; r1 the rank sum of the current sample and
+    tie = sum(t^3 - t) over the pooled tie runs; D = max |a1 n2 - a2 n1| /
+    (n1 n2) over tie-run ends (0 when a side is empty); m1, m2 the means and
+    q1, q2 the sums of squared deviations (0 for an empty side); over the
+    first min(n_cur, n_base) position pairs with both members finite and d =
+    cur - base formed in fp32: nzero pairs with d == 0, nw the others, npos of
+    them positive, rplus the rank sum of the positive pairs among the |d| and
+    tiew their tie term.  A difference that overflows fp32 counts as the
+    largest magnitude."""
+    c32 = np.asarray(cur, dtype=np.float32)
+    b32 = np.asarray(base, dtype=np.float32)
+    R = c32.shape[0]
+    c = np.where(np.isfinite(c32), c32, np.inf).astype(np.float64)
+    b = np.where(np.isfinite(b32), b32, np.inf).astype(np.float64)
+    pooled = np.concatenate([c, b], axis=1)
+    tags = np.concatenate([np.zeros(c.shape, np.int8), np.ones(b.shape, np.int8)], axis=1)
+    tags = np.where(np.isfinite(pooled), tags, -1)
+    n1 = (tags == 0).sum(1)
+    n2 = (tags == 1).sum(1)
+    out = np.zeros((R, 14), np.float64)
+    out[:, 0], out[:, 1] = n1, n2
+    if pooled.shape[1]:
+        ranks, _, tie, order, is_end = avg_ranks(pooled)
+        out[:, 3] = np.where(tags == 0, ranks, 0.0).sum(1)
+        out[:, 4] = tie
+        ts = np.take_along_axis(tags, order, axis=1)
+        a1 = np.cumsum(ts == 0, axis=1)
+        a2 = np.cumsum(ts == 1, axis=1)
+        dnum = np.where(is_end, np.abs(a1 * n2[:, None] - a2 * n1[:, None]), 0).max(axis=1)
+        both = (n1 > 0) & (n2 > 0)
+        out[:, 5] = np.where(both, dnum / np.maximum(n1 * n2, 1).astype(np.float64), 0.0)
+    for col, x, cnt in ((8, c, n1), (9, b, n2)):
+        fin = np.isfinite(x)
+        m = np.where(fin, x, 0.0).sum(1) / np.maximum(cnt, 1)
+        out[:, col] = m
+        out[:, col + 2] = np.where(fin, (np.where(fin, x, 0.0) - m[:, None]) ** 2, 0.0).sum(1)
+    npair = min(c32.shape[1], b32.shape[1])
+    if npair > 0:
+        pc, pb = c32[:, :npair], b32[:, :npair]
+        ok = np.isfinite(pc) & np.isfinite(pb)
+        with np.errstate(over="ignore", invalid="ignore"):
+            d = np.where(ok, pc - pb, np.float32(0)).astype(np.float64)
+        big = 2.0 * float(np.finfo(np.float32).max)
+        d = np.clip(d, -big, big)                       # an overflowed difference: the largest magnitude
+        nz = ok & (d != 0)
+        rw, _, tiew, _, _ = avg_ranks(np.where(nz, np.abs(d), np.inf))
+        out[:, 2] = nz.sum(1)
+        out[:, 6] = np.where(nz & (d > 0), rw, 0.0).sum(1)
+        out[:, 7] = tiew
+        out[:, 12] = (nz & (d > 0)).sum(1)
+        out[:, 13] = (ok & ~nz).sum(1)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # moving_average_all + decision
 

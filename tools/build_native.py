@@ -3,7 +3,7 @@
 
 * ``foremast_amd/_native/libforemast_hip.so`` — every ``csrc/kernels/*.hip``
   compiled by ``hipcc --offload-arch=gfx950`` (CDNA4 only, no other targets),
-  one unit per kernel family (the canary tick: ``pairwise``, ``hist_stats``,
+  one unit per kernel family (the canary tick: ``pairwise``, ``pairwise_wide``, ``hist_stats``,
   ``tick_front``, ``canary_rows``, ``decide``, ``synth``; device code shared
   between units lives in ``csrc/include/*.h``, and every unit is rebuilt when
   a header changes).
