@@ -1,0 +1,320 @@
+// K22 seasonal scale robust model: K14's per-phase median profile of the last
+// J whole cycles of a row, and about it a sigma per phase instead of one MAD,
+// one 512-thread workgroup per row.
+//
+// The span stays in LDS as the keys of fm_radix_select.h from the one HBM read
+// to the end.  Profile, smoothing, forecast and the residual keys |x -
+// profile[phase]| are K14's stages, copied (as K20 copies them), and the first
+// radix selection gives K14's sigma, sigma0.  Then the raw scale of a phase is
+// the middle of its J residual keys by the same register sorting network
+// (non-negative floats order as their bits, the missing key last); it is
+// smoothed over w phases each side, circular, with fp64 sums, and floored at
+// floor * sigma0 / 1.4826.  The keys are rewritten once more, as the bits of
+// u = r / scale[phase], and a second radix selection finds kappa = 1.4826
+// middle(u): sigma[phase] = kappa * scale[phase].
+//
+// LDS: the profile buffer is the selection's bin array while m <= 2,048, as in
+// K14.  The scale buffer is read while the keys are rewritten for a selection
+// that needs the bins right after, so it sits behind the keys always, and a
+// longer period puts the profile behind it: (J + 2) m <= kRobustLdsKeys
+// (ops/misc.py seasonal_cycles) holds the span and both.  At 7 x 1,440 a
+// workgroup takes 54,432 B against K14's 48,672 B: by bytes three still fit
+// the 160 KiB of a CU, with 544 to spare, but the timings on either side of
+// that edge say only two are resident (docs/PERF.md).  The contract is foremast_amd/ops/misc.py ref_seasonal_scale_robust;
+// forecast, profile and sigma0 are K14's bit for bit, and given the profile the
+// scale is exact up to kappa, which is exact where the middle of u is > 0.
+#include "fm_common.h"
+#include "fm_radix_select.h"
+
+using namespace fm;
+
+namespace {
+
+constexpr int kScaleThreads = 512;
+constexpr int kMaxCycles = 16;                   // foremast_amd/ops/misc.py SEASONAL_MAX_CYCLES mirrors it
+constexpr int kMaxPeriod = kRobustLdsKeys / 4;   // (J + 2) m <= kRobustLdsKeys with J >= 2
+static_assert(sizeof(SelectScratch<kScaleThreads>) + row_key_bytes(kRobustLdsKeys) + sizeof(uint4) <= kLaunchLds,
+              "the longest span, a profile and a scale behind it fit a launch");
+
+// compare-exchange: the smaller key first
+__device__ __forceinline__ void cex(unsigned& a, unsigned& b) {
+  const unsigned lo = a < b ? a : b, hi = a < b ? b : a;
+  a = lo;
+  b = hi;
+}
+
+// The J keys col[0], col[m], ... of a phase sorted in registers, the missing
+// key last: c = how many are finite, klo / kup their lower and upper middle
+// (the missing key when c == 0).
+__device__ __forceinline__ int phase_middles(const unsigned* col, int m, int J, unsigned& klo, unsigned& kup) {
+  unsigned s[kMaxCycles];
+  int c = 0;
+#pragma unroll
+  for (int j = 0; j < kMaxCycles; ++j) {
+    s[j] = j < J ? col[j * m] : kMissing;
+    c += s[j] != kMissing;
+  }
+#pragma unroll
+  for (int r = 0; r < kMaxCycles; ++r) {
+    if (r < J) {                                             // J rounds sort J keys; the padding is in place
+#pragma unroll
+      for (int i = r & 1; i + 1 < kMaxCycles; i += 2) cex(s[i], s[i + 1]);
+    }
+  }
+  const int il = (c - 1) >> 1, iu = c >> 1;
+  klo = kMissing;
+  kup = kMissing;
+#pragma unroll
+  for (int j = 0; j < kMaxCycles; ++j) {
+    klo = j == il ? s[j] : klo;
+    kup = j == iu ? s[j] : kup;
+  }
+  return c;
+}
+
+// buf[0..m) -> for each of this thread's phases the mean of the finite values
+// within k phases, circular, summed from -k up and divided in fp64; NaN when
+// none is finite.  The caller puts a barrier between this and a write of buf.
+template <int NT, int NP>
+__device__ __forceinline__ void smooth_phases(const float* buf, int m, int k, float (&sm)[NP]) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < NP; ++it) {
+    const int ph = tid + it * NT;
+    sm[it] = quiet_nan();
+    if (ph < m) {
+      double sum = 0.0;
+      int cnt = 0;
+      int q = ph - k;
+      if (q < 0) q += m;
+      for (int d = -k; d <= k; ++d) {
+        const float v = buf[q];
+        if (v == v) {
+          sum += (double)v;
+          ++cnt;
+        }
+        if (++q == m) q = 0;
+      }
+      if (cnt != 0) sm[it] = (float)(sum / (double)cnt);
+    }
+  }
+}
+
+// out[row, h] = buf[h mod m] for h < H
+template <int NT>
+__device__ __forceinline__ void write_wrapped(const float* buf, int m, int H, float* out) {
+  const int tid = threadIdx.x;
+  const int stepm = NT % m;
+  int ph = tid % m;
+  for (int h = tid; h < H; h += NT) {
+    out[h] = buf[ph];
+    ph += stepm;
+    if (ph >= m) ph -= m;
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* __restrict__ hist, int64_t ld, int T,
+                                                                   int m, int J, int k, int w, float floor_share,
+                                                                   int H, float* __restrict__ forecast,
+                                                                   float* __restrict__ sigma_h, int64_t ldf,
+                                                                   float* __restrict__ stats /*[R,3]*/,
+                                                                   float* __restrict__ profile /*[R,m] or null*/,
+                                                                   float* __restrict__ scale /*[R,m] or null*/) {
+  constexpr int kPhases = (kMaxPeriod + NT - 1) / NT;        // most phases a thread takes
+  extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
+  __shared__ SelectScratch<NT> s_sc;
+  const int tid = threadIdx.x;
+  const int64_t row = blockIdx.x;
+  const int N = J * m;                                       // span length
+  const float* p = hist + row * ld + (T - N);
+  const int a = row_word(p);                                 // LDS word of key 0
+  const int nq = row_quads(a, N);
+  unsigned* kw = reinterpret_cast<unsigned*>(s_keys);
+  float* scl = reinterpret_cast<float*>(kw + 4 * nq);        // [m]: raw scale, floored scale, sigma per phase
+  float* prof = m <= kBins ? reinterpret_cast<float*>(s_sc.bins) : scl + m;   // [m]: raw, then smoothed
+  const float qnan = quiet_nan();
+
+  // a row without a sigma per phase: v in every phase
+  auto flat = [&](float v, float sigma0, float n) {
+    for (int h = tid; h < H; h += NT) sigma_h[row * ldf + h] = v;
+    if (scale != nullptr)
+      for (int ph = tid; ph < m; ph += NT) scale[row * (int64_t)m + ph] = v;
+    if (tid == 0) {
+      stats[row * 3 + 0] = sigma0;
+      stats[row * 3 + 1] = n;
+      stats[row * 3 + 2] = qnan;
+    }
+  };
+
+  // ---- the span -> keys in place; finite count (the key range is not needed)
+  int n = 0;
+  auto count = [&](unsigned key) { n += key != kMissing; };
+  load_row_keys<NT>(p, N, a, s_keys, count);
+  n = uniform(block_sum<NT>(n, s_sc.redi));                  // (barriers: keys visible)
+  if (n == 0) {
+    for (int h = tid; h < H; h += NT) forecast[row * ldf + h] = qnan;
+    if (profile != nullptr)
+      for (int ph = tid; ph < m; ph += NT) profile[row * (int64_t)m + ph] = qnan;
+    flat(qnan, qnan, 0.f);
+    return;
+  }
+
+  // ---- raw profile: per-phase median of the finite samples
+  for (int ph = tid; ph < m; ph += NT) {
+    unsigned klo, kup;
+    const int c = phase_middles(kw + a + ph, m, J, klo, kup);
+    prof[ph] = c == 0 ? qnan : 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
+  }
+  __syncthreads();
+
+  // ---- smoothing in place: mean of the finite raw values within k phases, circular
+  {
+    float sm[kPhases];
+    smooth_phases<NT>(prof, m, k, sm);
+    __syncthreads();                                         // every raw value read
+#pragma unroll
+    for (int it = 0; it < kPhases; ++it) {
+      const int ph = tid + it * NT;
+      if (ph < m) {
+        prof[ph] = sm[it];
+        if (profile != nullptr) profile[row * (int64_t)m + ph] = sm[it];
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- forecast: the profile from phase 0 on, wrapped
+  write_wrapped<NT>(prof, m, H, forecast + row * ldf);
+
+  // word wd holds span index wd - a: its phase, carried along a thread's quads instead of divided out
+  const int stepm = (4 * NT) % m;
+  int ph_first = (4 * tid - a) % m;                          // (the padding in front of the span: a remainder below zero)
+  if (ph_first < 0) ph_first += m;
+
+  // ---- residuals about the profile: keys, fp64 sum, range
+  DevTally dev;
+  {
+    int ph0 = ph_first;
+    for (int q = tid; q < nq; q += NT) {
+      const uint4 v = s_keys[q];
+      unsigned e[4] = {v.x, v.y, v.z, v.w};
+      int ph = ph0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (e[j] != kMissing) {
+          e[j] = dev_key(e[j], prof[ph]);
+          dev(e[j]);
+        }
+        if (++ph == m) ph = 0;
+      }
+      s_keys[q] = make_uint4(e[0], e[1], e[2], e[3]);
+      ph0 += stepm;
+      if (ph0 >= m) ph0 -= m;
+    }
+  }
+  const double sum = uniform(block_sum<NT>(dev.sum, s_sc.redd));   // (barriers: the last read of the profile is behind)
+  s_sc.clear_bins();                                         // (made visible by the barriers of mad_sigma's range)
+
+  // ---- sigma0, K14's sigma: the padding words hold the missing key, so the span is swept as a whole row
+  const LdsRow<NT> rk{s_keys, nq};
+  const float sigma0 = mad_sigma(rk, (unsigned)n, sum, dev.range, &s_sc);
+  if (sigma0 == 0.f) {                                       // a perfectly periodic span (uniform: every thread read the same middles)
+    flat(0.f, 0.f, (float)n);
+    return;
+  }
+
+  // ---- raw scale: per-phase middle of the residuals (the keys are their bits)
+  for (int ph = tid; ph < m; ph += NT) {
+    unsigned klo, kup;
+    const int c = phase_middles(kw + a + ph, m, J, klo, kup);
+    scl[ph] = c == 0 ? qnan : 0.5f * __uint_as_float(klo) + 0.5f * __uint_as_float(kup);
+  }
+  __syncthreads();
+
+  // ---- smoothing in place over w phases each side, then the floor
+  const float f = __fmul_rn(floor_share, __fdiv_rn(sigma0, 1.4826f));
+  {
+    float sm[kPhases];
+    smooth_phases<NT>(scl, m, w, sm);
+    __syncthreads();                                         // every raw value read
+#pragma unroll
+    for (int it = 0; it < kPhases; ++it) {
+      const int ph = tid + it * NT;
+      if (ph < m) scl[ph] = sm[it] == sm[it] ? fmaxf(sm[it], f) : f;
+    }
+    __syncthreads();
+  }
+
+  // ---- the residuals in units of their phase's scale: keys, fp64 sum, range
+  DevTally rel;
+  {
+    int ph0 = ph_first;
+    for (int q = tid; q < nq; q += NT) {
+      const uint4 v = s_keys[q];
+      unsigned e[4] = {v.x, v.y, v.z, v.w};
+      int ph = ph0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (e[j] != kMissing) {
+          e[j] = __float_as_uint(__fdiv_rn(__uint_as_float(e[j]), scl[ph]));
+          rel(e[j]);
+        }
+        if (++ph == m) ph = 0;
+      }
+      s_keys[q] = make_uint4(e[0], e[1], e[2], e[3]);
+      ph0 += stepm;
+      if (ph0 >= m) ph0 -= m;
+    }
+  }
+  const double sum_u = uniform(block_sum<NT>(rel.sum, s_sc.redd));   // (barriers: keys visible; the bins are still zero)
+
+  // ---- kappa: sigma's rule over u
+  const float kappa = mad_sigma(rk, (unsigned)n, sum_u, rel.range, &s_sc);
+
+  // ---- sigma per phase, in place (a thread rewrites the phases it reads), and wrapped like the forecast
+  for (int ph = tid; ph < m; ph += NT) {
+    const float s = __fmul_rn(kappa, scl[ph]);
+    scl[ph] = s;
+    if (scale != nullptr) scale[row * (int64_t)m + ph] = s;
+  }
+  __syncthreads();
+  write_wrapped<NT>(scl, m, H, sigma_h + row * ldf);
+  if (tid == 0) {
+    stats[row * 3 + 0] = sigma0;
+    stats[row * 3 + 1] = (float)n;
+    stats[row * 3 + 2] = kappa;
+  }
+}
+
+}  // namespace
+
+// Per row of hist[r, :T], over its last J * m samples (phase = position in
+// that span mod m): fm_seasonal_robust's smoothed per-phase median profile and
+// forecast[r, h] = profile[h mod m]; the per-phase middle of the residuals
+// about the profile, smoothed over w phases each side, floored at floor *
+// sigma0 / 1.4826 and scaled by kappa (1.4826 times the middle of the
+// residuals over that scale): sigma_h[r, h] = scale[h mod m] for h < H
+// (forecast and sigma_h share the leading dimension ldf); stats[r] = (sigma0 =
+// fm_seasonal_robust's sigma, finite count of the span, kappa); the profile and
+// the scale [R, m] when their pointers are not null.  k and w = half widths of
+// the two smoothing windows.  hist and ld need 4-byte alignment only.  Nothing
+// is launched unless 2 <= J <= 16, J * m <= T, (J + 2) * m fits the LDS budget
+// of K13, 2 k + 1 <= m, 0 <= w, 2 w + 1 <= m and floor > 0.
+FM_API int fm_seasonal_scale_robust(const float* hist, int64_t ld, int T, int64_t R, int m, int J, int k, int w,
+                                    float floor, int H, float* forecast, float* sigma_h, int64_t ldf, float* stats,
+                                    float* profile, float* scale, hipStream_t stream) {
+  if (m < 1 || J < 2 || J > kMaxCycles || (int64_t)(J + 2) * m > kRobustLdsKeys || (int64_t)J * m > T || k < 0 ||
+      2 * (int64_t)k + 1 > m || H < 0 || R > 0x7FFFFFFF || (((uintptr_t)hist) & 3) != 0)
+    return (int)hipErrorInvalidValue;
+  if (w < 0 || 2 * (int64_t)w + 1 > m || !(floor > 0.f)) return (int)hipErrorInvalidValue;
+  if (R <= 0) return 0;
+  // keys: the span plus up to 3 words in front, in whole quads; behind them
+  // the scale, and the profile when the bin array is too short for it
+  const size_t lds = row_key_bytes(J * m) + (size_t)m * (m > kBins ? 2 : 1) * sizeof(float);
+  if (lds + sizeof(SelectScratch<kScaleThreads>) > kLaunchLds) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL((seasonal_scale_robust_kernel<kScaleThreads>), dim3((unsigned)R), dim3(kScaleThreads), lds,
+                     stream, hist, ld, T, m, J, k, w, floor, H, forecast, sigma_h, ldf, stats, profile, scale);
+  FM_LAUNCH_CHECK();
+  return 0;
+}

@@ -81,6 +81,10 @@ class BrainConfig:
     # and the half width of the profile's smoothing window in phases
     seasonal_period: int = 0                 # SEASONAL_PERIOD
     seasonal_smooth: int = 5                 # SEASONAL_SMOOTH
+    # seasonal_scale_robust: the half width of the smoothing window of the per-phase scale in phases, and
+    # the floor of that scale as a share of the pooled MAD (clamped to >= 1e-3)
+    seasonal_scale_smooth: int = 30          # SEASONAL_SCALE_SMOOTH
+    seasonal_scale_floor: float = 0.1        # SEASONAL_SCALE_FLOOR
     # shift_robust: samples per block (0 = one day at the brain's step), the score a level shift must
     # exceed (sigma-like units) and the whole blocks a new level must have held to count as normal
     shift_block: int = 0                     # SHIFT_BLOCK
@@ -218,6 +222,8 @@ class BrainConfig:
         c.multivariate_reject = _f(env, "ML_MULTIVARIATE_REJECT", c.multivariate_reject)
         c.seasonal_period = _i(env, "SEASONAL_PERIOD", c.seasonal_period)
         c.seasonal_smooth = _i(env, "SEASONAL_SMOOTH", c.seasonal_smooth)
+        c.seasonal_scale_smooth = _i(env, "SEASONAL_SCALE_SMOOTH", c.seasonal_scale_smooth)
+        c.seasonal_scale_floor = max(1e-3, _f(env, "SEASONAL_SCALE_FLOOR", c.seasonal_scale_floor))
         c.shift_block = _i(env, "SHIFT_BLOCK", c.shift_block)
         c.shift_threshold = _f(env, "SHIFT_THRESHOLD", c.shift_threshold)
         c.shift_min_blocks = max(1, _i(env, "SHIFT_MIN_BLOCKS", c.shift_min_blocks))

@@ -345,10 +345,20 @@ class Brain(BrainStateMixin):
         return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth,
                 "trend_min_blocks": self.cfg.trend_min_blocks}
 
+    def _seasonal_scale_args(self, algorithm: str) -> dict:
+        """``period`` / ``smooth`` / ``scale_smooth`` / ``scale_floor`` of a
+        zoo call: SEASONAL_PERIOD, SEASONAL_SMOOTH, SEASONAL_SCALE_SMOOTH and
+        SEASONAL_SCALE_FLOOR for ``seasonal_scale_robust``, nothing for any
+        other model."""
+        if zoo.canonical(algorithm) != "seasonal_scale_robust":
+            return {}
+        return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth,
+                "scale_smooth": self.cfg.seasonal_scale_smooth, "scale_floor": max(1e-3, self.cfg.seasonal_scale_floor)}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
-                **self._seasonal_trend_args(algorithm)}
+                **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -882,7 +892,8 @@ class Brain(BrainStateMixin):
                                  cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_args(self.cfg.hpa_forecast_algorithm),
                                  **self._trend_args(self.cfg.hpa_forecast_algorithm),
-                                 **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._seasonal_scale_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

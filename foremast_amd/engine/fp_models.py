@@ -630,6 +630,10 @@ class ModelsMixin:
             # the span is seasonal_robust's: no column before it is gathered
             kw = b._seasonal_trend_args(algo)
             return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
+        elif algo == "seasonal_scale_robust":
+            # the span is seasonal_robust's: no column before it is gathered; sigma comes back [R, H]
+            kw = b._seasonal_scale_args(algo)
+            return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
         elif algo == "trend_robust":
             # only the columns the kernel holds are gathered
             return zoo.forecast(algo, lazy.materialize(zoo.trend_start(sub.T)), sub.T, H, **b._trend_args(algo))

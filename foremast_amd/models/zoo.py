@@ -25,6 +25,7 @@ seasonal_robust                 per-phase median profile + residual MAD K14 + ba
 shift_robust                    median / MAD behind the last shift      K15 + band decide
 trend_robust                    repeated-median line + residual MAD     K16 + band decide
 seasonal_trend_robust           repeated-median line + phase profile    K20 + band decide
+seasonal_scale_robust           phase profile + a sigma per phase       K22 + band decide (per point)
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -53,7 +54,7 @@ from ..ops import smoothing as SM
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
-              "trend_robust", "robust_multivariate", "seasonal_trend_robust")
+              "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -75,6 +76,8 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "repeated_median": "trend_robust",
            "seasonal_trend_robust": "seasonal_trend_robust", "trend_seasonal_robust": "seasonal_trend_robust",
            "robust_seasonal_trend": "seasonal_trend_robust", "robust_stl": "seasonal_trend_robust",
+           "seasonal_scale_robust": "seasonal_scale_robust", "seasonal_hetero_robust": "seasonal_scale_robust",
+           "robust_seasonal_scale": "seasonal_scale_robust", "seasonal_mad_profile": "seasonal_scale_robust",
            "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
            "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
@@ -142,7 +145,7 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
            groups=None, mvn_threshold: float | None = None, smooth: int = 5, block: int | None = None,
            shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
-           mvn_reject: float = 3.5) -> RowDecision:
+           mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -154,7 +157,9 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     too and fits a slope from ``trend_min_blocks`` non-empty ones, and
     ``seasonal_trend_robust`` from as many non-empty cycles of ``period``.
     ``mvn_reject`` is ``robust_multivariate``'s rejection limit in MAD-sigmas
-    (<= 0: nothing is rejected)."""
+    (<= 0: nothing is rejected).  ``scale_smooth`` and ``scale_floor`` are
+    ``seasonal_scale_robust``'s: the half width of the window that smooths
+    its per-phase scale, and that scale's floor as a share of the pooled MAD."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -211,6 +216,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "seasonal_scale_robust":
+        # gated on the span's finite count, as seasonal_robust; sigma is [R, H] (1-D from the fallback)
+        fc, sigma, nfin = _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, scale_floor)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
     fc, sigma = forecast(algo, hist, T, H, period=period, lstm_model=lstm_model, cache=cache, smooth=smooth)
     return band(fc, sigma, horizon, cur, M, tables, diff, _valid(hist, T, cur, tables.min_hist))
 
@@ -219,12 +230,18 @@ def band(fc: torch.Tensor, sigma: torch.Tensor, horizon: torch.Tensor, cur: torc
          diff: torch.Tensor | None, valid: torch.Tensor) -> RowDecision:
     """Forecast -> per-point bands and decisions: each current point is
     judged against the forecast at its own horizon, centre +/- thr * sigma.
-    Rows without enough history (``valid`` bit 0) flag nothing."""
+    ``sigma`` is [R], or [R, H] with a sigma per forecast step, which is
+    gathered at the horizon like the centre.  Rows without enough history
+    (``valid`` bit 0) flag nothing."""
     H = fc.shape[1]
     idx = (horizon.clamp(1, H) - 1).to(fc.device)
     center = torch.gather(fc, 1, idx).contiguous()
-    up, lo, flags, cnt, sc = SM.band_decide(cur, center, sigma.contiguous(), M, tables.thr, tables.bound,
-                                            tables.minlb, diff, tables.pair_factor)
+    if sigma.dim() == 2:
+        up, lo, flags, cnt, sc = SM.band_decide_pp(cur, center, torch.gather(sigma, 1, idx).contiguous(), M,
+                                                   tables.thr, tables.bound, tables.minlb, diff, tables.pair_factor)
+    else:
+        up, lo, flags, cnt, sc = SM.band_decide(cur, center, sigma.contiguous(), M, tables.thr, tables.bound,
+                                                tables.minlb, diff, tables.pair_factor)
     has = (valid & 1).bool().to(cnt.device)
     cnt = torch.where(has, cnt, torch.zeros_like(cnt))
     flags = torch.where(has[:, None], flags, torch.zeros_like(flags))
@@ -279,7 +296,8 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
-FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust")
+FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust",
+                                 "seasonal_scale_robust")
 
 
 def seasonal_start(T: int, period: int | None) -> int:
@@ -345,12 +363,31 @@ def _seasonal_trend_robust(hist, T, H, period, smooth, min_blocks):
     return center[:, None].expand(-1, H), sigma, nfin
 
 
+def _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, floor):
+    """``seasonal_robust``'s per-phase median profile with a sigma per phase:
+    the middle of each phase's residuals, smoothed over neighbouring phases,
+    floored at a share of the pooled MAD and calibrated to a sigma, K22 ->
+    (forecast [R, H], sigma [R, H], finite count [R]).  The span, ``period``
+    None and the fallback are ``seasonal_robust``'s: a history shorter than
+    two periods, or a period too long for the kernel's budget, gets the
+    whole-history median with K13's one sigma, [R]."""
+    from ..ops import misc as MI
+    m = int(period or _detect_period(hist, T))
+    if MI.seasonal_cycles(T, m) >= 2:
+        fc, sigma_h, nfin = MI.seasonal_scale_robust(hist, T, m, H, smooth, int(scale_smooth), float(floor))[:3]
+        return fc, sigma_h, nfin
+    center, sigma, nfin = MI.robust_stats(hist, T)
+    return center[:, None].expand(-1, H), sigma, nfin
+
+
 def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | None = None,
              lstm_model=None, cache: CacheContext | None = None,
              smooth: int = 5, block: int | None = None,
-             trend_min_blocks: int = 3) -> tuple[torch.Tensor, torch.Tensor]:
+             trend_min_blocks: int = 3, scale_smooth: int = 30,
+             scale_floor: float = 0.1) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
-    forecasting model -> (forecast [R, H], residual sigma [R]).  Used by the
+    forecasting model -> (forecast [R, H], residual sigma [R]; sigma [R, H],
+    one per step, from ``seasonal_scale_robust`` unless it fell back).  Used by the
     band decision and, for HPA jobs, to publish the load forecast a cluster
     autoscaler can act on ahead of time (README.md:58-59 "ClusterAutoScaler
     prediction"; BASELINE config 4)."""
@@ -381,6 +418,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return _trend_robust(hist, T, H, block or 1440, trend_min_blocks)[:2]
     if algo == "seasonal_trend_robust":
         return _seasonal_trend_robust(hist, T, H, period, smooth, trend_min_blocks)[:2]
+    if algo == "seasonal_scale_robust":
+        return _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, scale_floor)[:2]
     raise ValueError(f"{algorithm!r} is not a forecasting model ({', '.join(FORECASTERS)})")
 
 

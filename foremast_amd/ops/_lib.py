@@ -106,6 +106,13 @@ _SIGS: dict[str, list] = {
     # hist ld T R m J k min_blocks H forecast ldf stats profile stream
     "fm_seasonal_trend_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_i64,
                                  c_void_p, c_void_p, c_void_p],
+    # hist ld T R m J k w floor H forecast sigma_h ldf stats profile scale stream
+    "fm_seasonal_scale_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p,
+                                 c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+    # cur ld_c n center ld_f sigma ld_s R M thr bound minlb diff pair_factor upper lower flags NW count score stream
+    "fm_band_decide_pp": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                          c_void_p],
     "fm_hpa_score": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.c_double, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p],

@@ -1,8 +1,9 @@
 """K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
-K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K8 HPA score, K9 downstream
-impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip, csrc/kernels/mvn_robust.hip,
-csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip, csrc/kernels/level_shift.hip,
-csrc/kernels/trend_robust.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
+K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K22 seasonal scale robust
+model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
+csrc/kernels/mvn_robust.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
+csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip, csrc/kernels/seasonal_scale_robust.hip,
+csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -803,6 +804,115 @@ def seasonal_trend_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: in
                  ptr(fc), max(H, 1), ptr(stats), ptr(prof), stream_of(hist))
     out = (fc, stats[:, 0], stats[:, 1].to(torch.int32), stats[:, 2])
     return out + (prof,) if want_profile else out
+
+
+# --------------------------------------------------------------------------- K22
+def scale_halfwidth(m: int, scale_smooth: int = 30) -> int:
+    """Half width w of the window that smooths the per-phase scale:
+    ``scale_smooth`` phases each side, but the window stays about a quarter of
+    the period (``m // 8`` each side), so ``2 w + 1 <= m`` for every ``m``."""
+    return max(0, min(int(scale_smooth), int(m) // 8))
+
+
+def ref_seasonal_scale_robust(hist, T: int, m: int, H: int, smooth: int = 5, scale_smooth: int = 30,
+                              floor: float = 0.1):
+    """:func:`ref_seasonal_robust` with a sigma per phase -> (forecast [R, H]
+    f32, sigma_h [R, H] f32, n [R] int32, sigma0 [R] f32, kappa [R] f32,
+    profile [R, m] f32, scale [R, m] f32), fp32 unless it says otherwise.
+
+    ``forecast``, ``sigma0`` (the one sigma of that model), ``n`` and
+    ``profile`` are ``ref_seasonal_robust(hist, T, m, H, smooth)``'s, and so
+    are the span and the phases.  With ``r_i = |x_i - profile[phase_i]|`` of
+    the finite samples, ``raw_s[p]`` is K13's middle rule over the ``r`` of
+    phase ``p`` (NaN when it has none) and ``g[p]`` the mean of the finite
+    ``raw_s[(p + d) % m]``, ``d = -w..w`` (:func:`scale_halfwidth`), summed in
+    that order and divided in fp64, rounded once.  The floor is ``f =
+    fp32(floor) * (sigma0 / 1.4826)``, a share of the pooled MAD: ``g'[p] =
+    max(g[p], f)``, and ``f`` where ``g[p]`` is NaN.  ``u_i = r_i /
+    g'[phase_i]``; ``kappa = 1.4826 * middle(u)`` over the ``n`` finite
+    samples, or ``1.2533 * mean(u)`` (fp64, rounded once) when that middle is
+    0: the factor that turns the median of the ``J`` half-normal values of a
+    phase into a sigma.  ``scale[p] = kappa * g'[p]`` and ``sigma_h[:, h - 1]
+    = scale[(h - 1) % m]``, wrapped like the forecast.  A row with ``sigma0 ==
+    0`` (a perfectly periodic span) has ``scale == 0`` and ``kappa`` NaN;
+    ``n == 0`` gives NaN everywhere."""
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    T, m, H = int(T), int(m), int(H)
+    check(float(floor) > 0, "floor must be > 0")
+    forecast, sigma0, n, profile = ref_seasonal_robust(x, T, m, H, smooth)
+    J = seasonal_cycles(T, m)
+    w = scale_halfwidth(m, scale_smooth)
+    span = x[:, T - J * m:T]
+    fin = np.isfinite(span)
+    half, inf, nan = np.float32(0.5), np.float32(np.inf), np.float32(np.nan)
+
+    def middle(v, ok, cnt, axis):                   # missing samples sort last as +inf
+        s = np.sort(np.where(ok, v, inf), axis=axis)
+        lo = np.expand_dims((np.maximum(cnt, 1) - 1) // 2, axis)
+        up = np.expand_dims(np.maximum(cnt, 1) // 2, axis)
+        return (half * np.take_along_axis(s, lo, axis) + half * np.take_along_axis(s, up, axis)).squeeze(axis)
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        r = np.abs(span - np.tile(profile, (1, J))).astype(np.float32)
+        fin3 = fin.reshape(R, J, m)
+        c = fin3.sum(1)
+        raw = np.where(c > 0, middle(r.reshape(R, J, m), fin3, c, 1), nan).astype(np.float32)
+        tot = np.zeros((R, m), np.float64)
+        cnt = np.zeros((R, m), np.int64)
+        for d in range(-w, w + 1):
+            nb = np.roll(raw, -d, axis=1)           # nb[:, p] = raw[:, (p + d) % m]
+            ok = np.isfinite(nb)
+            tot += np.where(ok, nb, 0).astype(np.float64)
+            cnt += ok
+        g = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan).astype(np.float32)
+        f = (np.float32(floor) * (sigma0 / np.float32(1.4826)).astype(np.float32)).astype(np.float32)
+        gp = np.where(np.isfinite(g), np.maximum(g, f[:, None]), f[:, None]).astype(np.float32)
+        u = (r / np.tile(gp, (1, J))).astype(np.float32)
+        mid = middle(u, fin, n, 1)
+        mean_u = (np.where(fin, u, 0).astype(np.float64).sum(1) / np.maximum(n, 1)).astype(np.float32)
+        kappa = np.where(mid > 0, np.float32(1.4826) * mid, np.float32(1.2533) * mean_u).astype(np.float32)
+        scale = (kappa[:, None] * gp).astype(np.float32)
+    flat = sigma0 == 0
+    kappa[flat | (n == 0)] = nan
+    scale[flat] = 0
+    scale[n == 0] = nan
+    sigma_h = np.ascontiguousarray(scale[:, np.arange(H) % m])
+    return forecast, sigma_h, n, sigma0, kappa, profile, scale
+
+
+def seasonal_scale_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: int = 5, scale_smooth: int = 30,
+                          floor: float = 0.1, want_profile: bool = False):
+    """K22: (forecast [R, H], sigma_h [R, H], n [R] int32, sigma0 [R], kappa
+    [R]) of :func:`ref_seasonal_scale_robust` over ``hist[:, :T]``, and the
+    profile and the scale [R, m] behind them when ``want_profile``.  ``hist``
+    may be any column view with unit column stride: rows need 4-byte alignment
+    only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, m, H = int(T), int(m), int(H)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_scale_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    check(H >= 0, "H must be >= 0")
+    check(float(floor) > 0, "floor must be > 0")
+    if not hist.is_cuda:
+        out = tuple(torch.from_numpy(a) for a in ref_seasonal_scale_robust(hist.numpy(), T, m, H, smooth, scale_smooth,
+                                                                          floor))
+        return out if want_profile else out[:5]
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    fc = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    sh = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    stats = torch.empty((R, 3), dtype=torch.float32, device=hist.device)
+    prof = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    scale = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    if R:
+        LIB.call("fm_seasonal_scale_robust", ptr(hist), hist.stride(0), T, R, m, J, seasonal_halfwidth(m, smooth),
+                 scale_halfwidth(m, scale_smooth), float(floor), H, ptr(fc), ptr(sh), max(H, 1), ptr(stats), ptr(prof),
+                 ptr(scale), stream_of(hist))
+    out = (fc, sh, stats[:, 1].to(torch.int32), stats[:, 0], stats[:, 2])
+    return out + (prof, scale) if want_profile else out
 
 
 # --------------------------------------------------------------------------- K8

@@ -481,3 +481,62 @@ def ref_band_decide(cur, center, sigma, M, thr, bound, minlb, diff, pair_factor)
     t = torch.from_numpy
     return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
             t(flag.sum(1).astype(np.int32)), t(score))
+
+
+def band_decide_pp(cur: torch.Tensor, center: torch.Tensor, sigma: torch.Tensor, M: int, thr, bound, minlb,
+                   diff: torch.Tensor | None = None, pair_factor: float = 0.8):
+    """:func:`band_decide` with a sigma per point, ``sigma [R, n]`` (any row
+    stride): point ``i`` of a row is judged against centre +/- thr *
+    sigma[:, i] and scores in units of its own sigma.  A NaN sigma flags
+    nothing; rows whose sigmas are all equal get :func:`band_decide`'s
+    outputs."""
+    R, n = cur.shape
+    check(sigma.dim() == 2 and tuple(sigma.shape) == (R, n) and sigma.dtype == torch.float32,
+          "sigma must be fp32 [R, n], one per current point")
+    NW = max(1, (n + 63) // 64)
+    if not cur.is_cuda:
+        return ref_band_decide_pp(cur.numpy(), center.numpy(), sigma.numpy(), M, thr.numpy(), bound.numpy(),
+                                  minlb.numpy(), None if diff is None else diff.numpy(), pair_factor)
+    require_native(cur)
+    if n > 1 and sigma.stride(1) != 1:
+        sigma = sigma.contiguous()
+    d = cur.device
+    up = torch.empty((R, n), dtype=torch.float32, device=d)
+    lo = torch.empty_like(up)
+    flags = torch.empty((R, NW), dtype=torch.int64, device=d)
+    cnt = torch.empty((R,), dtype=torch.int32, device=d)
+    sc = torch.empty((R,), dtype=torch.float32, device=d)
+    LIB.call("fm_band_decide_pp", ptr(cur), cur.stride(0), n, ptr(center), center.stride(0), ptr(sigma),
+             sigma.stride(0), R, M, ptr(thr), ptr(bound), ptr(minlb), ptr(diff), float(pair_factor), ptr(up), ptr(lo),
+             ptr(flags), NW, ptr(cnt), ptr(sc), stream_of(cur))
+    return up, lo, flags, cnt, sc
+
+
+def ref_band_decide_pp(cur, center, sigma, M, thr, bound, minlb, diff, pair_factor):
+    """:func:`ref_band_decide` with ``sigma [R, n]``: every point has its own
+    band and scores ``(x - upper) / sigma`` or ``(lower - x) / sigma`` of its
+    own sigma (1e30 where that is not > 0)."""
+    R, n = cur.shape
+    m = np.arange(R) % M
+    th = thr[m].astype(np.float32)
+    if diff is not None:
+        th = np.where(diff != 0, th * np.float32(pair_factor), th)
+    sigma = np.asarray(sigma, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        up = center + th[:, None] * sigma
+        lo = np.maximum(center - th[:, None] * sigma, minlb[m][:, None])
+    bd = bound[m]
+    ok = np.isfinite(cur) & np.isfinite(center)
+    hi = ((bd & 1) != 0)[:, None] & (cur > up) & ok
+    lw = ((bd & 2) != 0)[:, None] & (cur < lo) & ok
+    flag = hi | lw
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z = np.where(sigma > 0, np.where(hi, cur - up, lo - cur) / np.where(sigma > 0, sigma, 1), 1e30)
+    score = np.where(flag, z, 0).max(1, initial=0).astype(np.float32)
+    NW = max(1, (n + 63) // 64)
+    padded = np.zeros((R, NW * 64), bool)
+    padded[:, :n] = flag
+    words = np.packbits(padded.reshape(R, NW, 64), axis=2, bitorder="little").view(np.uint64).reshape(R, NW)
+    t = torch.from_numpy
+    return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
+            t(flag.sum(1).astype(np.int32)), t(score))
