@@ -93,6 +93,14 @@ class BrainConfig:
     # trend_robust: samples per block (0 = one day at the brain's step) and the non-empty blocks a slope needs
     trend_block: int = 0                     # TREND_BLOCK
     trend_min_blocks: int = 3                # TREND_MIN_BLOCKS
+    # auto_robust: held-out samples of the back-test (0 = one seasonal period), the nats a more elaborate
+    # model must win by, the cap on a point's standardised miss, the seconds of new history after which a
+    # row is selected again, and the candidate models (comma list, "" = all six; checked when the brain starts)
+    auto_holdout: int = 0                    # AUTO_HOLDOUT
+    auto_margin: float = 0.05                # AUTO_MARGIN
+    auto_zcap: float = 8.0                   # AUTO_ZCAP
+    auto_reselect: float = 86400.0           # AUTO_RESELECT
+    auto_candidates: str = ""                # AUTO_CANDIDATES
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -229,6 +237,12 @@ class BrainConfig:
         c.shift_min_blocks = max(1, _i(env, "SHIFT_MIN_BLOCKS", c.shift_min_blocks))
         c.trend_block = _i(env, "TREND_BLOCK", c.trend_block)
         c.trend_min_blocks = max(2, _i(env, "TREND_MIN_BLOCKS", c.trend_min_blocks))
+        c.auto_holdout = max(0, _i(env, "AUTO_HOLDOUT", c.auto_holdout))
+        c.auto_margin = max(0.0, _f(env, "AUTO_MARGIN", c.auto_margin))
+        z = _f(env, "AUTO_ZCAP", c.auto_zcap)
+        c.auto_zcap = z if z > 0 else c.auto_zcap
+        c.auto_reselect = _f(env, "AUTO_RESELECT", c.auto_reselect)
+        c.auto_candidates = env.get("AUTO_CANDIDATES", c.auto_candidates) or ""
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

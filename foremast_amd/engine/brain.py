@@ -146,6 +146,13 @@ class Brain(BrainStateMixin):
         from ..utils.spans import Spans
         self.spans = Spans(exporter.registry if exporter is not None else None)
         zoo.canonical(self.cfg.ml_algorithm)   # validate early
+        zoo.auto_candidates(self.cfg.auto_candidates)
+        # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
+        # last cycle ran: rows per model, and how many of them were selected anew
+        from ..models.cache import AutoChoices
+        self.auto_choices = AutoChoices(self.cfg.max_cache_size, self.cfg.auto_reselect)
+        self.auto_rows: dict[str, int] = {}
+        self.auto_selected = 0
         from .fastpath import FastPath, HpaTable
         # moving_average_all jobs: device-resident history + the benchmarked
         # tick (engine/fastpath.py); RESIDENT_HISTORY=0 sends every job
@@ -270,15 +277,19 @@ class Brain(BrainStateMixin):
         for i, a in enumerate(algos):
             groups.setdefault(a, []).append(i)
         keys = ("upper", "lower", "count", "score", "valid")
+        auto_choice: list = [None] * R
         if len(groups) == 1:
             algo = algos[0]
             pairs = self._pairs(rows) if algo == "bivariate_normal" else None
+            auto = self._auto_ctx(rows, algo)
             dec = zoo.decide(algo, hist, T, cur, hor, R, tables, diff,
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
                              pairs=pairs, cache=self._cache_ctx(rows, algo),
                              groups=self._groups(rows) if algo in zoo.MVN_MODELS else None,
                              mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
-                             **self._model_args(algo))
+                             auto=auto, **self._model_args(algo))
+            for i, nm in enumerate(self.auto_note(auto)):
+                auto_choice[i] = nm
             out = {k: getattr(dec, k).detach().cpu().numpy() for k in keys}
             flags = dec.flags
         else:
@@ -287,6 +298,7 @@ class Brain(BrainStateMixin):
                 sub = [rows[i] for i in idx]
                 it = torch.tensor(idx, dtype=torch.int64, device=hist.device)
                 pairs = self._pairs(sub) if algo == "bivariate_normal" else None
+                auto = self._auto_ctx(sub, algo)
                 dec = zoo.decide(algo, hist.index_select(0, it).contiguous(), T, cur.index_select(0, it).contiguous(),
                                  hor.index_select(0, it), len(idx),
                                  zoo.make_tables([r.alias for r in sub], self.cfg, self.device),
@@ -295,7 +307,9 @@ class Brain(BrainStateMixin):
                                  pairs=pairs, cache=self._cache_ctx(sub, algo),
                                  groups=self._groups(sub) if algo in zoo.MVN_MODELS else None,
                                  mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
-                                 **self._model_args(algo))
+                                 auto=auto, **self._model_args(algo))
+                for i, nm in zip(idx, self.auto_note(auto)):
+                    auto_choice[i] = nm
                 for k in keys:
                     v = getattr(dec, k).detach()
                     if k not in out:
@@ -307,6 +321,7 @@ class Brain(BrainStateMixin):
                 flags[it] = dec.flags
             out = {k: v.cpu().numpy() for k, v in out.items()}
         out["algorithms"] = algos
+        out["auto_choice"] = auto_choice
         out["_hist"], out["_T"] = hist, T
         out["flags"] = C.unpack_flags(flags, cur.shape[1])
         out["diff"] = None if diff is None else diff.cpu().numpy()
@@ -355,10 +370,43 @@ class Brain(BrainStateMixin):
         return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth,
                 "scale_smooth": self.cfg.seasonal_scale_smooth, "scale_floor": max(1e-3, self.cfg.seasonal_scale_floor)}
 
+    def _auto_args(self, algorithm: str) -> dict:
+        """The parameters of an ``auto_robust`` zoo call: AUTO_HOLDOUT,
+        AUTO_CANDIDATES, AUTO_ZCAP and AUTO_MARGIN, and for its candidates
+        what each gets as the configured model; nothing for any other model."""
+        if zoo.canonical(algorithm) != "auto_robust":
+            return {}
+        c = self.cfg
+        return {"period": c.seasonal_period_for(self.step), "smooth": c.seasonal_smooth,
+                "block": c.shift_block_for(self.step), "shift_threshold": c.shift_threshold,
+                "min_blocks": c.shift_min_blocks, "trend_block": c.trend_block_for(self.step),
+                "trend_min_blocks": c.trend_min_blocks, "scale_smooth": c.seasonal_scale_smooth,
+                "scale_floor": max(1e-3, c.seasonal_scale_floor), "holdout": c.auto_holdout,
+                "candidates": c.auto_candidates, "zcap": c.auto_zcap, "margin": c.auto_margin}
+
+    def _auto_ctx(self, rows: list[Row], algorithm: str) -> "zoo.AutoContext | None":
+        """The remembered choices of these rows, for an ``auto_robust`` call."""
+        if zoo.canonical(algorithm) != "auto_robust":
+            return None
+        return zoo.AutoContext(self.auto_choices, [(r.series, r.alias, r.base_metric) for r in rows],
+                               np.array([r.hist_t_last for r in rows], np.float64))
+
+    def auto_note(self, auto: "zoo.AutoContext | None") -> list:
+        """Count what an ``auto_robust`` call ran (``auto_rows``,
+        ``auto_selected``) -> the model name of each of its rows."""
+        if auto is None or auto.choice is None:
+            return []
+        names = [zoo.AUTO_CANDIDATES[c] for c in auto.choice.tolist()]
+        for nm in names:
+            self.auto_rows[nm] = self.auto_rows.get(nm, 0) + 1
+        self.auto_selected += auto.selected
+        return names
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
-                **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm)}
+                **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm),
+                **self._auto_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -459,6 +507,7 @@ class Brain(BrainStateMixin):
 
     def _cycle(self, t0: float) -> dict:
         now = self.clock()
+        self.auto_rows, self.auto_selected = {}, 0
         with self.spans.span("claim"):
             batch = self.store.claim_batch(self.worker, self.batch_size, self.cfg.max_stuck_seconds, now=now,
                                            shard=self._shard())
@@ -886,9 +935,11 @@ class Brain(BrainStateMixin):
         hist, T = res["_hist"], res["_T"]
         sel = torch.as_tensor(idx, dtype=torch.int64, device=hist.device)
         h = hist.index_select(0, sel).contiguous()
+        auto = self._auto_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm)
         try:
             fc, _ = zoo.forecast(self.cfg.hpa_forecast_algorithm, h, T, max(1, self.cfg.hpa_forecast_steps),
-                                 lstm_model=self.lstm_model,
+                                 lstm_model=self.lstm_model, auto=auto,
+                                 **self._auto_args(self.cfg.hpa_forecast_algorithm),
                                  cache=self._cache_ctx([rows[i] for i in idx], self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_args(self.cfg.hpa_forecast_algorithm),
                                  **self._trend_args(self.cfg.hpa_forecast_algorithm),

@@ -138,6 +138,9 @@ class ModelsMixin:
                 # every row of the group: the memo's list object, stable while the
                 # job list is (the model cache skips its per-row lookups for it)
                 keys = full if idx is None else kv[rows].tolist()
+            elif keys is None and algo == "auto_robust":
+                # the keys of the brain's choice memory (series, alias, base metric), as the general path makes them
+                keys = [k[:3] for k in self._cache_keys(works, p0, algo)[0][rows].tolist()]
             if hor is not None:
                 hr = hor[rows]
                 kh, hshape, hmax = i64(hr), hr.shape, max(1, int(hr.max()) if hr.size else 1)
@@ -637,6 +640,13 @@ class ModelsMixin:
         elif algo == "trend_robust":
             # only the columns the kernel holds are gathered
             return zoo.forecast(algo, lazy.materialize(zoo.trend_start(sub.T)), sub.T, H, **b._trend_args(algo))
+        elif algo == "auto_robust":
+            # its candidates read different spans: gathered from column 0; the rows' remembered
+            # choices go in, what is selected now comes back into the brain's memory and counters
+            auto = None if sub.keys is None else zoo.AutoContext(b.auto_choices, sub.keys, sub.t_last)
+            out = zoo.forecast(algo, lazy.materialize(0), sub.T, H, auto=auto, **b._auto_args(algo))
+            b.auto_note(auto)
+            return out
         else:
             hist = lazy.materialize(0)
         return zoo.forecast(algo, hist, sub.T, H, lstm_model=lstm, cache=ctx)
@@ -660,7 +670,9 @@ class ModelsMixin:
             sub = ModelSub(algo, list(range(M)), None, rm, shift, lim, T, None, keys,
                            self._hist_last(store.last_t[ga.rowmap.astype(np.int64)], store.step, ga.hist_end),
                            None, None, steps, M)
+            kept = dict(b.auto_rows), b.auto_selected
             fc, _ = self._forecast(algo, LazyHist(store.buf, rm, shift, lim, T), sub, steps)
+            b.auto_rows, b.auto_selected = kept             # auto_robust's counters describe the scoring alone
         return torch.nan_to_num(fc, nan=float("-inf")).amax(1).cpu().numpy()
 
     @staticmethod

@@ -387,3 +387,66 @@ class ModelCache:
                             pick(t.get(p + "season")) if kind >= 2 else None, pick(t[p + "sse"]), pick(t[p + "nobs"]))
             self._store([keys[i] for i in sel], kind, m, md, np.asarray(g["t_last"])[sel],
                         np.asarray(g["fitted_at"])[sel], device)
+
+
+class AutoChoices:
+    """``auto_robust``'s memory of which model each row took: key (series,
+    alias, base metric) -> (index into ``zoo.AUTO_CANDIDATES``, timestamp of
+    the history's last sample when it was selected).  A row is selected again
+    when it is unknown or its history has advanced by ``reselect`` seconds
+    since.  Bounded by ``capacity`` entries, the oldest entry leaving first
+    (0: nothing is remembered).  Host-side and not part of the checkpoint:
+    after a restart every row is selected anew.
+
+    The dict maps a key to a slot of two arrays, so that a lookup is one dict
+    probe per row and array passes for the rest."""
+
+    def __init__(self, capacity: int = 100000, reselect_seconds: float = 86400.0):
+        self.capacity = max(0, int(capacity))
+        self.reselect = float(reselect_seconds)
+        self.entries: dict = {}                    # key -> slot, oldest first
+        self.choice = np.zeros(0, np.int32)
+        self.t_sel = np.zeros(0, np.float64)
+        self.free: list[int] = []
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def lookup(self, keys: list, t_last) -> np.ndarray:
+        """Per row the remembered choice, or -1 where the row is to be selected now."""
+        get = self.entries.get
+        slot = np.fromiter((get(k, -1) for k in keys), np.int64, len(keys))
+        known = slot >= 0
+        if not known.any():
+            return np.full(len(keys), -1, np.int32)
+        s = np.where(known, slot, 0)
+        with np.errstate(invalid="ignore"):
+            stale = np.asarray(t_last, np.float64) - self.t_sel[s] >= self.reselect
+        return np.where(known & ~stale, self.choice[s], -1).astype(np.int32)
+
+    def remember(self, keys: list, t_last, choice, fresh=None) -> None:
+        """Record ``choice`` [R] for the rows ``fresh`` marks (default: all)."""
+        rows = range(len(keys)) if fresh is None else np.nonzero(np.asarray(fresh))[0].tolist()
+        slots = []
+        for i in rows:
+            s = self.entries.pop(keys[i], None)    # a re-selected row becomes the newest entry
+            if s is None:
+                if not self.free:
+                    n = len(self.choice)
+                    grow = max(64, n)
+                    self.choice = np.concatenate([self.choice, np.zeros(grow, np.int32)])
+                    self.t_sel = np.concatenate([self.t_sel, np.zeros(grow)])
+                    self.free = list(range(n + grow - 1, n - 1, -1))
+                s = self.free.pop()
+            self.entries[keys[i]] = s
+            slots.append(s)
+        if slots:
+            ix = np.fromiter(rows, np.int64, len(slots))
+            self.choice[slots] = np.asarray(choice)[ix]
+            self.t_sel[slots] = np.asarray(t_last, np.float64)[ix]
+        while len(self.entries) > self.capacity:
+            self.free.append(self.entries.pop(next(iter(self.entries))))
+
+    def clear(self) -> None:
+        self.entries.clear()
+        self.free = list(range(len(self.choice) - 1, -1, -1))

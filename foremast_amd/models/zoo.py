@@ -26,6 +26,8 @@ shift_robust                    median / MAD behind the last shift      K15 + ba
 trend_robust                    repeated-median line + residual MAD     K16 + band decide
 seasonal_trend_robust           repeated-median line + phase profile    K20 + band decide
 seasonal_scale_robust           phase profile + a sigma per phase       K22 + band decide (per point)
+auto_robust                     per row, the robust model that back-    K13-K22 fits + K23 + band
+                                tests best on the end of its history    decide (per point)
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -54,7 +56,7 @@ from ..ops import smoothing as SM
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
-              "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust")
+              "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -78,6 +80,8 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "robust_seasonal_trend": "seasonal_trend_robust", "robust_stl": "seasonal_trend_robust",
            "seasonal_scale_robust": "seasonal_scale_robust", "seasonal_hetero_robust": "seasonal_scale_robust",
            "robust_seasonal_scale": "seasonal_scale_robust", "seasonal_mad_profile": "seasonal_scale_robust",
+           "auto_robust": "auto_robust", "auto": "auto_robust", "robust_auto": "auto_robust",
+           "auto_select": "auto_robust",
            "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
            "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
@@ -98,6 +102,7 @@ class RowDecision:
     score: torch.Tensor      # [R] f32
     valid: torch.Tensor      # [R] int32 bit0 history ok, bit1 current present
     center: torch.Tensor | None = None
+    choice: torch.Tensor | None = None   # [R] int32 index into AUTO_CANDIDATES (auto_robust only)
 
 
 @dataclass
@@ -145,7 +150,9 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            lstm_model=None, pairs=None, cache: CacheContext | None = None, H: int | None = None,
            groups=None, mvn_threshold: float | None = None, smooth: int = 5, block: int | None = None,
            shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
-           mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1) -> RowDecision:
+           mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1, holdout: int = 0,
+           candidates=None, zcap: float = 8.0, margin: float = 0.05, auto: "AutoContext | None" = None,
+           trend_block: int | None = None) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -159,7 +166,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     ``mvn_reject`` is ``robust_multivariate``'s rejection limit in MAD-sigmas
     (<= 0: nothing is rejected).  ``scale_smooth`` and ``scale_floor`` are
     ``seasonal_scale_robust``'s: the half width of the window that smooths
-    its per-phase scale, and that scale's floor as a share of the pooled MAD."""
+    its per-phase scale, and that scale's floor as a share of the pooled MAD.
+    ``holdout``, ``candidates``, ``zcap`` and ``margin`` are ``auto_robust``'s
+    (:func:`auto_select`), which takes every other model's parameters for its
+    candidates (``trend_block``: its ``trend_robust``'s block where that
+    differs from ``block``); ``auto`` is its memory of earlier choices, when
+    there is one."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -222,6 +234,16 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "auto_robust":
+        # gated, row by row, on the finite count of the model the row chose
+        fc, sigma, nfin, choice = _auto_remembered(auto, hist, T, H, period, smooth, block, shift_threshold,
+                                                   min_blocks, trend_min_blocks, scale_smooth, scale_floor, holdout,
+                                                   candidates, zcap, margin, trend_block=trend_block)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        dec = band(fc, sigma, horizon, cur, M, tables, diff, valid)
+        dec.choice = choice
+        return dec
     fc, sigma = forecast(algo, hist, T, H, period=period, lstm_model=lstm_model, cache=cache, smooth=smooth)
     return band(fc, sigma, horizon, cur, M, tables, diff, _valid(hist, T, cur, tables.min_hist))
 
@@ -297,7 +319,7 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
 FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust",
-                                 "seasonal_scale_robust")
+                                 "seasonal_scale_robust", "auto_robust")
 
 
 def seasonal_start(T: int, period: int | None) -> int:
@@ -380,11 +402,161 @@ def _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, floor):
     return center[:, None].expand(-1, H), sigma, nfin
 
 
+# auto_robust's candidates in order of parsimony: a later one must back-test
+# better than an earlier one by more than the margin to be chosen.
+AUTO_CANDIDATES = ("robust_moving_average_all", "shift_robust", "trend_robust", "seasonal_robust",
+                   "seasonal_scale_robust", "seasonal_trend_robust")
+
+
+def auto_candidates(names=None) -> tuple[int, ...]:
+    """Indices into ``AUTO_CANDIDATES`` of a candidate list (names or aliases;
+    None or empty: all six), in the table's order whatever order they came in."""
+    if not names:
+        return tuple(range(len(AUTO_CANDIDATES)))
+    if isinstance(names, str):
+        names = [p for p in names.split(",") if p.strip()]
+    picked = set()
+    for nm in names:
+        k = str(nm).strip().lower()
+        if ALIASES.get(k) not in AUTO_CANDIDATES:
+            raise ValueError(f"unknown AUTO_CANDIDATES entry {nm!r}; supported: {', '.join(AUTO_CANDIDATES)}")
+        picked.add(AUTO_CANDIDATES.index(ALIASES[k]))
+    if not picked:
+        raise ValueError("AUTO_CANDIDATES names no model")
+    return tuple(sorted(picked))
+
+
+@dataclass
+class AutoContext:
+    """Which remembered choice each row of an ``auto_robust`` call maps to
+    (``models/cache.py`` AutoChoices)."""
+    choices: "AutoChoices"
+    keys: list              # one hashable key per row, e.g. (series, alias, base metric)
+    t_last: np.ndarray      # [R] timestamp of each row's last history sample
+    selected: int = 0       # out: rows this call selected anew
+    choice: np.ndarray | None = None    # out: [R] the model each row ran under (index into AUTO_CANDIDATES)
+
+
+def _auto_fit(ci: int, hist, T: int, H: int, m: int, smooth, block, shift_threshold, min_blocks, trend_min_blocks,
+              scale_smooth, scale_floor, trend_block=None):
+    """Candidate ``ci``'s own batched fit of ``hist[:, :T]``, exactly as its
+    single-model branch of :func:`decide` calls it -> (forecast [R, H] or
+    [R, 1], sigma [R] or [R, H], finite count [R]).  ``block`` is
+    ``shift_robust``'s and, unless ``trend_block`` names another,
+    ``trend_robust``'s."""
+    from ..ops import misc as MI
+    name = AUTO_CANDIDATES[ci]
+    if name == "robust_moving_average_all":
+        center, sigma, nfin = MI.robust_stats(hist[:, :T], T)
+        return center[:, None], sigma, nfin
+    if name == "shift_robust":
+        s0 = shift_start(T)
+        center, sigma, nseg = MI.shift_robust(hist[:, s0:T], T - s0, int(block), float(shift_threshold),
+                                              int(min_blocks))[:3]
+        return center[:, None], sigma, nseg
+    if name == "trend_robust":
+        return _trend_robust(hist, T, H, trend_block or block, trend_min_blocks)
+    if name == "seasonal_robust":
+        return _seasonal_robust(hist, T, H, m, smooth)
+    if name == "seasonal_scale_robust":
+        return _seasonal_scale_robust(hist, T, H, m, smooth, scale_smooth, scale_floor)
+    return _seasonal_trend_robust(hist, T, H, m, smooth, trend_min_blocks)
+
+
+def auto_select(hist: torch.Tensor, T: int, period: int | None = None, holdout: int = 0, smooth: int = 5,
+                block: int | None = None, shift_threshold: float = 4.0, min_blocks: int = 2,
+                trend_min_blocks: int = 3, scale_smooth: int = 30, scale_floor: float = 0.1, candidates=None,
+                zcap: float = 8.0, margin: float = 0.05, trend_block: int | None = None):
+    """Back-test selection of ``auto_robust`` -> (choice [R] int32 into
+    ``AUTO_CANDIDATES``, score [R, C] f32, n [R, C] int32; C = the candidates
+    in play).  The last ``L = holdout or period`` samples are held out, every
+    candidate is fitted on columns ``[0, T - L)`` of the same tensor (no copy)
+    with a forecast of ``L`` steps, and K23 scores the forecasts against
+    ``hist[:, T - L:T]`` and picks (``ops/misc.py`` ref_holdout_score,
+    ref_auto_pick).  A history shorter than ``2 L`` is not back-tested: every
+    row gets the first candidate.  A seasonal candidate that falls back
+    produces the first candidate's numbers and loses the tie by order."""
+    from ..ops import misc as MI
+    cand = auto_candidates(candidates)
+    R = hist.shape[0]
+    m = int(period or _detect_period(hist, T))
+    L = min(int(holdout) if holdout and int(holdout) > 0 else m, MI.ROBUST_LDS_KEYS)
+    if T < 2 * L or R == 0:
+        return (torch.full((R,), cand[0], dtype=torch.int32, device=hist.device),
+                torch.full((R, len(cand)), float("inf"), dtype=torch.float32, device=hist.device),
+                torch.zeros((R, len(cand)), dtype=torch.int32, device=hist.device))
+    fcs, sigmas = [], []
+    for ci in cand:
+        fc, sigma, _ = _auto_fit(ci, hist, T - L, L, m, smooth, block or 1440, shift_threshold, min_blocks,
+                                 trend_min_blocks, scale_smooth, scale_floor, trend_block)
+        fcs.append(fc)
+        sigmas.append(sigma)
+    score, n, _, pick = MI.holdout_score(hist[:, T - L:T], fcs, sigmas, zcap, margin)
+    choice = pick if len(cand) == len(AUTO_CANDIDATES) else \
+        torch.tensor(cand, dtype=torch.int32, device=pick.device)[pick.long()]
+    return choice, score, n
+
+
+def _auto_robust(hist, T, H, period=None, smooth=5, block=None, shift_threshold=4.0, min_blocks=2,
+                 trend_min_blocks=3, scale_smooth=30, scale_floor=0.1, holdout=0, candidates=None, zcap=8.0,
+                 margin=0.05, choice=None, trend_block=None):
+    """Every row under the robust model that back-tests best on it ->
+    (forecast [R, H], sigma [R, H], finite count [R] int32, choice [R] int32).
+    ``choice`` brings the caller's memory: entries ``>= 0`` are kept, ``-1``
+    (and all rows without it) are selected now (:func:`auto_select`).  Each
+    chosen model then runs once over the rows that chose it, on the whole
+    history; a sigma per row is broadcast along ``H``."""
+    R = hist.shape[0]
+    dev = hist.device
+    m = int(period or _detect_period(hist, T))
+    block = block or 1440
+    args = (smooth, block, shift_threshold, min_blocks, trend_min_blocks, scale_smooth, scale_floor)
+    trend_block = trend_block or block
+    if choice is None:
+        choice = torch.full((R,), -1, dtype=torch.int32, device=dev)
+    choice = choice.to(device=dev, dtype=torch.int32).clone()
+    if choice.numel() != R or bool((choice >= len(AUTO_CANDIDATES)).any()):
+        raise ValueError("choice must hold one candidate index (or -1) per row")
+    todo = (choice < 0).nonzero().squeeze(1)
+    if todo.numel():
+        sub = hist if todo.numel() == R else _aligned_rows(hist, todo, T)
+        choice[todo] = auto_select(sub, T, m, holdout, *args, candidates=candidates, zcap=zcap, margin=margin,
+                                    trend_block=trend_block)[0]
+    fc = torch.empty((R, H), dtype=torch.float32, device=dev)
+    sigma = torch.empty((R, H), dtype=torch.float32, device=dev)
+    nfin = torch.zeros((R,), dtype=torch.int32, device=dev)
+    for ci in torch.unique(choice).tolist():
+        idx = (choice == ci).nonzero().squeeze(1)
+        sub = hist if idx.numel() == R else _aligned_rows(hist, idx, T)
+        f, s, n = _auto_fit(int(ci), sub, T, H, m, *args, trend_block)
+        s = s[:, None] if s.dim() == 1 else s
+        fc[idx], sigma[idx], nfin[idx] = f.expand(-1, H), s.expand(-1, H), n.to(torch.int32)
+    return fc, sigma, nfin, choice
+
+
+def _auto_remembered(auto, hist, T, H, *args, trend_block=None):
+    """:func:`_auto_robust` with the choices ``auto`` remembers (an
+    :class:`AutoContext`, or None: every row is selected): rows it knows skip
+    the selection, and what is selected now is remembered."""
+    if auto is None:
+        return _auto_robust(hist, T, H, *args, trend_block=trend_block)
+    known = torch.from_numpy(auto.choices.lookup(auto.keys, auto.t_last))
+    out = _auto_robust(hist, T, H, *args, choice=known, trend_block=trend_block)
+    fresh = (known < 0).numpy()
+    auto.selected = int(fresh.sum())
+    auto.choice = out[3].cpu().numpy()
+    if auto.selected:
+        auto.choices.remember(auto.keys, auto.t_last, auto.choice, fresh)
+    return out
+
+
 def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | None = None,
              lstm_model=None, cache: CacheContext | None = None,
              smooth: int = 5, block: int | None = None,
              trend_min_blocks: int = 3, scale_smooth: int = 30,
-             scale_floor: float = 0.1) -> tuple[torch.Tensor, torch.Tensor]:
+             scale_floor: float = 0.1, shift_threshold: float = 4.0, min_blocks: int = 2, holdout: int = 0,
+             candidates=None, zcap: float = 8.0, margin: float = 0.05,
+             auto: AutoContext | None = None, trend_block: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]; sigma [R, H],
     one per step, from ``seasonal_scale_robust`` unless it fell back).  Used by the
@@ -420,6 +592,10 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return _seasonal_trend_robust(hist, T, H, period, smooth, trend_min_blocks)[:2]
     if algo == "seasonal_scale_robust":
         return _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, scale_floor)[:2]
+    if algo == "auto_robust":
+        return _auto_remembered(auto, hist, T, H, period, smooth, block, shift_threshold, min_blocks,
+                                trend_min_blocks, scale_smooth, scale_floor, holdout, candidates, zcap, margin,
+                                trend_block=trend_block)[:2]
     raise ValueError(f"{algorithm!r} is not a forecasting model ({', '.join(FORECASTERS)})")
 
 

@@ -113,6 +113,9 @@ _SIGS: dict[str, list] = {
     "fm_band_decide_pp": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                           c_void_p],
+    # x ld L R cands (host int64 [C, 6]) C zcap margin score n nx choice stream
+    "fm_holdout_score": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p],
     "fm_hpa_score": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                      ctypes.c_double, c_float, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                      c_void_p, c_void_p, c_void_p, c_void_p],

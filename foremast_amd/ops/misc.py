@@ -1,9 +1,9 @@
 """K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
 K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K22 seasonal scale robust
-model, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
+model, K23 hold-out score, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
 csrc/kernels/mvn_robust.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
 csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip, csrc/kernels/seasonal_scale_robust.hip,
-csrc/kernels/hpa_graph.hip) with numpy references."""
+csrc/kernels/holdout_score.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -913,6 +913,116 @@ def seasonal_scale_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: in
                  ptr(scale), stream_of(hist))
     out = (fc, sh, stats[:, 1].to(torch.int32), stats[:, 0], stats[:, 2])
     return out + (prof, scale) if want_profile else out
+
+
+# --------------------------------------------------------------------------- K23
+# Most candidates one launch scores (csrc/kernels/holdout_score.hip kHoldoutMaxCands).
+HOLDOUT_MAX_CANDIDATES = 8
+AUTO_ZCAP = 8.0
+AUTO_MARGIN = 0.05
+
+
+def ref_holdout_score(x, fc, sigma, zcap: float = AUTO_ZCAP):
+    """Capped Laplace log score of ``C`` forecasts of the held-out samples
+    ``x`` [R, L] -> (score [R, C] f32, n [R, C] int32, nx [R] int32).
+
+    ``fc`` and ``sigma`` are lists of ``C`` arrays, each [R, L] or [R, 1] (one
+    value along the row).  A point ``(r, c, t)`` counts when ``x``, ``fc`` and
+    ``sigma`` are finite and ``sigma > 0``; it contributes ``l + z`` with ``z =
+    min(fl32(|fl32(x - fc)| / sigma), zcap)`` and ``l = fl32(ln sigma)``, each
+    operation in fp32 rounded once.  ``score[r, c]`` is the fp64 sum of
+    ``(double) l + (double) z`` over the ``n[r, c]`` points that count, divided
+    by their number in fp64 and rounded once to fp32; ``+inf`` without one.
+    ``nx[r]`` is the number of finite ``x[r, :]``.  A narrow band scores low, a
+    band the held-out points fall outside of scores high, and no point adds
+    more than ``zcap``, so an incident inside the hold-out cannot decide."""
+    x = np.asarray(x, np.float32)
+    R, L = x.shape
+    C = len(fc)
+    check(len(sigma) == C, "one sigma per forecast")
+    zc = np.float32(zcap)
+    finx = np.isfinite(x)
+    nx = finx.sum(1).astype(np.int32)
+    score = np.full((R, C), np.inf, np.float32)
+    n = np.zeros((R, C), np.int32)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for c in range(C):
+            f = np.broadcast_to(np.asarray(fc[c], np.float32), (R, L))
+            s = np.broadcast_to(np.asarray(sigma[c], np.float32), (R, L))
+            ok = finx & np.isfinite(f) & np.isfinite(s) & (s > 0)
+            d = np.abs((x - f).astype(np.float32))
+            z = np.minimum((d / s).astype(np.float32), zc)
+            l = np.log(np.where(ok, s, 1).astype(np.float64)).astype(np.float32)
+            tot = np.where(ok, l.astype(np.float64) + z.astype(np.float64), 0.0).sum(1)
+            cnt = ok.sum(1)
+            n[:, c] = cnt
+            score[:, c] = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.inf).astype(np.float32)
+    return score, n, nx
+
+
+def ref_auto_pick(score, n, nx, margin: float = AUTO_MARGIN):
+    """The candidate each row takes -> choice [R] int32.  Candidate ``c`` is
+    eligible when it scored at least one point and at least half of the row's
+    finite samples (``n >= 1`` and ``2 n >= nx``); ``best`` is the smallest
+    eligible score, and the choice the first eligible candidate, in candidate
+    order, with ``score <= fl32(best + margin)``: a later candidate must win
+    by more than ``margin``.  0 when no candidate is eligible."""
+    score = np.asarray(score, np.float32)
+    n = np.asarray(n, np.int64)
+    nx = np.asarray(nx, np.int64)
+    elig = (n >= 1) & (2 * n >= nx[:, None])
+    best = np.where(elig, score, np.float32(np.inf)).min(1).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        near = elig & (score <= (best + np.float32(margin)).astype(np.float32)[:, None])
+    return np.where(near.any(1), near.argmax(1), 0).astype(np.int32)
+
+
+def _holdout_operand(t: torch.Tensor, x: torch.Tensor, what: str) -> torch.Tensor:
+    """A candidate's forecast or sigma as [R, L] or [R, 1] with column stride 0 or 1."""
+    R, L = x.shape
+    if t.dim() == 1:
+        t = t[:, None]
+    check(t.dim() == 2 and t.dtype == torch.float32 and t.device == x.device and t.shape[0] == R
+          and t.shape[1] in (1, L), f"{what} must be fp32 [R, L], [R, 1] or [R] on the device of x")
+    if t.shape[1] > 1 and t.stride(1) not in (0, 1):
+        t = t.contiguous()
+    return t
+
+
+def holdout_score(x: torch.Tensor, fc, sigma, zcap: float = AUTO_ZCAP, margin: float = AUTO_MARGIN):
+    """K23: (score [R, C], n [R, C] int32, nx [R] int32, choice [R] int32) of
+    :func:`ref_holdout_score` and :func:`ref_auto_pick` for the held-out
+    samples ``x`` [R, L] and ``C`` candidates.  ``x`` may be any column view
+    with unit column stride (rows need 4-byte alignment only); ``fc[c]`` and
+    ``sigma[c]`` are [R, L], [R, 1] or [R], at any row stride, and an expanded
+    (column stride 0) tensor counts as one value per row."""
+    check(x.dim() == 2 and x.dtype == torch.float32, "x must be fp32 [R, L]")
+    R, L = x.shape
+    C = len(fc)
+    check(len(sigma) == C and 1 <= C <= HOLDOUT_MAX_CANDIDATES,
+          f"between 1 and {HOLDOUT_MAX_CANDIDATES} candidates, one sigma per forecast")
+    check(L <= ROBUST_LDS_KEYS, f"at most {ROBUST_LDS_KEYS} held-out samples")
+    check(float(zcap) > 0 and float(margin) >= 0, "zcap must be > 0 and margin >= 0")
+    fc = [_holdout_operand(t, x, "fc") for t in fc]
+    sigma = [_holdout_operand(t, x, "sigma") for t in sigma]
+    if not x.is_cuda:
+        score, n, nx = ref_holdout_score(x.numpy(), [t.numpy() for t in fc], [t.numpy() for t in sigma], zcap)
+        return (torch.from_numpy(score), torch.from_numpy(n), torch.from_numpy(nx),
+                torch.from_numpy(ref_auto_pick(score, n, nx, margin)))
+    require_native(x)
+    check(x.stride(1) == 1 or L <= 1, "rows must have unit column stride")
+    d = x.device
+    score = torch.empty((R, C), dtype=torch.float32, device=d)
+    n = torch.empty((R, C), dtype=torch.int32, device=d)
+    nx = torch.empty((R,), dtype=torch.int32, device=d)
+    choice = torch.empty((R,), dtype=torch.int32, device=d)
+    if R:
+        col = lambda t: int(t.shape[1] > 1 and t.stride(1) == 1)
+        cands = np.array([[f.data_ptr(), f.stride(0), col(f), s.data_ptr(), s.stride(0), col(s)]
+                          for f, s in zip(fc, sigma)], np.int64)
+        LIB.call("fm_holdout_score", ptr(x), x.stride(0), L, R, cands.ctypes.data, C, float(zcap), float(margin),
+                 ptr(score), ptr(n), ptr(nx), ptr(choice), stream_of(x))
+    return score, n, nx, choice
 
 
 # --------------------------------------------------------------------------- K8
