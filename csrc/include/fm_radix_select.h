@@ -373,6 +373,117 @@ __device__ __forceinline__ void median_sigma(Keys& rk, unsigned n, KeyRange r, S
 }
 
 // ---------------------------------------------------------------------------
+// Several ranks of one row (K24, quantile_robust.hip: the median and a rank in
+// either tail).  All ranks share the prefix of the first pass, so its
+// histogram, the pass in which every key makes an add, is built once and
+// scanned once per rank; the passes below it are radix_select's, rank by rank.
+
+// wave 0, after the bins of a pass are complete: the lane whose run of bins
+// (mine; total s, exc keys in the lanes before it) holds rank k writes the
+// grown prefix, the rank inside the bin and the bin's count to out[0..3)
+__device__ __forceinline__ void pick_bin(const unsigned* mine, unsigned s, unsigned exc, unsigned k, unsigned pref,
+                                         int shift, unsigned* out) {
+  if (exc <= k && k < exc + s) {                               // one lane: the missing keys sort last
+    unsigned rest = k - exc, b = 0u, cc = mine[0];
+    while (rest >= cc) { rest -= cc; ++b; cc = mine[b]; }
+    out[0] = pref | (((unsigned)(lane_id() * kBinsPerLane) + b) << shift);
+    out[1] = rest;
+    out[2] = cc;
+  }
+}
+
+// Keys of the ranks rank[0..NR) (0-based, each below n) among the n finite
+// keys of rk, all within r: key[j], with cnt[j] keys equal to it and resid[j]
+// the rank inside that run.  sel is LDS, 3 NR words, free on entry.
+template <int NT, int NR, class Keys>
+__device__ __forceinline__ void radix_select_ranks(const Keys& rk, KeyRange r, const unsigned (&rank)[NR], unsigned n,
+                                                   SelectScratch<NT>* sc, unsigned* sel, unsigned (&key)[NR],
+                                                   unsigned (&resid)[NR], unsigned (&cnt)[NR]) {
+  unsigned* bins = sc->bins;
+  const int hi0 = r.min == r.max ? 32 : __clz(r.min ^ r.max);  // leading bits shared by every finite key
+  const unsigned pref0 = hi0 == 0 ? 0u : (hi0 == 32 ? r.min : (r.min & (~0u << (32 - hi0))));
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    key[j] = pref0;
+    resid[j] = rank[j];
+    cnt[j] = n;
+  }
+  if (hi0 == 32) return;
+  // every finite key carries pref0: the first pass counts them all, once
+  const int w0 = 32 - hi0 < kDigitBits ? 32 - hi0 : kDigitBits;
+  {
+    const int shift = 32 - hi0 - w0;
+    const unsigned dm = (1u << w0) - 1u;
+    rk.sweep([&](unsigned k) { bin_add(bins, k != kMissing, (k >> shift) & dm); });
+    __syncthreads();
+    if (wave_id() == 0) {
+      unsigned* mine = bins + lane_id() * kBinsPerLane;
+      unsigned s = 0u;
+#pragma unroll
+      for (int i = 0; i < kBinsPerLane / 4; ++i) {
+        const uint4 c = reinterpret_cast<const uint4*>(mine)[i];
+        s += c.x + c.y + c.z + c.w;
+      }
+      const unsigned inc = wave_incl_sum(s), exc = inc - s;
+#pragma unroll
+      for (int j = 0; j < NR; ++j) pick_bin(mine, s, exc, rank[j], pref0, shift, sel + 3 * j);
+#pragma unroll
+      for (int i = 0; i < kBinsPerLane / 4; ++i) reinterpret_cast<uint4*>(mine)[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      key[j] = sel[3 * j];
+      resid[j] = sel[3 * j + 1];
+      cnt[j] = sel[3 * j + 2];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    unsigned pref = key[j], k = resid[j], c = cnt[j];
+    unsigned* out = sel + 3 * j;
+    for (int hi = hi0 + w0; hi < 32;) {
+      const int w = 32 - hi < kDigitBits ? 32 - hi : kDigitBits, shift = 32 - hi - w;
+      const unsigned mask = ~0u << (32 - hi), dm = (1u << w) - 1u;
+      rk.sweep([&](unsigned x) { bin_add(bins, ((x ^ pref) & mask) == 0u, (x >> shift) & dm); });
+      __syncthreads();
+      if (wave_id() == 0) {
+        unsigned* mine = bins + lane_id() * kBinsPerLane;
+        unsigned s = 0u;
+#pragma unroll
+        for (int i = 0; i < kBinsPerLane / 4; ++i) {
+          const uint4 v = reinterpret_cast<const uint4*>(mine)[i];
+          s += v.x + v.y + v.z + v.w;
+        }
+        const unsigned inc = wave_incl_sum(s);
+        pick_bin(mine, s, inc - s, k, pref, shift, out);
+#pragma unroll
+        for (int i = 0; i < kBinsPerLane / 4; ++i) reinterpret_cast<uint4*>(mine)[i] = make_uint4(0u, 0u, 0u, 0u);
+      }
+      __syncthreads();
+      pref = out[0];
+      k = out[1];
+      c = out[2];
+      hi += w;
+    }
+    key[j] = pref;
+    resid[j] = k;
+    cnt[j] = c;
+  }
+}
+
+// The upper middle key of n finite keys whose lower middle lo was selected
+// with (resid, cnt): select_middles' second half.
+template <int NT, class Keys>
+__device__ __forceinline__ unsigned upper_middle(const Keys& rk, unsigned lo, unsigned n, unsigned resid, unsigned cnt,
+                                                 SelectScratch<NT>* sc) {
+  if ((n & 1u) != 0u || resid + 1u < cnt) return lo;           // the run of lo still holds the upper middle
+  unsigned above = kMissing;
+  rk.sweep([&](unsigned k) { if (k > lo && k < above) above = k; });
+  return block_min_u32<NT>(above, sc->redu);
+}
+
+// ---------------------------------------------------------------------------
 // The J blocks of L words that start at word lo of kw: f(key, block) for every
 // word of the quads they touch, block outside [0, J) for a word in front of or
 // behind them.  A thread walks its quads with the block and the position in it

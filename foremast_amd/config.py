@@ -101,6 +101,9 @@ class BrainConfig:
     auto_zcap: float = 8.0                   # AUTO_ZCAP
     auto_reselect: float = 86400.0           # AUTO_RESELECT
     auto_candidates: str = ""                # AUTO_CANDIDATES
+    # quantile_robust: the threshold at which its band ends on the history's own tail quantiles, clamped to
+    # [0.5, 3.0]; a side tolerates 1 - Phi(z) of the history as past incidents (2.3 % at 2.0)
+    quantile_tail_z: float = 2.0             # QUANTILE_TAIL_Z
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -243,6 +246,7 @@ class BrainConfig:
         c.auto_zcap = z if z > 0 else c.auto_zcap
         c.auto_reselect = _f(env, "AUTO_RESELECT", c.auto_reselect)
         c.auto_candidates = env.get("AUTO_CANDIDATES", c.auto_candidates) or ""
+        c.quantile_tail_z = min(3.0, max(0.5, _f(env, "QUANTILE_TAIL_Z", c.quantile_tail_z)))
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

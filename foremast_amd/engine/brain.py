@@ -402,11 +402,18 @@ class Brain(BrainStateMixin):
         self.auto_selected += auto.selected
         return names
 
+    def _quantile_args(self, algorithm: str) -> dict:
+        """``tail_z`` of a zoo decision: QUANTILE_TAIL_Z (within [0.5, 3.0])
+        for ``quantile_robust``, nothing for any other model."""
+        if zoo.canonical(algorithm) != "quantile_robust":
+            return {}
+        return {"tail_z": min(3.0, max(0.5, float(self.cfg.quantile_tail_z)))}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
                 **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm),
-                **self._auto_args(algorithm)}
+                **self._auto_args(algorithm), **self._quantile_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),

@@ -310,8 +310,8 @@ class ModelsMixin:
             lazy = LazyHist(store.buf, sub.rm, *sub.shift_lim(), sub.T)
             algo = sub.algo
             if algo in ("moving_average_all", "bivariate_normal", *zoo.MVN_MODELS, "moving_average", *zoo.ROBUST,
-                        "shift_robust"):
-                lo_col = 0
+                        "shift_robust", "quantile_robust"):
+                lo_col = 0                                   # (quantile_robust: the whole history, as it lies)
                 if algo == "moving_average":
                     w = min(sub.T, max(4, (60 + 3) // 4 * 4))
                     lo_col = (sub.T - w) // 4 * 4
@@ -321,7 +321,7 @@ class ModelsMixin:
                     lo_col = zoo.shift_start(sub.T)
                 dec = zoo.decide(algo, lazy.materialize(lo_col), sub.T, cur, sub.hor, sub.M, sub.tables, dsub,
                                  mvn_threshold=cfg.mvn_threshold(), mvn_reject=cfg.multivariate_reject,
-                                 **b._shift_args(algo))
+                                 **b._shift_args(algo), **b._quantile_args(algo))
             else:
                 H = sub.H
                 if hpa_algo == algo:

@@ -28,6 +28,7 @@ seasonal_trend_robust           repeated-median line + phase profile    K20 + ba
 seasonal_scale_robust           phase profile + a sigma per phase       K22 + band decide (per point)
 auto_robust                     per row, the robust model that back-    K13-K22 fits + K23 + band
                                 tests best on the end of its history    decide (per point)
+quantile_robust                 median + a sigma per side, tail ranks   K24 + band decide (two sigmas)
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -56,7 +57,8 @@ from ..ops import smoothing as SM
 ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "double_exponential_smoothing",
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
-              "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust")
+              "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust",
+              "quantile_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -82,6 +84,8 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "robust_seasonal_scale": "seasonal_scale_robust", "seasonal_mad_profile": "seasonal_scale_robust",
            "auto_robust": "auto_robust", "auto": "auto_robust", "robust_auto": "auto_robust",
            "auto_select": "auto_robust",
+           "quantile_robust": "quantile_robust", "skew_robust": "quantile_robust",
+           "asymmetric_robust": "quantile_robust", "tail_quantile": "quantile_robust",
            "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
            "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
@@ -152,7 +156,7 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
            mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1, holdout: int = 0,
            candidates=None, zcap: float = 8.0, margin: float = 0.05, auto: "AutoContext | None" = None,
-           trend_block: int | None = None) -> RowDecision:
+           trend_block: int | None = None, tail_z: float = 2.0) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -171,7 +175,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     (:func:`auto_select`), which takes every other model's parameters for its
     candidates (``trend_block``: its ``trend_robust``'s block where that
     differs from ``block``); ``auto`` is its memory of earlier choices, when
-    there is one."""
+    there is one.  ``tail_z`` is ``quantile_robust``'s: the threshold at which
+    its band ends on the history's own tail quantiles."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -187,6 +192,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         return _expand_stats(dec, n)
     if algo in ROBUST:
         return _robust(hist, T, robust_start(algo, T, window), cur, horizon, M, tables, diff)
+    if algo == "quantile_robust":
+        return _quantile_robust(hist, T, cur, horizon, M, tables, diff, tail_z)
     if algo == "shift_robust":
         return _shift_robust(hist, T, cur, horizon, M, tables, diff, block or 1440, shift_threshold, min_blocks)
     if algo == "bivariate_normal":
@@ -248,17 +255,22 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     return band(fc, sigma, horizon, cur, M, tables, diff, _valid(hist, T, cur, tables.min_hist))
 
 
-def band(fc: torch.Tensor, sigma: torch.Tensor, horizon: torch.Tensor, cur: torch.Tensor, M: int, tables: Tables,
+def band(fc: torch.Tensor, sigma, horizon: torch.Tensor, cur: torch.Tensor, M: int, tables: Tables,
          diff: torch.Tensor | None, valid: torch.Tensor) -> RowDecision:
     """Forecast -> per-point bands and decisions: each current point is
     judged against the forecast at its own horizon, centre +/- thr * sigma.
     ``sigma`` is [R], or [R, H] with a sigma per forecast step, which is
-    gathered at the horizon like the centre.  Rows without enough history
-    (``valid`` bit 0) flag nothing."""
+    gathered at the horizon like the centre, or a pair (sigma_lo [R],
+    sigma_up [R]) with a sigma per side of the centre.  Rows without enough
+    history (``valid`` bit 0) flag nothing."""
     H = fc.shape[1]
     idx = (horizon.clamp(1, H) - 1).to(fc.device)
     center = torch.gather(fc, 1, idx).contiguous()
-    if sigma.dim() == 2:
+    if isinstance(sigma, (tuple, list)):
+        sigma_lo, sigma_up = sigma
+        up, lo, flags, cnt, sc = SM.band_decide_2s(cur, center, sigma_lo.contiguous(), sigma_up.contiguous(), M,
+                                                   tables.thr, tables.bound, tables.minlb, diff, tables.pair_factor)
+    elif sigma.dim() == 2:
         up, lo, flags, cnt, sc = SM.band_decide_pp(cur, center, torch.gather(sigma, 1, idx).contiguous(), M,
                                                    tables.thr, tables.bound, tables.minlb, diff, tables.pair_factor)
     else:
@@ -290,6 +302,22 @@ def _robust(hist, T, start, cur, horizon, M, tables, diff) -> RowDecision:
     has_cur = torch.isfinite(cur).any(1).to(torch.int32)
     valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
     return band(center[:, None], sigma, horizon, cur, M, tables, diff, valid)
+
+
+def _quantile_robust(hist, T, cur, horizon, M, tables, diff, tail_z=2.0) -> RowDecision:
+    """Asymmetric band for skewed metrics: centre = median, and a sigma per
+    side such that the band at ``thr = tail_z`` ends on the history's own
+    ``Phi(-tail_z)`` and ``Phi(tail_z)`` quantiles (K24; the one-sided mean
+    deviation where a side's quantile is the median itself); the band decision
+    with two sigmas then applies the per-metric thresholds, bounds and canary
+    factor, each side in its own sigma units.  The history gate is the
+    kernel's finite count, as ``_robust``'s.  Whole history only: no window,
+    no cache, no seasonal form."""
+    from ..ops import misc as MI
+    center, sigma_lo, sigma_up, nfin = MI.quantile_robust_stats(hist[:, :T], T, MI.quantile_tail_z(tail_z))
+    has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+    valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+    return band(center[:, None], (sigma_lo, sigma_up), horizon, cur, M, tables, diff, valid)
 
 
 def shift_start(T: int) -> int:

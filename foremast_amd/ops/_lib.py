@@ -113,6 +113,13 @@ _SIGS: dict[str, list] = {
     "fm_band_decide_pp": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                           c_void_p],
+    # hist ld T R p inv_z0 out stream
+    "fm_quantile_robust_stats": [c_void_p, c_i64, c_int, c_i64, ctypes.c_double, c_float, c_void_p, c_void_p],
+    # cur ld_c n center ld_f sigma_lo sigma_up R M thr bound minlb diff pair_factor upper lower flags NW count score
+    # stream
+    "fm_band_decide_2s": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                          c_void_p],
     # x ld L R cands (host int64 [C, 6]) C zcap margin score n nx choice stream
     "fm_holdout_score": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p],

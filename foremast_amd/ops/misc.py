@@ -1,6 +1,7 @@
 """K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
 K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K22 seasonal scale robust
-model, K23 hold-out score, K8 HPA score, K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
+model, K23 hold-out score, K24 quantile robust statistics (csrc/kernels/quantile_robust.hip), K8 HPA score,
+K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
 csrc/kernels/mvn_robust.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
 csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip, csrc/kernels/seasonal_scale_robust.hip,
 csrc/kernels/holdout_score.hip, csrc/kernels/hpa_graph.hip) with numpy references."""
@@ -1023,6 +1024,94 @@ def holdout_score(x: torch.Tensor, fc, sigma, zcap: float = AUTO_ZCAP, margin: f
         LIB.call("fm_holdout_score", ptr(x), x.stride(0), L, R, cands.ctypes.data, C, float(zcap), float(margin),
                  ptr(score), ptr(n), ptr(nx), ptr(choice), stream_of(x))
     return score, n, nx, choice
+
+
+# --------------------------------------------------------------------------- K24
+QUANTILE_TAIL_Z = 2.0
+QUANTILE_TAIL_Z_RANGE = (0.5, 3.0)
+
+
+def quantile_tail_z(z0) -> float:
+    """``QUANTILE_TAIL_Z`` within the range the model takes, [0.5, 3.0] (the
+    default for a value that is no number)."""
+    z = float(z0)
+    if not np.isfinite(z):
+        return QUANTILE_TAIL_Z
+    return min(max(z, QUANTILE_TAIL_Z_RANGE[0]), QUANTILE_TAIL_Z_RANGE[1])
+
+
+def quantile_tail_params(z0: float) -> tuple[float, np.float32]:
+    """What K24 and its contract take of ``z0``: ``p = Phi(z0)`` in fp64 and
+    ``float32(1 / z0)``."""
+    import math
+    z = float(z0)
+    check(z > 0 and math.isfinite(z), "z0 must be a positive number")
+    return 0.5 * (1.0 + math.erf(z / math.sqrt(2.0))), np.float32(1.0 / z)
+
+
+def ref_quantile_robust_stats(hist, T: int, z0: float = QUANTILE_TAIL_Z):
+    """Median and one sigma per side, from tail order statistics of the finite
+    samples of ``hist[r, :T]`` -> (center [R] f32, sigma_lo [R] f32, sigma_up
+    [R] f32, n [R] int32).  With ``s`` the sorted finite samples, ``p =
+    Phi(z0)`` (fp64) and ``iz = float32(1 / z0)``: ``center = 0.5 s[(n-1)//2]
+    + 0.5 s[n//2]`` (:func:`ref_robust_stats`' centre), ``k_up = ceil(p (n -
+    1))`` in fp64, ``k_lo = (n - 1) - k_up``, ``d_up = s[k_up] - center``,
+    ``d_lo = center - s[k_lo]`` in fp32, and ``sigma = d * iz`` on either side:
+    the band at ``thr = z0`` ends on those two samples.  A side with ``d == 0``
+    takes ``1.2533`` times the mean of ``x - center`` over the finite ``x >=
+    center`` (of ``center - x`` over ``x <= center``), summed and divided in
+    fp64 and rounded once, which is 0 only where no sample lies on that side.
+    ``n == 0`` gives NaN for all three.  Single order statistics, nothing
+    interpolated: the GPU kernel reproduces centre and ``d`` bit for bit."""
+    p, iz = quantile_tail_params(z0)
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    fin = np.isfinite(x)
+    n = fin.sum(1).astype(np.int32)
+    center = np.full(R, np.nan, np.float32)
+    sigma_lo = np.full(R, np.nan, np.float32)
+    sigma_up = np.full(R, np.nan, np.float32)
+    if x.shape[1] == 0 or not n.any():
+        return center, sigma_lo, sigma_up, n
+    n1 = (np.maximum(n, 1) - 1).astype(np.int64)
+    k_up = np.minimum(np.ceil(p * n1.astype(np.float64)).astype(np.int64), n1)
+    k_lo = n1 - k_up
+    s = np.sort(np.where(fin, x, np.float32(np.inf)), axis=1)         # missing samples sort last
+    at = lambda k: np.take_along_axis(s, k[:, None], 1)[:, 0]
+    half, mean_dev = np.float32(0.5), np.float32(1.2533)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = half * at(n1 // 2) + half * at((n1 + 1) // 2)
+        d_up = (at(k_up) - c).astype(np.float32)
+        d_lo = (c - at(k_lo)).astype(np.float32)
+        dev = x - c[:, None]                                            # fp32
+        above, below = fin & (dev >= 0), fin & (dev <= 0)
+        m_up = (np.where(above, dev, 0).astype(np.float64).sum(1) / np.maximum(above.sum(1), 1)).astype(np.float32)
+        m_lo = (np.where(below, -dev, 0).astype(np.float64).sum(1) / np.maximum(below.sum(1), 1)).astype(np.float32)
+        su = np.where(d_up > 0, d_up * iz, mean_dev * m_up).astype(np.float32)
+        sl = np.where(d_lo > 0, d_lo * iz, mean_dev * m_lo).astype(np.float32)
+    ok = n > 0
+    center[ok], sigma_lo[ok], sigma_up[ok] = c[ok], sl[ok], su[ok]
+    return center, sigma_lo, sigma_up, n
+
+
+def quantile_robust_stats(hist: torch.Tensor, T: int, z0: float = QUANTILE_TAIL_Z):
+    """K24: per-row (center, sigma_lo, sigma_up, n) of
+    :func:`ref_quantile_robust_stats` over ``hist[:, :T]``, by exact selection
+    of three ranks on the GPU.  ``hist`` may be any column view with unit
+    column stride: rows need 4-byte alignment only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    p, iz = quantile_tail_params(z0)
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_quantile_robust_stats(hist.numpy(), T, z0))
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    out = torch.empty((R, 4), dtype=torch.float32, device=hist.device)
+    if R:
+        LIB.call("fm_quantile_robust_stats", ptr(hist), hist.stride(0), int(T), R, p, float(iz), ptr(out),
+                 stream_of(hist))
+    return out[:, 0], out[:, 1], out[:, 2], out[:, 3].to(torch.int32)
 
 
 # --------------------------------------------------------------------------- K8

@@ -540,3 +540,64 @@ def ref_band_decide_pp(cur, center, sigma, M, thr, bound, minlb, diff, pair_fact
     t = torch.from_numpy
     return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
             t(flag.sum(1).astype(np.int32)), t(score))
+
+
+def band_decide_2s(cur: torch.Tensor, center: torch.Tensor, sigma_lo: torch.Tensor, sigma_up: torch.Tensor, M: int,
+                   thr, bound, minlb, diff: torch.Tensor | None = None, pair_factor: float = 0.8):
+    """:func:`band_decide` with a sigma per side, ``sigma_lo [R]`` and
+    ``sigma_up [R]``: a row's points are judged against [centre - thr *
+    sigma_lo, centre + thr * sigma_up] and a flagged point scores its excess in
+    units of the sigma of the side it left.  A NaN sigma flags nothing on its
+    side; rows with ``sigma_lo == sigma_up`` get :func:`band_decide`'s
+    outputs."""
+    R, n = cur.shape
+    for s in (sigma_lo, sigma_up):
+        check(s.dim() == 1 and s.shape[0] == R and s.dtype == torch.float32, "sigma_lo and sigma_up must be fp32 [R]")
+    NW = max(1, (n + 63) // 64)
+    if not cur.is_cuda:
+        return ref_band_decide_2s(cur.numpy(), center.numpy(), sigma_lo.numpy(), sigma_up.numpy(), M, thr.numpy(),
+                                  bound.numpy(), minlb.numpy(), None if diff is None else diff.numpy(), pair_factor)
+    require_native(cur)
+    sigma_lo, sigma_up = sigma_lo.contiguous(), sigma_up.contiguous()
+    d = cur.device
+    up = torch.empty((R, n), dtype=torch.float32, device=d)
+    lo = torch.empty_like(up)
+    flags = torch.empty((R, NW), dtype=torch.int64, device=d)
+    cnt = torch.empty((R,), dtype=torch.int32, device=d)
+    sc = torch.empty((R,), dtype=torch.float32, device=d)
+    LIB.call("fm_band_decide_2s", ptr(cur), cur.stride(0), n, ptr(center), center.stride(0), ptr(sigma_lo),
+             ptr(sigma_up), R, M, ptr(thr), ptr(bound), ptr(minlb), ptr(diff), float(pair_factor), ptr(up), ptr(lo),
+             ptr(flags), NW, ptr(cnt), ptr(sc), stream_of(cur))
+    return up, lo, flags, cnt, sc
+
+
+def ref_band_decide_2s(cur, center, sigma_lo, sigma_up, M, thr, bound, minlb, diff, pair_factor):
+    """:func:`ref_band_decide` with ``sigma_lo [R]`` below the centre and
+    ``sigma_up [R]`` above it: a point over the upper bound scores ``(x -
+    upper) / sigma_up``, one under the lower bound ``(lower - x) / sigma_lo``
+    (1e30 where that side's sigma is not > 0)."""
+    R, n = cur.shape
+    m = np.arange(R) % M
+    th = thr[m].astype(np.float32)
+    if diff is not None:
+        th = np.where(diff != 0, th * np.float32(pair_factor), th)
+    sigma_lo, sigma_up = np.asarray(sigma_lo, np.float32), np.asarray(sigma_up, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        up = center + (th * sigma_up)[:, None]
+        lo = np.maximum(center - (th * sigma_lo)[:, None], minlb[m][:, None])
+    bd = bound[m]
+    ok = np.isfinite(cur) & np.isfinite(center)
+    hi = ((bd & 1) != 0)[:, None] & (cur > up) & ok
+    lw = ((bd & 2) != 0)[:, None] & (cur < lo) & ok
+    flag = hi | lw
+    sd = np.where(hi, sigma_up[:, None], sigma_lo[:, None])
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z = np.where(sd > 0, np.where(hi, cur - up, lo - cur) / np.where(sd > 0, sd, 1), 1e30)
+    score = np.where(flag, z, 0).max(1, initial=0).astype(np.float32)
+    NW = max(1, (n + 63) // 64)
+    padded = np.zeros((R, NW * 64), bool)
+    padded[:, :n] = flag
+    words = np.packbits(padded.reshape(R, NW, 64), axis=2, bitorder="little").view(np.uint64).reshape(R, NW)
+    t = torch.from_numpy
+    return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
+            t(flag.sum(1).astype(np.int32)), t(score))
