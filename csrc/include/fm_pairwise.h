@@ -22,7 +22,8 @@ using namespace fm;
 // K4: pairwise tests. One wave per (service, metric) row, 4 rows per 256-thread
 // workgroup.  The pooled sample (n1 + n2 <= 64*K) is sorted in registers with a
 // bitonic network (in-register swaps for strides >= 64, __shfl_xor below),
-// average ranks with ties come from a max-scan / suffix-min-scan over tie runs.
+// average ranks with ties come from a max-scan / suffix-min-scan over tie runs
+// (a sorted array without ties skips them: the run-free path of avg_ranks).
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -93,25 +94,63 @@ __device__ __forceinline__ void bitonic_sort(T (&v)[K], int (&tag)[K]) {
 // over tie runs (the caller reduces it, packed with its other integer sums);
 // is_end marks the last element of each run (where empirical CDFs are
 // evaluated).
-template <int K, typename T>
+//
+// Run-free path: when no two neighbours among the n real entries are equal
+// (decided for the whole wave by ballot, so the branch is scalar), every tie
+// run has length 1: rank2 = 2 i + 2, is_end = i < n and the tie term is 0,
+// and none of the scans below runs.  A sorted array takes this path if and
+// only if its tie term is 0.  Equality is T's own == (float: -0.0 ties +0.0),
+// the comparison the tied path uses for its run starts, and the tied path
+// reuses the neighbour compare made here.
+// REDUCE: the return value is the wave-uniform tie term itself, reduced inside
+// the tied path (for a caller that has nothing to pack it with: the run-free
+// path then pays no reduction for a sum known to be 0).
+template <int K, bool REDUCE, typename T>
 __device__ __forceinline__ int avg_ranks(const T (&v)[K], int n, int (&rank2)[K], bool (&is_end)[K]) {
   // rank2 = 2 x (1-based average rank) = start + end + 2: exact integers, so
   // rank sums and the tie term sum(t^3 - t) (<= 1024^3 < 2^31) need no doubles.
   const int lane = lane_id();
-  int start_idx[K];
-  int carry = 0;
+  bool ne_prev[K];   // v[i] != v[i - 1] (lane 0 of register 0: against the edge value, unused)
+  unsigned long long tied = 0;
   T last_prev = 0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    const int i = k * 64 + lane;
     const T prev = lane_prev(v[k], last_prev);
-    const bool st = (i == 0) || (v[k] != prev);
+    ne_prev[k] = v[k] != prev;
+    // 0 < i < n as a scalar lane mask: pads (+inf) sit at i >= n and equal each
+    // other, and lane 0 of register 0 has no left neighbour
+    const int nk = n - 64 * k;
+    const unsigned long long real = nk >= 64 ? ~0ull : (nk > 0 ? (1ull << nk) - 1ull : 0ull);
+    tied |= __ballot(v[k] == prev) & (k == 0 ? real & ~1ull : real);
+    if (k + 1 < K) last_prev = lane_bcast(v[k], 63);
+  }
+  if (tied == 0) {
+    // Everything here is a function of the lane id and n alone.  It is formed
+    // from an opaque copy of the lane id: as loop invariants the compiler would
+    // hoist the K rank constants (and the i of i < n) out of the caller's row
+    // loop and hold that many more registers through both sorts.  One add per
+    // register either way: hoisted, this arm is K copies.
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int i = k * 64 + lo;
+      rank2[k] = 2 * i + 2;
+      is_end[k] = i < n;
+    }
+    return 0;
+  }
+  int start_idx[K];
+  int carry = 0;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = k * 64 + lane;
+    const bool st = (i == 0) || ne_prev[k];
     int s = st ? i : 0;
     s = wave_incl_max(s, 0);
     s = s > carry ? s : carry;
     start_idx[k] = s;
     carry = lane_bcast(s, 63);
-    last_prev = lane_bcast(v[k], 63);
   }
   int carry_e = 0x7fffffff;
   T next_first = 0;
@@ -134,6 +173,7 @@ __device__ __forceinline__ int avg_ranks(const T (&v)[K], int n, int (&rank2)[K]
       tl += __mul24(__mul24(t, t) - 1, t);
     }
   }
+  if constexpr (REDUCE) tl = (int)wave_sum_uniform((unsigned)tl);
   return tl;
 }
 
@@ -270,10 +310,22 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
   }
 
   hook.loaded();
+  // The four integer sums, packed by their bounds at n <= 64 K pooled values
+  // and nw <= 64 KW pairs (what the registers hold): tie <= n^3 - n (one run),
+  // r1x2 <= n (n + 1) (the doubled average ranks of all n values sum to that),
+  // likewise tiew and rplus2 over nw.  K = 1: two words; K = 2 and 4: three;
+  // K >= 8: four.  A tie term that shares no word comes reduced from avg_ranks.
+  constexpr long long N = 64LL * K, NW = 64LL * KW;
+  constexpr int bTie = pw_bits(N * N * N - N), bR1 = pw_bits(N * (N + 1));
+  constexpr int bTiew = pw_bits(NW * NW * NW - NW), bRp = pw_bits(NW * (NW + 1));
+  static_assert(bTie <= 32 && bTiew <= 32 && bR1 <= 32 && bRp <= 32, "32-bit sums");
+  constexpr bool packA = bTie + bR1 <= 32;                        // tie | r1x2
+  constexpr bool packB = bTiew + bRp <= 32;                       // tiew | rplus2
+  constexpr bool packC = !packA && !packB && bR1 + bRp <= 32;     // r1x2 | rplus2
   bitonic_sort<K, SPLIT>(v, tag);
   int rk2[K];
   bool en[K];
-  const int tie_l = avg_ranks<K>(v, n, rk2, en);
+  const int tie_l = avg_ranks<K, !packA>(v, n, rk2, en);
 
   unsigned r1x2 = 0;
   int dnum = 0;   // max |a1 n2 - a2 n1| over tie-run ends = D n1 n2
@@ -299,37 +351,25 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
   for (int k = 0; k < KW; ++k) dmag[k] = dk[k] >> 1;
   int rw2[KW];
   bool ew[KW];
-  const int tiew_l = avg_ranks<KW>(dmag, nw, rw2, ew);
+  const int tiew_l = avg_ranks<KW, !packB>(dmag, nw, rw2, ew);
   unsigned rplus2 = 0;
 #pragma unroll
   for (int k = 0; k < KW; ++k)
     if ((dk[k] & 1u) != 0u) rplus2 += (unsigned)rw2[k];
 
-  // The four integer sums, packed by their bounds at n <= 64 K pooled values
-  // and nw <= 64 KW pairs (what the registers hold): tie <= n^3 - n (one run),
-  // r1x2 <= n (n + 1) (the doubled average ranks of all n values sum to that),
-  // likewise tiew and rplus2 over nw.  K = 1: two words; K = 2 and 4: three;
-  // K >= 8: four.
-  constexpr long long N = 64LL * K, NW = 64LL * KW;
-  constexpr int bTie = pw_bits(N * N * N - N), bR1 = pw_bits(N * (N + 1));
-  constexpr int bTiew = pw_bits(NW * NW * NW - NW), bRp = pw_bits(NW * (NW + 1));
-  static_assert(bTie <= 32 && bTiew <= 32 && bR1 <= 32 && bRp <= 32, "32-bit sums");
-  constexpr bool packA = bTie + bR1 <= 32;                        // tie | r1x2
-  constexpr bool packB = bTiew + bRp <= 32;                       // tiew | rplus2
-  constexpr bool packC = !packA && !packB && bR1 + bRp <= 32;     // r1x2 | rplus2
   unsigned tie, tiew, r1s, rps;
   auto lowbits = [](unsigned w, int b) { return b >= 32 ? w : (w & ((1u << (b & 31)) - 1u)); };
   if constexpr (packA) {
     const unsigned w = wave_sum_uniform((unsigned)tie_l | (r1x2 << bTie));
     tie = lowbits(w, bTie); r1s = w >> bTie;
   } else {
-    tie = wave_sum_uniform((unsigned)tie_l);
+    tie = (unsigned)tie_l;   // reduced by avg_ranks, in its tied path only
   }
   if constexpr (packB) {
     const unsigned w = wave_sum_uniform((unsigned)tiew_l | (rplus2 << bTiew));
     tiew = lowbits(w, bTiew); rps = w >> bTiew;
   } else {
-    tiew = wave_sum_uniform((unsigned)tiew_l);
+    tiew = (unsigned)tiew_l;
   }
   if constexpr (packC) {
     const unsigned w = wave_sum_uniform(r1x2 | (rplus2 << bR1));
