@@ -42,31 +42,36 @@ struct EsModel {
   // adds its squared one-step error to acc and counts in n.  (Accumulating
   // inside the observed branch keeps the compiler from deferring 16 error
   // terms to the end of a prefetch chunk, which cost ~15 % in VGPRs/VALU.)
+  // Every product feeds an explicit fma, so no contraction is left to the
+  // compiler and the roundings do not depend on the instantiation: left to
+  // it, the NOSTORE runs (whose seasonal update is dead code) contracted the
+  // level and trend updates differently, and a fit's forecast differed in
+  // the last bit with the caller's keep_season.
   __device__ __forceinline__ void step(float xt, float& s, float& acc, int& n) {
-    const float pred = KIND == 3 ? (lvl + tr) * s : lvl + tr + s;
+    const float lt = lvl + tr;
     if (isfinite(xt)) {
-      const float e = xt - pred;
-      acc += e * e;
+      const float e = KIND == 3 ? __builtin_fmaf(-lt, s, xt) : xt - (lt + s);
+      acc = __builtin_fmaf(e, e, acc);
       ++n;
       const float lprev = lvl;
       if (KIND == 0) {
-        lvl = al * xt + (1.f - al) * lvl;
+        lvl = __builtin_fmaf(al, xt, (1.f - al) * lvl);
       } else if (KIND == 1) {
-        lvl = al * xt + (1.f - al) * (lvl + tr);
-        tr = be * (lvl - lprev) + (1.f - be) * tr;
+        lvl = __builtin_fmaf(al, xt, (1.f - al) * lt);
+        tr = __builtin_fmaf(be, lvl - lprev, (1.f - be) * tr);
       } else if (KIND == 2) {
-        lvl = al * (xt - s) + (1.f - al) * (lvl + tr);
-        tr = be * (lvl - lprev) + (1.f - be) * tr;
-        s = ga * (xt - lvl) + (1.f - ga) * s;
+        lvl = __builtin_fmaf(al, xt - s, (1.f - al) * lt);
+        tr = __builtin_fmaf(be, lvl - lprev, (1.f - be) * tr);
+        s = __builtin_fmaf(ga, xt - lvl, (1.f - ga) * s);
       } else {
         const float ds = fabsf(s) > kDivEps ? xt / s : xt;
-        lvl = al * ds + (1.f - al) * (lvl + tr);
-        tr = be * (lvl - lprev) + (1.f - be) * tr;
+        lvl = __builtin_fmaf(al, ds, (1.f - al) * lt);
+        tr = __builtin_fmaf(be, lvl - lprev, (1.f - be) * tr);
         const float dl = fabsf(lvl) > kDivEps ? xt / lvl : 1.f;
-        s = ga * dl + (1.f - ga) * s;
+        s = __builtin_fmaf(ga, dl, (1.f - ga) * s);
       }
     } else {
-      lvl = lvl + tr;  // missing sample: propagate the forecast
+      lvl = lt;  // missing sample: propagate the forecast
     }
   }
 };
@@ -627,6 +632,19 @@ __global__ __launch_bounds__(256) void hw2_fit_kernel(const float* __restrict__ 
   if (j == 0 && nfin) nfin[row] = nf0 + n;
 }
 
+// The candidate with the smallest finite SSE (the lowest index among equals);
+// a non-finite SSE is never selected, and a row without a finite one keeps
+// candidate 0 (ops/smoothing.py: ref_es_fit).
+__device__ __forceinline__ int best_candidate(const float* __restrict__ sse, int G) {
+  int bg = 0;
+  float bs = isfinite(sse[0]) ? sse[0] : __builtin_inff();
+  for (int g = 1; g < G; ++g) {
+    const float v = sse[g];
+    if (isfinite(v) && v < bs) { bs = v; bg = g; }
+  }
+  return bg;
+}
+
 __global__ __launch_bounds__(256) void hw2_forecast_kernel(const float* __restrict__ sse,
                                                            const float* __restrict__ state,
                                                            const int* __restrict__ nobs,
@@ -638,12 +656,8 @@ __global__ __launch_bounds__(256) void hw2_forecast_kernel(const float* __restri
   if (row >= R) return;
   const int GP = (G + 1) >> 1;
   const int64_t NT = R * GP;
-  int bg = 0;
-  float bs = sse[row * G];
-  for (int g = 1; g < G; ++g) {
-    const float v = sse[row * G + g];
-    if (v < bs || !isfinite(bs)) { bs = v; bg = g; }
-  }
+  const int bg = best_candidate(sse + row * G, G);
+  const float bs = sse[row * G + bg];
   const int64_t pid = row * G + bg;
   const int64_t tid = row * GP + (bg >> 1);
   const float lvl = state[pid * 3 + 0], tr = state[pid * 3 + 1], sc = sscale[row];
@@ -713,12 +727,8 @@ __global__ __launch_bounds__(256) void es_forecast_kernel(const float* __restric
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= R) return;
   const int64_t P = R * G;
-  int bg = 0;
-  float bs = sse[row * G];
-  for (int g = 1; g < G; ++g) {
-    const float v = sse[row * G + g];
-    if (v < bs || !isfinite(bs)) { bs = v; bg = g; }
-  }
+  const int bg = best_candidate(sse + row * G, G);
+  const float bs = sse[row * G + bg];
   const int64_t pid = row * G + bg;
   const float lvl = state[pid * 3 + 0], tr = state[pid * 3 + 1];
   const int tph = (int)state[pid * 3 + 2];

@@ -383,7 +383,9 @@ def ref_es_fit(x: np.ndarray, kind: int, H: int, m: int, grid: np.ndarray, retur
     sse = np.zeros(P, np.float64)
     n = np.zeros(P, np.int64)
     lvl, tr = _run(kind, xr, t0, T, max(m, 1), al, be, ga, lvl, tr, season, sse, n)
-    sse = sse.reshape(R, G)
+    # the SSEs are fp32 outputs: one that overflows fp32 is not finite, and is never selected
+    with np.errstate(over="ignore"):
+        sse = np.where(np.isfinite(sse) & ~np.isfinite(sse.astype(np.float32)), np.inf, sse).reshape(R, G)
     best = np.argmin(np.where(np.isfinite(sse), sse, np.inf), axis=1)
     pid = np.arange(R) * G + best
     fc, sig = _forecast(kind, m, lvl[pid], tr[pid], None if season is None else season[pid], T % max(m, 1),
