@@ -6,7 +6,9 @@
 // of the residuals about a per-phase median profile), K15 (level_shift.hip:
 // the band of the row, or of the segment behind a level shift found over the
 // block medians) and K16 (trend_robust.hip: a line through the block medians,
-// then median and MAD of the detrended row).
+// then median and MAD of the detrended row).  Two headers build on it:
+// fm_seasonal_profile.h (the per-phase stages of K14, K20 and K22) and
+// fm_repeated_median.h (the slope and detrend stages of K16 and K20).
 //
 // Keys: negatives have all bits flipped, non-negatives get the sign bit set.
 // NaN / +-inf become the key 0xFFFFFFFF, which no finite value maps to and

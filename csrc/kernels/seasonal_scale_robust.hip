@@ -4,8 +4,9 @@
 //
 // The span stays in LDS as the keys of fm_radix_select.h from the one HBM read
 // to the end.  Profile, smoothing, forecast and the residual keys |x -
-// profile[phase]| are K14's stages, copied (as K20 copies them), and the first
-// radix selection gives K14's sigma, sigma0.  Then the raw scale of a phase is
+// profile[phase]| are K14's stages (fm_seasonal_profile.h, one text for K14,
+// K20 and this kernel), and the first radix selection gives K14's sigma,
+// sigma0.  Then the raw scale of a phase is
 // the middle of its J residual keys by the same register sorting network
 // (non-negative floats order as their bits, the missing key last); it is
 // smoothed over w phases each side, circular, with fp64 sums, and floored at
@@ -24,94 +25,15 @@
 // forecast, profile and sigma0 are K14's bit for bit, and given the profile the
 // scale is exact up to kappa, which is exact where the middle of u is > 0.
 #include "fm_common.h"
-#include "fm_radix_select.h"
+#include "fm_seasonal_profile.h"
 
 using namespace fm;
 
 namespace {
 
 constexpr int kScaleThreads = 512;
-constexpr int kMaxCycles = 16;                   // foremast_amd/ops/misc.py SEASONAL_MAX_CYCLES mirrors it
-constexpr int kMaxPeriod = kRobustLdsKeys / 4;   // (J + 2) m <= kRobustLdsKeys with J >= 2
 static_assert(sizeof(SelectScratch<kScaleThreads>) + row_key_bytes(kRobustLdsKeys) + sizeof(uint4) <= kLaunchLds,
               "the longest span, a profile and a scale behind it fit a launch");
-
-// compare-exchange: the smaller key first
-__device__ __forceinline__ void cex(unsigned& a, unsigned& b) {
-  const unsigned lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo;
-  b = hi;
-}
-
-// The J keys col[0], col[m], ... of a phase sorted in registers, the missing
-// key last: c = how many are finite, klo / kup their lower and upper middle
-// (the missing key when c == 0).
-__device__ __forceinline__ int phase_middles(const unsigned* col, int m, int J, unsigned& klo, unsigned& kup) {
-  unsigned s[kMaxCycles];
-  int c = 0;
-#pragma unroll
-  for (int j = 0; j < kMaxCycles; ++j) {
-    s[j] = j < J ? col[j * m] : kMissing;
-    c += s[j] != kMissing;
-  }
-#pragma unroll
-  for (int r = 0; r < kMaxCycles; ++r) {
-    if (r < J) {                                             // J rounds sort J keys; the padding is in place
-#pragma unroll
-      for (int i = r & 1; i + 1 < kMaxCycles; i += 2) cex(s[i], s[i + 1]);
-    }
-  }
-  const int il = (c - 1) >> 1, iu = c >> 1;
-  klo = kMissing;
-  kup = kMissing;
-#pragma unroll
-  for (int j = 0; j < kMaxCycles; ++j) {
-    klo = j == il ? s[j] : klo;
-    kup = j == iu ? s[j] : kup;
-  }
-  return c;
-}
-
-// buf[0..m) -> for each of this thread's phases the mean of the finite values
-// within k phases, circular, summed from -k up and divided in fp64; NaN when
-// none is finite.  The caller puts a barrier between this and a write of buf.
-template <int NT, int NP>
-__device__ __forceinline__ void smooth_phases(const float* buf, int m, int k, float (&sm)[NP]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int it = 0; it < NP; ++it) {
-    const int ph = tid + it * NT;
-    sm[it] = quiet_nan();
-    if (ph < m) {
-      double sum = 0.0;
-      int cnt = 0;
-      int q = ph - k;
-      if (q < 0) q += m;
-      for (int d = -k; d <= k; ++d) {
-        const float v = buf[q];
-        if (v == v) {
-          sum += (double)v;
-          ++cnt;
-        }
-        if (++q == m) q = 0;
-      }
-      if (cnt != 0) sm[it] = (float)(sum / (double)cnt);
-    }
-  }
-}
-
-// out[row, h] = buf[h mod m] for h < H
-template <int NT>
-__device__ __forceinline__ void write_wrapped(const float* buf, int m, int H, float* out) {
-  const int tid = threadIdx.x;
-  const int stepm = NT % m;
-  int ph = tid % m;
-  for (int h = tid; h < H; h += NT) {
-    out[h] = buf[ph];
-    ph += stepm;
-    if (ph >= m) ph -= m;
-  }
-}
 
 template <int NT>
 __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* __restrict__ hist, int64_t ld, int T,
@@ -121,7 +43,6 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
                                                                    float* __restrict__ stats /*[R,3]*/,
                                                                    float* __restrict__ profile /*[R,m] or null*/,
                                                                    float* __restrict__ scale /*[R,m] or null*/) {
-  constexpr int kPhases = (kMaxPeriod + NT - 1) / NT;        // most phases a thread takes
   extern __shared__ __attribute__((aligned(16))) uint4 s_keys[];
   __shared__ SelectScratch<NT> s_sc;
   const int tid = threadIdx.x;
@@ -161,58 +82,25 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
   }
 
   // ---- raw profile: per-phase median of the finite samples
-  for (int ph = tid; ph < m; ph += NT) {
-    unsigned klo, kup;
-    const int c = phase_middles(kw + a + ph, m, J, klo, kup);
-    prof[ph] = c == 0 ? qnan : 0.5f * dec_key(klo) + 0.5f * dec_key(kup);
-  }
+  phase_values<NT>(kw + a, m, J, prof, SampleKey{});
   __syncthreads();
 
   // ---- smoothing in place: mean of the finite raw values within k phases, circular
-  {
-    float sm[kPhases];
-    smooth_phases<NT>(prof, m, k, sm);
-    __syncthreads();                                         // every raw value read
-#pragma unroll
-    for (int it = 0; it < kPhases; ++it) {
-      const int ph = tid + it * NT;
-      if (ph < m) {
-        prof[ph] = sm[it];
-        if (profile != nullptr) profile[row * (int64_t)m + ph] = sm[it];
-      }
-    }
-    __syncthreads();
-  }
+  smooth_in_place<NT>(prof, m, k, [&](int ph, float v) {
+    if (profile != nullptr) profile[row * (int64_t)m + ph] = v;
+    return v;
+  });
 
   // ---- forecast: the profile from phase 0 on, wrapped
   write_wrapped<NT>(prof, m, H, forecast + row * ldf);
 
-  // word wd holds span index wd - a: its phase, carried along a thread's quads instead of divided out
-  const int stepm = (4 * NT) % m;
-  int ph_first = (4 * tid - a) % m;                          // (the padding in front of the span: a remainder below zero)
-  if (ph_first < 0) ph_first += m;
-
   // ---- residuals about the profile: keys, fp64 sum, range
   DevTally dev;
-  {
-    int ph0 = ph_first;
-    for (int q = tid; q < nq; q += NT) {
-      const uint4 v = s_keys[q];
-      unsigned e[4] = {v.x, v.y, v.z, v.w};
-      int ph = ph0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (e[j] != kMissing) {
-          e[j] = dev_key(e[j], prof[ph]);
-          dev(e[j]);
-        }
-        if (++ph == m) ph = 0;
-      }
-      s_keys[q] = make_uint4(e[0], e[1], e[2], e[3]);
-      ph0 += stepm;
-      if (ph0 >= m) ph0 -= m;
-    }
-  }
+  sweep_phase_keys<NT>(s_keys, nq, a, m, [&](unsigned key, int ph) {
+    const unsigned d = dev_key(key, prof[ph]);
+    dev(d);
+    return d;
+  });
   const double sum = uniform(block_sum<NT>(dev.sum, s_sc.redd));   // (barriers: the last read of the profile is behind)
   s_sc.clear_bins();                                         // (made visible by the barriers of mad_sigma's range)
 
@@ -225,48 +113,20 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
   }
 
   // ---- raw scale: per-phase middle of the residuals (the keys are their bits)
-  for (int ph = tid; ph < m; ph += NT) {
-    unsigned klo, kup;
-    const int c = phase_middles(kw + a + ph, m, J, klo, kup);
-    scl[ph] = c == 0 ? qnan : 0.5f * __uint_as_float(klo) + 0.5f * __uint_as_float(kup);
-  }
+  phase_values<NT>(kw + a, m, J, scl, DeviationKey{});
   __syncthreads();
 
   // ---- smoothing in place over w phases each side, then the floor
   const float f = __fmul_rn(floor_share, __fdiv_rn(sigma0, 1.4826f));
-  {
-    float sm[kPhases];
-    smooth_phases<NT>(scl, m, w, sm);
-    __syncthreads();                                         // every raw value read
-#pragma unroll
-    for (int it = 0; it < kPhases; ++it) {
-      const int ph = tid + it * NT;
-      if (ph < m) scl[ph] = sm[it] == sm[it] ? fmaxf(sm[it], f) : f;
-    }
-    __syncthreads();
-  }
+  smooth_in_place<NT>(scl, m, w, [&](int, float v) { return v == v ? fmaxf(v, f) : f; });
 
   // ---- the residuals in units of their phase's scale: keys, fp64 sum, range
   DevTally rel;
-  {
-    int ph0 = ph_first;
-    for (int q = tid; q < nq; q += NT) {
-      const uint4 v = s_keys[q];
-      unsigned e[4] = {v.x, v.y, v.z, v.w};
-      int ph = ph0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (e[j] != kMissing) {
-          e[j] = __float_as_uint(__fdiv_rn(__uint_as_float(e[j]), scl[ph]));
-          rel(e[j]);
-        }
-        if (++ph == m) ph = 0;
-      }
-      s_keys[q] = make_uint4(e[0], e[1], e[2], e[3]);
-      ph0 += stepm;
-      if (ph0 >= m) ph0 -= m;
-    }
-  }
+  sweep_phase_keys<NT>(s_keys, nq, a, m, [&](unsigned key, int ph) {
+    const unsigned u = __float_as_uint(__fdiv_rn(__uint_as_float(key), scl[ph]));
+    rel(u);
+    return u;
+  });
   const double sum_u = uniform(block_sum<NT>(rel.sum, s_sc.redd));   // (barriers: keys visible; the bins are still zero)
 
   // ---- kappa: sigma's rule over u
@@ -304,14 +164,10 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
 FM_API int fm_seasonal_scale_robust(const float* hist, int64_t ld, int T, int64_t R, int m, int J, int k, int w,
                                     float floor, int H, float* forecast, float* sigma_h, int64_t ldf, float* stats,
                                     float* profile, float* scale, hipStream_t stream) {
-  if (m < 1 || J < 2 || J > kMaxCycles || (int64_t)(J + 2) * m > kRobustLdsKeys || (int64_t)J * m > T || k < 0 ||
-      2 * (int64_t)k + 1 > m || H < 0 || R > 0x7FFFFFFF || (((uintptr_t)hist) & 3) != 0)
-    return (int)hipErrorInvalidValue;
+  if (!seasonal_args_ok(hist, T, R, m, J, k, H)) return (int)hipErrorInvalidValue;
   if (w < 0 || 2 * (int64_t)w + 1 > m || !(floor > 0.f)) return (int)hipErrorInvalidValue;
   if (R <= 0) return 0;
-  // keys: the span plus up to 3 words in front, in whole quads; behind them
-  // the scale, and the profile when the bin array is too short for it
-  const size_t lds = row_key_bytes(J * m) + (size_t)m * (m > kBins ? 2 : 1) * sizeof(float);
+  const size_t lds = seasonal_lds_bytes(J, m, 1);                // the scale behind the keys always
   if (lds + sizeof(SelectScratch<kScaleThreads>) > kLaunchLds) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL((seasonal_scale_robust_kernel<kScaleThreads>), dim3((unsigned)R), dim3(kScaleThreads), lds,
                      stream, hist, ld, T, m, J, k, w, floor, H, forecast, sigma_h, ldf, stats, profile, scale);

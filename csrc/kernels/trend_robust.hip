@@ -19,10 +19,11 @@
 //
 // Built with contraction limited to single expressions: under the library's
 // -ffp-contract=fast the backend fuses the residual's product and difference
-// across statements and past the pragma in detrend().
+// across statements and past the pragma in detrend() (fm_repeated_median.h,
+// the slope and the detrend sweep, shared with K20).
 // fm-hipcc-flags: -ffp-contract=on
 #include "fm_common.h"
-#include "fm_radix_select.h"
+#include "fm_repeated_median.h"
 
 using namespace fm;
 
@@ -30,25 +31,6 @@ namespace {
 
 constexpr int kTrendThreads = 512;
 constexpr int kMaxBlocks = kBatchBlocks;         // foremast_amd/ops/misc.py SHIFT_MAX_BLOCKS mirrors it
-
-// x - slope * t, the product and the difference each rounded to fp32: never
-// one fused multiply-add
-__device__ __forceinline__ float detrend(float x, float slope, float t) {
-#pragma clang fp contract(off)
-  const float m = __fmul_rn(slope, t);
-  return __fsub_rn(x, m);
-}
-
-template <int NT>
-struct TrendShared {
-  SelectScratch<NT> sc;
-  RowBlocks blk;
-  int q[kMaxBlocks];                                         // block indices of the medians above the quorum
-  float pair[kMaxBlocks][kMaxBlocks];                        // a block's pair slopes, sorted in place
-  float si[kMaxBlocks];                                      // the inner medians
-  int nb;                                                    // blocks above the quorum
-  float slope;
-};
 static_assert(sizeof(TrendShared<kTrendThreads>) + row_key_bytes(kRobustLdsKeys) <= kLaunchLds,
               "the longest row fits a launch");
 
@@ -62,7 +44,6 @@ __global__ __launch_bounds__(NT) void trend_robust_kernel(const float* __restric
   const float* p = hist + row * ld;
   const int a = row_word(p);                                 // LDS word of key 0
   const int nq = row_quads(a, T);
-  float* s_b = s.blk.median;                                 // block medians, compacted below
   const float qnan = quiet_nan();
 
   // ---- the row -> keys; finite count, key range, block counts and medians
@@ -73,49 +54,13 @@ __global__ __launch_bounds__(NT) void trend_robust_kernel(const float* __restric
     return;
   }
 
-  // ---- repeated median of the pair slopes: the inner medians one lane a block
-  if (tid == 0) {                                            // the medians above the quorum, oldest first (B <= j)
-    int B = 0;
-    for (int j = 0; j < J; ++j)
-      if (s_b[j] == s_b[j]) {
-        s_b[B] = s_b[j];
-        s.q[B] = j;
-        ++B;
-      }
-    s.nb = B;
-  }
-  __syncthreads();
-  const int B = s.nb;
-  const bool fit = B >= min_blocks;                          // uniform over the workgroup
-  if (fit && tid < B) {
-    int c = 0;
-    for (int j = 0; j < B; ++j)
-      if (j != tid) s.pair[tid][c++] = __fdiv_rn(s_b[j] - s_b[tid], (float)((s.q[j] - s.q[tid]) * L));
-    s.si[tid] = small_median(s.pair[tid], c);
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float slope = fit ? small_median(s.si, B) : 0.f;
-    if ((__float_as_uint(slope) & 0x7F800000u) == 0x7F800000u) slope = 0.f;   // NaN, +-inf
-    s.slope = slope;
-  }
-  __syncthreads();
-  const float slope = s.slope;
+  // ---- repeated median of the pair slopes of the block medians
+  int B;
+  const float slope = repeated_median_slope<NT>(J, L, min_blocks, &s, B);
 
   // ---- the keys of the residuals in place; their finite count and key range
   RowTally res;
-  for (int q = tid; q < nq; q += NT) {
-    const uint4 v = s_keys[q];
-    unsigned e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (e[j] == kMissing) continue;                        // (the words outside the row are missing)
-      const float t = (float)(4 * q + j - a - (T - 1));
-      e[j] = enc_key(detrend(dec_key(e[j]), slope, t));
-      res(e[j]);
-    }
-    s_keys[q] = make_uint4(e[0], e[1], e[2], e[3]);
-  }
+  detrend_keys<NT>(s_keys, nq, a, T - 1, slope, res);
   n = uniform(block_sum<NT>(res.n, s.sc.redi));
   if (n == 0) {                                              // every residual overflowed
     if (tid == 0) *reinterpret_cast<float4*>(out + row * 4) = make_float4(qnan, qnan, 0.f, slope);

@@ -436,6 +436,31 @@ def seasonal_halfwidth(m: int, smooth: int = 5) -> int:
     return max(0, min(int(smooth), int(m) // 24))
 
 
+def _middle(v, ok, cnt, axis: int = 1):
+    """K13's median rule along ``axis`` over the entries of ``v`` where ``ok``
+    (``cnt`` of them, ``v``'s shape without that axis; a set with none gives a
+    value to be masked).  Missing samples sort last as +inf."""
+    s = np.sort(np.where(ok, v, np.float32(np.inf)), axis=axis)
+    lo = np.expand_dims((np.maximum(cnt, 1) - 1) // 2, axis)
+    up = np.expand_dims(np.maximum(cnt, 1) // 2, axis)
+    half = np.float32(0.5)
+    return (half * np.take_along_axis(s, lo, axis) + half * np.take_along_axis(s, up, axis)).squeeze(axis)
+
+
+def _smooth_circular(raw, k: int):
+    """``raw`` [R, m] f32 -> the mean of the finite ``raw[:, (p + d) % m]``,
+    ``d = -k..k``, summed in that order and divided in fp64, rounded once to
+    fp32; NaN where none is finite."""
+    tot = np.zeros(raw.shape, np.float64)
+    cnt = np.zeros(raw.shape, np.int64)
+    for d in range(-k, k + 1):
+        nb = np.roll(raw, -d, axis=1)               # nb[:, p] = raw[:, (p + d) % m]
+        ok = np.isfinite(nb)
+        tot += np.where(ok, nb, 0).astype(np.float64)
+        cnt += ok
+    return np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan).astype(np.float32)
+
+
 def ref_seasonal_robust(hist, T: int, m: int, H: int, smooth: int = 5):
     """Per-phase median / MAD model of ``hist[r, :T]`` with period ``m`` ->
     (forecast [R, H] f32, sigma [R] f32, n [R] int32, profile [R, m] f32).
@@ -459,28 +484,14 @@ def ref_seasonal_robust(hist, T: int, m: int, H: int, smooth: int = 5):
     span = x[:, T - J * m:T]
     fin = np.isfinite(span)
     n = fin.sum(1).astype(np.int32)
-    half, inf = np.float32(0.5), np.float32(np.inf)
-
-    def middle(v, ok, cnt, axis):                   # missing samples sort last as +inf
-        s = np.sort(np.where(ok, v, inf), axis=axis)
-        lo = np.expand_dims((np.maximum(cnt, 1) - 1) // 2, axis)
-        up = np.expand_dims(np.maximum(cnt, 1) // 2, axis)
-        return (half * np.take_along_axis(s, lo, axis) + half * np.take_along_axis(s, up, axis)).squeeze(axis)
 
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         fin3 = fin.reshape(R, J, m)
         c = fin3.sum(1)
-        raw = np.where(c > 0, middle(span.reshape(R, J, m), fin3, c, 1), np.float32(np.nan)).astype(np.float32)
-        tot = np.zeros((R, m), np.float64)
-        cnt = np.zeros((R, m), np.int64)
-        for d in range(-k, k + 1):
-            nb = np.roll(raw, -d, axis=1)           # nb[:, p] = raw[:, (p + d) % m]
-            ok = np.isfinite(nb)
-            tot += np.where(ok, nb, 0).astype(np.float64)
-            cnt += ok
-        profile = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan).astype(np.float32)
+        raw = np.where(c > 0, _middle(span.reshape(R, J, m), fin3, c, 1), np.float32(np.nan)).astype(np.float32)
+        profile = _smooth_circular(raw, k)
         r = np.abs(span - np.tile(profile, (1, J)))
-        mad = middle(r, fin, n, 1)
+        mad = _middle(r, fin, n)
         mean_r = (np.where(fin, r, 0).astype(np.float64).sum(1) / np.maximum(n, 1)).astype(np.float32)
         sigma = np.where(mad > 0, np.float32(1.4826) * mad, np.float32(1.2533) * mean_r).astype(np.float32)
     sigma[n == 0] = np.nan
@@ -528,16 +539,6 @@ def shift_blocks(T: int, L: int) -> int:
     if L < 1:
         return 0
     return max(0, min(T // L, SHIFT_MAX_BLOCKS))
-
-
-def _middle(v, ok, cnt):
-    """K13's median rule along axis 1 over the entries of ``v`` where ``ok``
-    (``cnt`` of them; rows with none give a value to be masked)."""
-    s = np.sort(np.where(ok, v, np.float32(np.inf)), axis=1)
-    lo = (np.maximum(cnt, 1) - 1) // 2
-    up = np.maximum(cnt, 1) // 2
-    half = np.float32(0.5)
-    return half * np.take_along_axis(s, lo[:, None], 1)[:, 0] + half * np.take_along_axis(s, up[:, None], 1)[:, 0]
 
 
 def shift_candidates(hist, T: int, L: int, min_blocks: int = 2):
@@ -846,31 +847,18 @@ def ref_seasonal_scale_robust(hist, T: int, m: int, H: int, smooth: int = 5, sca
     w = scale_halfwidth(m, scale_smooth)
     span = x[:, T - J * m:T]
     fin = np.isfinite(span)
-    half, inf, nan = np.float32(0.5), np.float32(np.inf), np.float32(np.nan)
-
-    def middle(v, ok, cnt, axis):                   # missing samples sort last as +inf
-        s = np.sort(np.where(ok, v, inf), axis=axis)
-        lo = np.expand_dims((np.maximum(cnt, 1) - 1) // 2, axis)
-        up = np.expand_dims(np.maximum(cnt, 1) // 2, axis)
-        return (half * np.take_along_axis(s, lo, axis) + half * np.take_along_axis(s, up, axis)).squeeze(axis)
+    nan = np.float32(np.nan)
 
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         r = np.abs(span - np.tile(profile, (1, J))).astype(np.float32)
         fin3 = fin.reshape(R, J, m)
         c = fin3.sum(1)
-        raw = np.where(c > 0, middle(r.reshape(R, J, m), fin3, c, 1), nan).astype(np.float32)
-        tot = np.zeros((R, m), np.float64)
-        cnt = np.zeros((R, m), np.int64)
-        for d in range(-w, w + 1):
-            nb = np.roll(raw, -d, axis=1)           # nb[:, p] = raw[:, (p + d) % m]
-            ok = np.isfinite(nb)
-            tot += np.where(ok, nb, 0).astype(np.float64)
-            cnt += ok
-        g = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan).astype(np.float32)
+        raw = np.where(c > 0, _middle(r.reshape(R, J, m), fin3, c, 1), nan).astype(np.float32)
+        g = _smooth_circular(raw, w)
         f = (np.float32(floor) * (sigma0 / np.float32(1.4826)).astype(np.float32)).astype(np.float32)
         gp = np.where(np.isfinite(g), np.maximum(g, f[:, None]), f[:, None]).astype(np.float32)
         u = (r / np.tile(gp, (1, J))).astype(np.float32)
-        mid = middle(u, fin, n, 1)
+        mid = _middle(u, fin, n)
         mean_u = (np.where(fin, u, 0).astype(np.float64).sum(1) / np.maximum(n, 1)).astype(np.float32)
         kappa = np.where(mid > 0, np.float32(1.4826) * mid, np.float32(1.2533) * mean_u).astype(np.float32)
         scale = (kappa[:, None] * gp).astype(np.float32)
