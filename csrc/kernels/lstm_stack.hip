@@ -392,6 +392,10 @@ __global__ __launch_bounds__(64 * H / (8 * RT)) void lstm_stack2_pipe_kernel(
   segment(ic<KS0>{}, accA, W0w, KS0, ks_l0,
           [&](int i) { const uint4 v = lds16(h0r + 16 * (i == 0 ? 0 : i - 1)); return i == 0 ? xt : v; },
           W1w, KS1, KH, KH + 1, no_cell);
+  // every wave has read h0_{-1} before any wave's cells overwrite it with h0_0
+  // (the image is single-buffered; without this a fast wave's h0_0 reached a
+  // slow wave's L0(0) k-steps: a few 1e-2 in h, timing dependent)
+  lds_barrier();
 #pragma unroll
   for (int q = 0; q < NC; ++q) cell_q(q, accA, c0, h0w, false);
   lds_barrier();
