@@ -15,6 +15,7 @@
 // global memory.  The contract is foremast_amd/ops/misc.py
 // ref_quantile_robust_stats.
 #include "fm_common.h"
+#include "fm_quantile_row.h"   // quantile_row_stats
 #include "fm_radix_select.h"
 
 using namespace fm;
@@ -25,51 +26,6 @@ constexpr int kQuantileThreads = 512;
 
 static_assert(sizeof(SelectScratch<kQuantileThreads>) + 16 * sizeof(unsigned) + row_key_bytes(kRobustLdsKeys) <=
                       kLaunchLds, "the longest LDS row fits a launch");
-
-// One-sided deviations about the centre: what the fallback of a side sums.
-struct SideTally {
-  float c;
-  double up = 0.0, lo = 0.0;
-  int nup = 0, nlo = 0;
-  __device__ __forceinline__ void operator()(unsigned k) {
-    if (k != kMissing) {
-      const float x = dec_key(k);
-      if (x >= c) {
-        up += (double)(x - c);
-        ++nup;
-      }
-      if (x <= c) {
-        lo += (double)(c - x);
-        ++nlo;
-      }
-    }
-  }
-};
-
-// (centre, sigma_lo, sigma_up) of the n >= 1 finite keys of rk, all within r;
-// the same in every thread.
-template <int NT, class Keys>
-__device__ __forceinline__ void quantile_sigmas(const Keys& rk, unsigned n, KeyRange r, double p, float iz,
-                                                SelectScratch<NT>* sc, unsigned* sel, float& center, float& sigma_lo,
-                                                float& sigma_up) {
-  unsigned kup = (unsigned)ceil(p * (double)(n - 1u));
-  if (kup > n - 1u) kup = n - 1u;
-  const unsigned rank[3] = {(n - 1u) >> 1, kup, (n - 1u) - kup};
-  unsigned key[3], resid[3], cnt[3];
-  radix_select_ranks(rk, r, rank, n, sc, sel, key, resid, cnt);
-  center = mid_value(key[0], upper_middle(rk, key[0], n, resid[0], cnt[0], sc));
-  const float d_up = dec_key(key[1]) - center, d_lo = center - dec_key(key[2]);
-  sigma_up = d_up * iz;
-  sigma_lo = d_lo * iz;
-  if (uniform((int)(!(d_up > 0.f) || !(d_lo > 0.f)))) {        // (the same in every thread)
-    SideTally t{center};
-    rk.sweep(t);
-    const double su = block_sum<NT>(t.up, sc->redd), sl = block_sum<NT>(t.lo, sc->redd);
-    const int nu = block_sum<NT>(t.nup, sc->redi), nl = block_sum<NT>(t.nlo, sc->redi);
-    if (!(d_up > 0.f)) sigma_up = 1.2533f * (float)(su / (double)(nu > 0 ? nu : 1));
-    if (!(d_lo > 0.f)) sigma_lo = 1.2533f * (float)(sl / (double)(nl > 0 ? nl : 1));
-  }
-}
 
 template <int NT, bool LDS>
 __global__ __launch_bounds__(NT) void quantile_robust_kernel(const float* __restrict__ hist, int64_t ld, int T,
@@ -83,24 +39,8 @@ __global__ __launch_bounds__(NT) void quantile_robust_kernel(const float* __rest
   const float* prow = hist + row * ld;
   s_sc.clear_bins();
   float center, sigma_lo, sigma_up;
-  center = sigma_lo = sigma_up = quiet_nan();
   int n;
-  RowTally t;
-  if constexpr (LDS) {
-    const int a = row_word(prow);
-    load_row_keys<NT>(prow, T, a, s_keys, t);
-    n = uniform(block_sum<NT>(t.n, s_sc.redi));               // (barriers: keys and bins visible)
-    if (n != 0) {                                             // (the same in every thread)
-      LdsRow<NT> rk{s_keys, row_quads(a, T)};
-      quantile_sigmas(rk, (unsigned)n, block_range(t.range, &s_sc), p, iz, &s_sc, s_sel, center, sigma_lo, sigma_up);
-    }
-  } else {
-    GlobalRow<NT> rk{prow, T};
-    rk.sweep(t);
-    n = uniform(block_sum<NT>(t.n, s_sc.redi));
-    if (n != 0)
-      quantile_sigmas(rk, (unsigned)n, block_range(t.range, &s_sc), p, iz, &s_sc, s_sel, center, sigma_lo, sigma_up);
-  }
+  quantile_row_stats<NT, LDS>(prow, T, p, iz, s_keys, &s_sc, s_sel, center, sigma_lo, sigma_up, n);
   if (tid == 0) {
     out[row * 4 + 0] = center;
     out[row * 4 + 1] = sigma_lo;

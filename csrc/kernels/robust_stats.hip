@@ -15,6 +15,7 @@
 // static history is selected once and costs 12 bytes per tick afterwards.
 #include "fm_common.h"
 #include "fm_radix_select.h"
+#include "fm_robust_row.h"   // tallied_stats, robust_row_stats
 #include "fm_row_stats.h"
 
 using namespace fm;
@@ -30,40 +31,6 @@ constexpr int kRobustScanBlocks = 512;
 // scan pass (K13 has the scratch alone)
 static_assert(sizeof(SelectScratch<kRobustThreads>) + (kRobustThreads + 1) * sizeof(int) +
                       row_key_bytes(kRobustLdsKeys) <= kLaunchLds, "the longest LDS row fits a launch");
-
-// (centre, sigma, finite count) of the keys rk makes of a row, tallied into t
-// on the way; the same in every thread.
-template <int NT, class Keys>
-__device__ __forceinline__ void tallied_stats(Keys& rk, const RowTally& t, SelectScratch<NT>* sc, float& center,
-                                              float& sigma, int& nfin) {
-  nfin = uniform(block_sum<NT>(t.n, sc->redi));               // (barriers: keys and bins visible)
-  if (nfin == 0) {                                            // (the same in every thread)
-    center = sigma = quiet_nan();
-    return;
-  }
-  median_sigma(rk, (unsigned)nfin, block_range(t.range, sc), sc, center, sigma);
-}
-
-// The statistics of p[0..T).  The bins are zero on entry and on return; keys
-// holds row_key_bytes(T) when LDS.  Every thread of the workgroup calls it; all
-// branches around barriers are workgroup-uniform, so it can be called for one
-// row after another: the last reads of keys and scratch sit in front of a
-// barrier that every thread passes before the next row's first write to them.
-template <int NT, bool LDS>
-__device__ __forceinline__ void robust_row_stats(const float* __restrict__ p, int T, uint4* keys,
-                                                 SelectScratch<NT>* sc, float& center, float& sigma, int& nfin) {
-  RowTally t;
-  if constexpr (LDS) {
-    const int a = row_word(p);
-    load_row_keys<NT>(p, T, a, keys, t);
-    LdsRow<NT> rk{keys, row_quads(a, T)};
-    tallied_stats(rk, t, sc, center, sigma, nfin);
-  } else {
-    GlobalRow<NT> rk{p, T};
-    rk.sweep(t);
-    tallied_stats(rk, t, sc, center, sigma, nfin);
-  }
-}
 
 template <int NT, bool LDS>
 __global__ __launch_bounds__(NT) void robust_stats_kernel(const float* __restrict__ hist, int64_t ld, int T, int64_t R,

@@ -92,6 +92,7 @@ class FastPath(PlanMixin, FetchMixin, ArraysMixin, ModelsMixin, FinishMixin):
         self._es_plan = None      # (keys, cache lookup) a declined fused cycle hands to es_forecast
         self.fused_steps = 0
         self.robust_ticks = 0                       # static robust_moving_average_all groups ticked resident
+        self.band_ticks = 0                         # static band-model groups with quantile_robust ticked resident (K25)
         self._routes0 = _canary_ops.route_rows()    # the process-wide pairwise route counts when this path began
         self.fused_declined: dict[str, int] = {}   # why a forecasting group's cycle took the op-by-op path
         self._col: dict = {}      # column-wise fetched windows of sliding groups (consumed by _arrays)

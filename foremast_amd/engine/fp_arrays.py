@@ -48,8 +48,13 @@ class ArraysMixin:
         self._last_groups = g
         return g
 
-    def _scorer(self, aliases: tuple, model: str = "moving_average_all") -> CanaryScorer:
+    def _scorer(self, aliases: tuple, model: str = "moving_average_all", codes=None,
+                tail_z: float = 2.0) -> CanaryScorer:
+        """``codes`` and ``tail_z`` are ``band_mix``'s: a scorer is made again
+        when the configuration gave either another value."""
         sc = self.scorers.get((aliases, model))
+        if sc is not None and codes is not None and (sc.codes != tuple(codes) or sc.tail_z != tail_z):
+            sc = None
         if sc is None:
             # XCD-balanced history ranges off in the brain: one scorer serves
             # every group of an alias set, so a split learned on one group's
@@ -58,7 +63,8 @@ class ArraysMixin:
             # vs 26.3-28.3 without (profiles/front_xcd_fraction_ab_r6.jsonl)
             sc = self.scorers[(aliases, model)] = CanaryScorer(
                 list(aliases), self.b.cfg, device=self.b.device,
-                xcd_balance=os.environ.get("FM_BRAIN_XCD_BALANCE", "0") == "1", model=model)
+                xcd_balance=os.environ.get("FM_BRAIN_XCD_BALANCE", "0") == "1", model=model, codes=codes,
+                tail_z=tail_z)
         if len(sc._out) > 8:
             sc._out.clear()
         return sc
@@ -382,7 +388,15 @@ class ArraysMixin:
         store = self.sliding if p0.sliding else self.static
         ga = self._arrays(works, key if key is not None else ("adhoc",) + p0.group)
         model = "moving_average_all"
-        if any(a != "moving_average_all" for a in p0.algos):
+        band = self._band_route(p0, M, store)
+        if band is not None:
+            # a static group judged by the static band models, quantile_robust
+            # among them, alone or next to a per-metric default: every model is
+            # four numbers per history row, so the group ticks like the
+            # mean/std one, over the store's band-record cache (K25)
+            model = "band_mix"
+            self.band_ticks += 1
+        elif any(a != "moving_average_all" for a in p0.algos):
             # a static group judged by robust_moving_average_all alone ticks like
             # the mean/std one, over the store's robust row-statistics cache: a
             # canary job's history is written once, so its median and MAD are
@@ -400,8 +414,8 @@ class ArraysMixin:
             store.used[ga.rowmap] = self.cycle
             ga.marked = self.cycle
         n = ga.cur.shape[1]
-        o = self._scorer(p0.aliases, model).score_resident(store.view_until(ga.hist_end), ga.rm_d, ga.cur_dev,
-                                                           ga.base_d)
+        sc = self._scorer(p0.aliases, model) if band is None else self._scorer(p0.aliases, model, *band)
+        o = sc.score_resident(store.view_until(ga.hist_end), ga.rm_d, ga.cur_dev, ga.base_d)
         dec = o.decide
         if dev.type == "cuda":
             cap = max(1024, min(R * n, 1 << 16))
@@ -426,6 +440,23 @@ class ArraysMixin:
         return {"works": works, "M": M, "ga": ga, "cur": ga.cur, "cur_t": ga.cur_t, "cur_len": ga.cur_len,
                 "packed": packed, "stats": stats, "count": count, "anom": idx, "hist_rows": ga.rowmap,
                 "store": store}
+
+    def _band_route(self, p0, M: int, store):
+        """(codes, tail_z) when the group ticks through ``band_mix``, else None:
+        a static group whose algorithms are all static band models with
+        ``quantile_robust`` among them (a mean + robust mix keeps the op-by-op
+        route), up to 16 metrics, a view K25 takes, and ``FM_BAND_TICK`` not
+        ``0`` / ``false``."""
+        from ..ops import misc as MI
+        algos = p0.algos
+        if (p0.sliding or "quantile_robust" not in algos or any(a not in MI.BAND_CODES for a in algos)
+                or M > MI.BAND_MAX_METRICS or os.environ.get("FM_BAND_TICK", "1") in ("0", "false")):
+            return None
+        codes = tuple(MI.BAND_CODES[a] for a in algos)
+        T = store.view().T
+        if T >= (1 << MI.BAND_TAG_SHIFT) or (0 in codes and T > MI.BAND_MEAN_MAX_T):
+            return None
+        return codes, self.b._quantile_args("quantile_robust")["tail_z"]
 
     def _compact(self, dec, cur_d, R: int, n: int, cap: int):
         dev = cur_d.device

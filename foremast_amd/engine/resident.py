@@ -68,14 +68,22 @@ class RowStatsCache:
 
     ``dirty`` is the host's count of words cleared since the last tick.  It
     only shapes that tick's launch (:meth:`expect_miss`); what is recomputed
-    is decided on the device, word by word."""
+    is decided on the device, word by word.
 
-    def __init__(self, rows: int, device):
+    ``width=4`` is the cache of the static band models' records (K25,
+    ``ops.misc.band_stats_cached``): (centre, sigma_lo, sigma_up, n) per row,
+    16-byte entries, the word a tag of model and view length.  Such a cache
+    also remembers the ``quantile_robust`` tail parameter its entries were made
+    with (:meth:`rekey`)."""
+
+    def __init__(self, rows: int, device, width: int = 3):
         self.device = torch.device(device)
-        self.stats = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        self.width = int(width)
+        self.stats = torch.empty((rows, self.width), dtype=torch.float32, device=self.device)
         self.valid = torch.zeros((rows,), dtype=torch.int32, device=self.device)
         self.dirty = rows
         self.T = 0                                  # view length of the last tick
+        self.z0: float | None = None                # width 4: tail parameter of the quantile_robust entries
 
     def __len__(self) -> int:
         return self.valid.numel()
@@ -85,7 +93,7 @@ class RowStatsCache:
         n = len(self)
         if rows <= n:
             return
-        stats = torch.empty((rows, 3), dtype=torch.float32, device=self.device)
+        stats = torch.empty((rows, self.width), dtype=torch.float32, device=self.device)
         valid = torch.zeros((rows,), dtype=torch.int32, device=self.device)
         stats[:n].copy_(self.stats)
         valid[:n].copy_(self.valid)
@@ -107,6 +115,16 @@ class RowStatsCache:
             self.valid.zero_()
         self.dirty = max(self.dirty, len(self))
 
+    def rekey(self, z0: float) -> None:
+        """The next tick makes its ``quantile_robust`` records with the tail
+        parameter ``z0``: entries made with another one are stale, and the tag
+        does not tell them apart, so everything is invalidated (on the current
+        stream)."""
+        z0 = float(z0)
+        if self.z0 is not None and self.z0 != z0:
+            self.invalidate()
+        self.z0 = z0
+
     def expect_miss(self, T: int, rows: int) -> bool:
         """Whether the tick over ``rows`` rows of a view of length ``T`` should
         be shaped for streaming history (many misses) rather than for hits."""
@@ -121,12 +139,14 @@ class HistView:
     """What a scoring launch needs: the buffer view (16-B aligned rows), its
     leading dimension, the logical history length and the row map; for a
     static store also the row-statistics caches of the buffer: ``cache``
-    holds (mean, std, n), ``rcache`` the robust (median, sigma, n)."""
+    holds (mean, std, n), ``rcache`` the robust (median, sigma, n), ``bcache``
+    the static band models' records (centre, sigma_lo, sigma_up, n)."""
     hist: torch.Tensor        # [rows, >= T] view into the resident buffer
     ld: int
     T: int
     cache: RowStatsCache | None = None
     rcache: RowStatsCache | None = None
+    bcache: RowStatsCache | None = None
 
 
 class ResidentHistory:
@@ -147,6 +167,8 @@ class ResidentHistory:
         # of its own, with its own view length and dirty count -- a fleet may
         # tick some groups with each model
         self.rcache = None if sliding else RowStatsCache(0, self.device)
+        # the band records of a per-metric mix of the static band models (K25)
+        self.bcache = None if sliding else RowStatsCache(0, self.device, width=4)
         self.slot: dict = {}
         self.free: list[int] = []
         self.last_t = np.zeros(0, np.float64)       # time of each row's newest sample (-inf: none)
@@ -193,6 +215,8 @@ class ResidentHistory:
             self.cache.grow(new_cap)
         if self.rcache is not None:
             self.rcache.grow(new_cap)
+        if self.bcache is not None:
+            self.bcache.grow(new_cap)
         self.free.extend(range(new_cap - 1, cap - 1, -1))
         self.last_t = np.concatenate([self.last_t, np.full(new_cap - cap, -np.inf)])
         self.nlen = np.concatenate([self.nlen, np.zeros(new_cap - cap, np.int64)])
@@ -323,10 +347,11 @@ class ResidentHistory:
             idx = idx.to(self.device)
             self.cache.touch(idx)
             self.rcache.touch(idx)
+            self.bcache.touch(idx)
 
     def view(self) -> HistView:
         if not self.sliding:
-            return HistView(self.buf, self.width, max(1, self.max_len), self.cache, self.rcache)
+            return HistView(self.buf, self.width, max(1, self.max_len), self.cache, self.rcache, self.bcache)
         vs = max(0, self.ws // 4 * 4)
         return HistView(self.buf[:, vs:], self.width, self.e - vs)
 

@@ -41,10 +41,11 @@ class CanaryOutputs:
     effect_counts: torch.Tensor | None = None   # [R, 2] int32 #{d > 0}, #{d < 0}
     effect_passed: torch.Tensor | None = None   # [R] int8
     pvals_gated: torch.Tensor | None = None     # [R, 6] what the decision reads: pvals, NaN where the gate failed
+    bs: torch.Tensor | None = None              # [R, 4] band records (centre, sigma_lo, sigma_up, n): model="band_mix"
 
 
 MODES = ("front", "fused", "overlap", "serial")
-MODELS = ("moving_average_all", "robust_moving_average_all")
+MODELS = ("moving_average_all", "robust_moving_average_all", "band_mix")
 
 
 class _BoundHist:
@@ -103,7 +104,8 @@ class CanaryScorer:
                  mode: str | None = None, hist_blocks: int = 0, pw_blocks: int = 0, pw_cap_rows: int = 32,
                  front_wgs: tuple[float, float] | None = None, front_queue: bool = True,
                  xcd_balance: bool | None = None, hist_cache: bool = True,
-                 front_hot_wgs: tuple[float, float] | None = None, model: str = "moving_average_all"):
+                 front_hot_wgs: tuple[float, float] | None = None, model: str = "moving_average_all",
+                 codes=None, tail_z: float = 2.0):
         """``model``: what the history statistics ``hs [R, 3]`` are --
         ``moving_average_all`` (mean, std, n) or ``robust_moving_average_all``
         (median, 1.4826 MAD or its mean-deviation fallback, n: K13 / K18).  The
@@ -111,6 +113,15 @@ class CanaryScorer:
         history gate and service reduce are the same code for both.  The
         robust model ticks through ``score`` and ``score_resident`` only (no
         graph capture, split launchers or ``mode="fused"``).
+
+        ``band_mix`` is a per-metric mix of the static band models: ``codes``
+        names each metric's model (``ops.misc.BAND_CODES``: 0 mean / std, 1
+        median / MAD, 2 ``quantile_robust`` with the tail parameter
+        ``tail_z``), the statistics are band records ``bs [R, 4]`` = (centre,
+        sigma_lo, sigma_up, n) from K25 (``fm_band_stats_cached``, a resident
+        store's ``bcache``) and the decision takes a sigma per side
+        (``fm_decide_services_2s``).  At most 16 metrics; it ticks through
+        ``score`` and ``score_resident`` only, as the robust model.
 
         ``hist_cache`` (and env ``FM_HIST_CACHE``, ``0`` = off): keep each
         history row's (mean, std, n) across ticks where the history has an
@@ -126,8 +137,23 @@ class CanaryScorer:
             raise ValueError(f"model must be one of {MODELS}")
         self.model = model
         self.robust = model == "robust_moving_average_all"
-        if self.robust and self.mode == "fused":
-            raise ValueError("mode='fused' reads mean/std off the row image: not available for the robust model")
+        self.band = model == "band_mix"
+        if (self.robust or self.band) and self.mode == "fused":
+            raise ValueError(f"mode='fused' reads mean/std off the row image: not available for model={model!r}")
+        if self.band:
+            from ..ops import misc as MI
+            if codes is None or len(codes) != len(aliases) or any(int(c) not in (0, 1, 2) for c in codes):
+                raise ValueError("model='band_mix' takes codes, one of 0, 1, 2 (ops.misc.BAND_CODES) per metric")
+            if len(aliases) > MI.BAND_MAX_METRICS:
+                raise ValueError(f"model='band_mix' supports up to {MI.BAND_MAX_METRICS} metrics per service")
+            self.codes = tuple(int(c) for c in codes)
+            self.tail_z = MI.quantile_tail_z(tail_z)
+            self.code_mask = 0
+            for c in self.codes:
+                self.code_mask |= 1 << c
+            self._codes_d = torch.tensor(self.codes, dtype=torch.int32, device=torch.device(device))
+        elif codes is not None:
+            raise ValueError("codes belong to model='band_mix'")
         self.gate = C.EffectGate.from_config(cfg or BrainConfig())
         if self.gate.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the pairwise effect gate (ML_PAIRWISE_MIN_EFFECT / "
@@ -217,6 +243,8 @@ class CanaryScorer:
                 e = C.alloc_effect(R, d)
                 o = self._out[key]
                 o.effect, o.effect_counts, o.effect_passed, o.pvals_gated = e.effect, e.counts, e.passed, e.pvals_gated
+            if self.band:
+                self._out[key].bs = torch.empty((R, 4), dtype=torch.float32, device=d)
         return self._out[key]
 
     # -- effect-size gate (K19) ----------------------------------------------
@@ -265,6 +293,8 @@ class CanaryScorer:
         R = cur.shape[0]
         if self.robust:
             return self._score_robust(hist, base, cur, n_hist, packed_out)
+        if self.band:
+            return self._score_band(hist, base, cur, n_hist, packed_out)
         if not cur.is_cuda:
             if base is not None and base.shape[1] > 0:
                 pv, ps, df = C.pairwise_tests(cur, base, self.pcfg)
@@ -349,6 +379,8 @@ class CanaryScorer:
         if not cur.is_cuda:
             if self.robust and self.hist_cache and getattr(hview, "rcache", None) is not None:
                 self._store_caches.add(hview.rcache)       # (invalidate_history reaches it on either device)
+            if self.band and self.hist_cache and getattr(hview, "bcache", None) is not None:
+                self._store_caches.add(hview.bcache)
             hist = hview.hist.index_select(0, rowmap.to(torch.int64))
             return self.score(hist, base if has_base else None, cur, hview.T)
         from ..ops._lib import LIB, ptr, stream_of
@@ -361,6 +393,8 @@ class CanaryScorer:
         n = cur.shape[1] + (base.shape[1] if has_base else 0)
         if self.robust:
             return self._resident_robust(hview, rowmap, cur, base if has_base else None, o, st)
+        if self.band:
+            return self._resident_band(hview, rowmap, cur, base if has_base else None, o, st)
         # a static store's rows keep their statistics between its writes
         cache = getattr(hview, "cache", None) if self.hist_cache else None
         miss = True
@@ -483,9 +517,77 @@ class CanaryScorer:
             cache.ticked(T)
         return o
 
+    # -- band_mix: a per-metric mix of the static band models ------------------
+    def _score_band(self, hist, base, cur, n_hist, packed_out) -> CanaryOutputs:
+        """``score`` of the mix: K25 without a cache (the tensor has no owner)
+        into ``bs``, the pairwise tests, the gate, the two-sigma decision."""
+        from ..ops import misc as MI
+        R = cur.shape[0]
+        T = hist.shape[1] if n_hist is None else int(n_hist)
+        has_base = base is not None and base.shape[1] > 0
+        if not cur.is_cuda:
+            if has_base:
+                pv, ps, df = C.pairwise_tests(cur, base, self.pcfg)
+            else:
+                pv = torch.full((R, C.N_TESTS), float("nan"))
+                ps = pv.clone()
+                df = torch.zeros((R,), dtype=torch.int8)
+            df, eff = self._gate_cpu(cur, base if has_base else None, pv, df)
+            rec, _ = MI.ref_band_stats(hist.numpy(), T, self.codes, self.tail_z)
+            dec, packed, _ = C.ref_decide_services_2s(rec, cur.numpy(), self.M, self.thr.numpy(), self.bound.numpy(),
+                                                      self.minlb.numpy(), self.cfg.pairwise_threshold_factor,
+                                                      self.cfg.min_historical_points, diff=df.numpy())
+            return self._with_effect(CanaryOutputs(pv, ps, df, None, dec, packed, bs=torch.from_numpy(rec)), eff)
+        C.check(hist.dim() == 2 and hist.dtype == torch.float32 and (hist.stride(1) == 1 or hist.shape[1] <= 1)
+                and hist.shape[0] == R and 0 <= T <= hist.shape[1],
+                "history must be fp32 [R, >= T] with unit column stride")
+        o = self._alloc(R, cur.shape[1])
+        if packed_out is not None:
+            C.check(packed_out.shape == o.packed.shape and packed_out.is_contiguous()
+                    and packed_out.dtype == torch.float32, "packed_out must be a contiguous fp32 [S, 4] tensor")
+            o = dataclasses.replace(o, packed=packed_out)
+        MI.band_stats_cached(hist, T, None, self.codes, None, self.tail_z, out=o.bs, codes_dev=self._codes_d)
+        if has_base:
+            self._pairwise_wide(cur, base, o)
+        o = self._gate_into(cur, base if has_base else None, o)
+        self._decide_services(cur, o, has_base)
+        return o
+
+    def _resident_band(self, hview, rowmap, cur, base, o: CanaryOutputs, st: int) -> CanaryOutputs:
+        """``score_resident`` of the mix on the GPU: K25 fills ``bs`` from the
+        store's band-record cache (computing only the rows written since their
+        last tick under this model and view length), then the pairwise kernels,
+        the gate and the two-sigma decision, all on the stream of ``cur``."""
+        from ..ops import misc as MI
+        from ..ops._lib import LIB, ptr
+        R = cur.shape[0]
+        T = hview.T
+        C.check(T < (1 << MI.BAND_TAG_SHIFT) and (not (self.code_mask & 1) or T <= MI.BAND_MEAN_MAX_T),
+                "the view is longer than the band-record kernel takes")
+        cache = getattr(hview, "bcache", None) if self.hist_cache else None
+        miss = True
+        if cache is not None:
+            self._store_caches.add(cache)
+            cache.rekey(self.tail_z)
+            miss = cache.expect_miss(T, R)
+        c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
+        p, iz = MI.quantile_tail_params(self.tail_z)
+        # streaming: a workgroup per row; hits: two workgroups per CU, as K18
+        LIB.call("fm_band_stats_cached", ptr(hview.hist), hview.ld, T, R, self.M, ptr(self._codes_d), self.code_mask,
+                 p, float(iz), ptr(o.bs), ptr(rowmap), c_stats, c_valid, int(miss), 0 if miss else 2 * self._cus, st)
+        if base is not None:
+            self._pairwise_wide(cur, base, o)
+        o = self._gate_into(cur, base, o)
+        self._decide_services(cur, o, base is not None)
+        if cache is not None:
+            cache.ticked(T)
+        return o
+
     def _no_robust(self, what: str) -> None:
-        if self.robust:
-            raise ValueError(f"{what} is not available for model='robust_moving_average_all'")
+        """The forms that bind mean / std history (graph capture, the front
+        launch alone, the split launchers) take ``moving_average_all`` only."""
+        if self.robust or self.band:
+            raise ValueError(f"{what} is not available for model={self.model!r}")
 
     def _front_grid(self, miss: bool) -> tuple[int, int]:
         """(pairwise, history) workgroups of a front launch: ``front_wgs`` per
@@ -525,7 +627,8 @@ class CanaryScorer:
         """Drop every cached row statistic this scorer can reach: the caches of
         the tensors bound by ``split_launchers`` / ``capture_front`` and of the
         resident stores it has ticked (a robust scorer: the stores' robust
-        caches).  The next tick of each recomputes all rows.
+        caches; a ``band_mix`` scorer: their band-record caches).  The next
+        tick of each recomputes all rows.
 
         The caches see a write in two ways only: a ``ResidentHistory`` clears
         the rows it writes itself, and a bound tensor is watched through
@@ -608,7 +711,8 @@ class CanaryScorer:
         (a workgroup per service, a wave per metric row)."""
         from ..ops._lib import LIB, ptr, stream_of
         C.check(self.M <= 16, "overlap/fused ticks support up to 16 metrics per service (use mode='serial')")
-        LIB.call("fm_decide_services", *self._decide_call_args(cur, o, has_base), stream_of(cur))
+        LIB.call("fm_decide_services_2s" if self.band else "fm_decide_services",
+                 *self._decide_call_args(cur, o, has_base), stream_of(cur))
 
     def _decide_call_args(self, cur, o: CanaryOutputs, has_base: bool) -> tuple:
         from ..ops._lib import ptr
@@ -616,7 +720,7 @@ class CanaryScorer:
         d = o.decide
         # with the effect gate on, the decision combines the gated copy (NaN rows: "no test applies")
         pv = o.pvals if o.pvals_gated is None else o.pvals_gated
-        return (ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1], cur.shape[0] // self.M,
+        return (ptr(o.bs if self.band else o.hs), ptr(cur), cur.stride(0), cur.shape[1], cur.shape[0] // self.M,
                 self.M, ptr(self.thr), ptr(self.bound), ptr(self.minlb), float(self.cfg.pairwise_threshold_factor),
                 ptr(pv) if has_base else None, mask, anyc, float(self.pcfg.p_threshold),
                 int(self.cfg.min_historical_points), ptr(d.stats), ptr(d.flags), d.flags.shape[1], ptr(d.count),

@@ -120,6 +120,9 @@ _SIGS: dict[str, list] = {
     "fm_band_decide_2s": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                           c_void_p],
+    # hist ld T R M codes code_mask p inv_z0 out rowmap cache valid expect_miss blocks stream (K25)
+    "fm_band_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_int, ctypes.c_double, c_float,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],
     # x ld L R cands (host int64 [C, 6]) C zcap margin score n nx choice stream
     "fm_holdout_score": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p],
@@ -133,6 +136,10 @@ _SIGS: dict[str, list] = {
     "fm_decide_services": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_float,
                            c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                            c_void_p, c_void_p, c_void_p, c_void_p],
+    # fm_decide_services with bs [R, 4] band records in place of hs [R, 3]
+    "fm_decide_services_2s": [c_void_p, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_float,
+                              c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_pvalues_only": [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "fm_pairwise_suff": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p],
     "fm_pairwise_suff_v": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_void_p],

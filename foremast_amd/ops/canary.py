@@ -4,7 +4,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
 (``pairwise.hip``, ``pairwise_wide.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
-``decide.hip``, ``synth.hip``);
+``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
 numerics oracle for tests).
@@ -415,6 +415,96 @@ def service_reduce(count: torch.Tensor, score: torch.Tensor, valid: torch.Tensor
     packed = out if out is not None else torch.empty((S, 4), dtype=torch.float32, device=count.device)
     LIB.call("fm_service_reduce", ptr(count), ptr(score), ptr(valid), S, M, ptr(packed), stream_of(count))
     return packed
+
+
+def combine_pvalues(pvals, test_mask: int, combine_any: int, p_thr: float) -> np.ndarray:
+    """"Distribution differs" per row as the decision kernels combine the
+    p-values they are given (fp32 [R, N_TESTS], NaN = test not applicable):
+    among the tests of ``test_mask`` that apply, any (``combine_any``) or all
+    below ``float32(p_thr)``; no applicable test: 0.  -> int8 [R]."""
+    P = np.asarray(pvals, np.float32)
+    sel = np.array([(int(test_mask) >> i) & 1 for i in range(N_TESTS)], dtype=bool)
+    app = ~np.isnan(P[:, sel])
+    sig = app & (np.nan_to_num(P[:, sel].astype(np.float64), nan=1.0) < float(np.float32(p_thr)))
+    na, ns = app.sum(1), sig.sum(1)
+    return np.where(na > 0, (ns > 0) if combine_any else (ns == na), False).astype(np.int8)
+
+
+def ref_decide_services_2s(bs, cur, M: int, thr, bound, minlb, pair_factor: float = 0.8, min_hist: int = 1,
+                           pvals=None, test_mask: int = (1 << N_TESTS) - 1, combine_any: int = 0,
+                           p_thr: float = 0.05, diff=None):
+    """The contract of :func:`decide_services_2s` on numpy arrays, composed of
+    the references that exist: :func:`combine_pvalues`, the two-sigma band
+    decision ``ops.smoothing.ref_band_decide_2s`` on the band records ``bs
+    [R, 4]`` (centre, sigma_lo, sigma_up, n), the history gate ``n >= min_hist
+    and n > 0`` (a row without enough history flags and scores nothing) and
+    the service reduce.  ``diff`` (int8 [R]) stands in for the combined
+    p-values when the caller has it.  -> (DecideResult with stats = centre,
+    sigma_up, upper, lower; packed [S, 4]; diff int8 [R] or None)."""
+    from .smoothing import ref_band_decide_2s
+    bs = np.asarray(bs, np.float32)
+    x = np.asarray(cur, np.float32)
+    if diff is not None:
+        diff = np.asarray(diff, np.int8)
+    elif pvals is not None:
+        diff = combine_pvalues(pvals, test_mask, combine_any, p_thr)
+    c, slo, sup = bs[:, 0], bs[:, 1], bs[:, 2]
+    with np.errstate(invalid="ignore", over="ignore"):
+        up, lo, flags, cnt, sc = ref_band_decide_2s(x, c[:, None], slo, sup, M, np.asarray(thr, np.float32),
+                                                    np.asarray(bound), np.asarray(minlb, np.float32), diff,
+                                                    pair_factor)
+        n = bs[:, 3].astype(np.int64)
+    has = torch.from_numpy((n >= min_hist) & (n > 0))
+    cnt = torch.where(has, cnt, torch.zeros_like(cnt))
+    sc = torch.where(has, sc, torch.zeros_like(sc))
+    flags = torch.where(has[:, None], flags, torch.zeros_like(flags))
+    valid = has.to(torch.int32) | (torch.from_numpy(np.isfinite(x).any(1)).to(torch.int32) << 1)
+    stats = torch.stack([torch.from_numpy(c.copy()), torch.from_numpy(sup.copy()), up[:, 0], lo[:, 0]], 1)
+    dec = DecideResult(stats, flags, cnt, sc, valid)
+    return dec, service_reduce(cnt, sc, valid, M), (None if diff is None else torch.from_numpy(diff))
+
+
+def decide_services_2s(bs: torch.Tensor, cur: torch.Tensor, M: int, thr: torch.Tensor, bound: torch.Tensor,
+                       minlb: torch.Tensor, pair_factor: float = 0.8, min_hist: int = 1,
+                       pvals: torch.Tensor | None = None, test_mask: int = (1 << N_TESTS) - 1, combine_any: int = 0,
+                       p_thr: float = 0.05, out: DecideResult | None = None, packed: torch.Tensor | None = None,
+                       diff: torch.Tensor | None = None):
+    """The service decision over band records ``bs [R, 4]`` = (centre,
+    sigma_lo, sigma_up, n) (K25, ``ops.misc.band_stats_cached``), one launch:
+    the p-values (fp32 [R, N_TESTS] or None) combine into "distribution
+    differs", which lowers the row's threshold by ``pair_factor``; the current
+    window is judged against [centre - thr sigma_lo (clamped at
+    min_lower_bound), centre + thr sigma_up], each side scoring in its own
+    sigma; rows with fewer than ``min_hist`` history samples flag nothing; the
+    service verdict is reduced.  Rows are services x M, ``M <= 16``.  With
+    ``sigma_lo == sigma_up`` the outputs are fm_decide_services' bit for bit.
+    -> (DecideResult with stats = centre, sigma_up, upper, lower; packed
+    [S, 4]; diff int8 [R], or None without p-values)."""
+    R, n_cur = cur.shape
+    check(bs.dim() == 2 and tuple(bs.shape) == (R, 4) and bs.dtype == torch.float32, "bs must be fp32 [R, 4]")
+    check(1 <= M <= 16 and R % M == 0, "rows must be services x M, M <= 16")
+    check(n_cur >= 1, "the current window is empty")
+    if not cur.is_cuda:
+        return ref_decide_services_2s(bs.numpy(), cur.numpy(), M, thr.numpy(), bound.numpy(), minlb.numpy(),
+                                      pair_factor, min_hist, None if pvals is None else pvals.numpy(), test_mask,
+                                      combine_any, p_thr)
+    require_native(cur)
+    check(bs.is_contiguous() and cur.stride(1) == 1 or n_cur == 1, "bs contiguous, cur with unit column stride")
+    for t, dt in ((thr, torch.float32), (bound, torch.int32), (minlb, torch.float32)):
+        check(t.is_cuda and t.dtype == dt and t.numel() == M, "per-metric tables must be device tensors of length M")
+    if pvals is not None:
+        check(pvals.dtype == torch.float32 and tuple(pvals.shape) == (R, N_TESTS) and pvals.is_contiguous(),
+              "pvals must be contiguous fp32 [R, N_TESTS]")
+    o = out if out is not None else alloc_decide(R, n_cur, cur.device)
+    if packed is None:
+        packed = torch.empty((R // M, 4), dtype=torch.float32, device=cur.device)
+    if diff is None and pvals is not None:
+        diff = torch.empty((R,), dtype=torch.int8, device=cur.device)
+    LIB.call("fm_decide_services_2s", ptr(bs), ptr(cur), cur.stride(0), n_cur, R // M, M, ptr(thr), ptr(bound),
+             ptr(minlb), float(pair_factor), ptr(pvals), int(test_mask), int(combine_any), float(p_thr), int(min_hist),
+             ptr(o.stats), ptr(o.flags), o.flags.shape[1], ptr(o.count), ptr(o.score), ptr(o.valid),
+             ptr(diff) if pvals is not None else None, ptr(packed), stream_of(cur))
+    return o, packed, (diff if pvals is not None else None)
 
 
 def compact_anomalies(res: DecideResult, cur: torch.Tensor, cap: int | None = None):

@@ -1102,6 +1102,126 @@ def quantile_robust_stats(hist: torch.Tensor, T: int, z0: float = QUANTILE_TAIL_
     return out[:, 0], out[:, 1], out[:, 2], out[:, 3].to(torch.int32)
 
 
+# --------------------------------------------------------------------------- K25
+# The static band models: a band that is constant over the current window, made
+# of four numbers per history row (centre, sigma_lo, sigma_up, n), computed from
+# the whole history and valid until the row is written again.
+BAND_CODES = {"moving_average_all": 0, "robust_moving_average_all": 1, "quantile_robust": 2}
+BAND_MAX_METRICS = 16
+# longest view whose code-0 rows the register-resident K1 takes (fm_row_stats.h row_stats_dispatch_nv)
+BAND_MEAN_MAX_T = 16 * 256 * 4
+BAND_TAG_SHIFT = 28
+
+
+def band_tag(code: int, T: int) -> int:
+    """The validity word of a band record: ``((code + 1) << 28) | T``."""
+    return ((int(code) + 1) << BAND_TAG_SHIFT) | int(T)
+
+
+def ref_hist_stats(hist, T: int):
+    """K1's contract, the statistics of ``ops.reference.stats_decide``: mean
+    and population std of the finite samples of ``hist[r, :T]`` in fp64,
+    rounded once -> (mean [R] f32, std [R] f32, n [R] int32); 0, 0 for a row
+    without a finite sample, NaN, NaN when ``T == 0``."""
+    x = np.asarray(hist, np.float32)[:, :T].astype(np.float64)
+    fin = np.isfinite(x)
+    n = fin.sum(1)
+    if x.shape[1] == 0:
+        nan = np.full(x.shape[0], np.nan, np.float32)
+        return nan, nan.copy(), n.astype(np.int32)
+    h = np.where(fin, x, 0.0)
+    mean = np.where(n > 0, h.sum(1) / np.maximum(n, 1), 0.0)
+    var = np.where(n > 0, (np.where(fin, x - mean[:, None], 0.0) ** 2).sum(1) / np.maximum(n, 1), 0.0)
+    return mean.astype(np.float32), np.sqrt(var).astype(np.float32), n.astype(np.int32)
+
+
+def _band_codes(codes) -> np.ndarray:
+    c = np.asarray(codes.cpu() if isinstance(codes, torch.Tensor) else codes).astype(np.int64).reshape(-1)
+    check(1 <= c.size <= BAND_MAX_METRICS, f"between 1 and {BAND_MAX_METRICS} model codes, one per metric")
+    check(bool(((c >= 0) & (c <= 2)).all()), "model codes are 0, 1 or 2 (BAND_CODES)")
+    return c
+
+
+def ref_band_stats(hist, T: int, codes, z0: float = QUANTILE_TAIL_Z):
+    """Band records of the static band models: row ``r`` of ``hist`` under the
+    model ``codes[r % M]`` (``BAND_CODES``) -> (records [R, 4] f32 = centre,
+    sigma_lo, sigma_up, n; n [R] int32).  Code 0 is :func:`ref_hist_stats`,
+    code 1 :func:`ref_robust_stats` (either with its one sigma on both sides),
+    code 2 :func:`ref_quantile_robust_stats` at ``z0``."""
+    c = _band_codes(codes)
+    x = np.asarray(hist, np.float32)
+    R = x.shape[0]
+    rec = np.zeros((R, 4), np.float32)
+    n = np.zeros(R, np.int32)
+    code = c[np.arange(R) % c.size]
+    for k in (0, 1, 2):
+        rows = np.flatnonzero(code == k)
+        if not len(rows):
+            continue
+        if k == 2:
+            ce, sl, su, nn = ref_quantile_robust_stats(x[rows], T, z0)
+        else:
+            ce, sl, nn = (ref_hist_stats if k == 0 else ref_robust_stats)(x[rows], T)
+            su = sl
+        rec[rows, 0], rec[rows, 1], rec[rows, 2], rec[rows, 3] = ce, sl, su, nn
+        n[rows] = nn
+    return rec, n
+
+
+def band_stats_cached(hist: torch.Tensor, T: int, rowmap: torch.Tensor | None, codes, cache,
+                      z0: float = QUANTILE_TAIL_Z, expect_miss: bool | None = None, blocks: int = 0,
+                      out: torch.Tensor | None = None, codes_dev: torch.Tensor | None = None) -> torch.Tensor:
+    """K25: the band records ``[R, 4]`` (centre, sigma_lo, sigma_up, n) of the
+    rows ``hist[rowmap[r], :T]`` (identity without a row map), row ``r`` under
+    the model ``codes[r % M]`` (``BAND_CODES``; a sequence or a host tensor),
+    bit for bit what K1, K13 and K24 give for the row.  The record of every
+    physical row is kept in ``cache`` (an ``engine.resident.RowStatsCache`` of
+    width 4 over the rows of ``hist``, or None): an entry whose tag names this
+    model and ``T`` is copied, any other is computed and recorded.  Within one
+    call a physical row is mapped under one code only.  ``expect_miss`` only
+    shapes the launch (None: the cache's own estimate), as ``blocks`` does (0:
+    the kernel's own grid).  Whoever writes a row of ``hist`` calls
+    ``cache.touch`` on the same stream, and ``cache.rekey(z0)`` precedes a call
+    with another ``z0`` (done here).  ``codes_dev``: the codes as int32 on the
+    device, when the caller keeps them.  CPU: :func:`ref_band_stats` over the
+    mapped rows; the cache is ignored."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [P, >= T]")
+    c = _band_codes(codes)
+    M = int(c.size)
+    if rowmap is not None:
+        check(rowmap.dim() == 1 and rowmap.dtype == torch.int32 and rowmap.device == hist.device,
+              "rowmap must be int32 [R] on the device of hist")
+        if rowmap.numel():
+            check(0 <= int(rowmap.min()) and int(rowmap.max()) < hist.shape[0], "rowmap points outside hist")
+    R = hist.shape[0] if rowmap is None else rowmap.numel()
+    z0 = float(z0)
+    if not hist.is_cuda:
+        x = hist.numpy() if rowmap is None else hist.numpy()[rowmap.numpy().astype(np.int64)]
+        return torch.from_numpy(ref_band_stats(x, T, c, z0)[0])
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    check(T < (1 << BAND_TAG_SHIFT), "view length beyond the tag's 28 bits")
+    if cache is not None:
+        check(len(cache) >= hist.shape[0] and cache.valid.device == hist.device and cache.stats.shape[1] == 4,
+              "the cache must hold 4 floats for every row of hist, on its device")
+        cache.rekey(z0)
+    if out is None:
+        out = torch.empty((R, 4), dtype=torch.float32, device=hist.device)
+    if R:
+        p, iz = quantile_tail_params(z0)
+        if codes_dev is None:
+            codes_dev = torch.from_numpy(c.astype(np.int32)).to(hist.device)
+        mask = int(np.bitwise_or.reduce(1 << c))
+        miss = (cache is None or cache.expect_miss(int(T), R)) if expect_miss is None else bool(expect_miss)
+        LIB.call("fm_band_stats_cached", ptr(hist), hist.stride(0), int(T), R, M, ptr(codes_dev), mask, p, float(iz),
+                 ptr(out), ptr(rowmap), ptr(cache.stats) if cache is not None else None,
+                 ptr(cache.valid) if cache is not None else None, int(miss), int(blocks), stream_of(hist))
+        if cache is not None:
+            cache.ticked(int(T))
+    return out
+
+
 # --------------------------------------------------------------------------- K8
 SLA_HINTS = ("latency", "error", "5xx", "4xx", "sla")
 REASONS = {0: "hpa is holding", 1: "hpa is scaling up", 2: "hpa is scaling down",
