@@ -95,8 +95,9 @@ def tick_variants(modes, dev, st, rm, cur, base) -> dict:
         sc_f = CanaryScorer(ALIASES, cfg, device=dev, xcd_balance=False)
         o = sc_f.score_resident(st.view(), rm, cur, base)     # fills this scorer's view of the cache
         v = st.view()
-        args = sc_f._front_args(ptr(v.hist), v.ld, v.T, base, cur, o, rm, v.cache, False)
-        var["front_alone"] = lambda: LIB.call("fm_tick_front", *args, stream_of(cur))
+        args = sc_f._front_args(ptr(v.hist), v.ld, v.T, base, cur, o, rm, v.cache, False,
+                                sc_f._base_cache_of(base, cur))
+        var["front_alone"] = lambda: LIB.call("fm_tick_front_bc", *args, stream_of(cur))
     return var
 
 

@@ -7,6 +7,10 @@ cache entry written) -- what the first tick after a history write costs.
 ``hot`` is the steady state (every row's statistics read from the cache),
 ``mixed`` a tick after ``--dirty-frac`` of the rows were rewritten (those rows
 are invalidated before every tick; the others hit).
+``basecold`` is ``hot`` with the baseline cache emptied before every tick (its
+tags zeroed, one small fill launch on the stream): every pairwise row misses
+and rewrites its entry -- what the first tick against a new baseline tensor
+costs.  On a scorer without that cache it is ``hot``.
 On a scorer without the cache (``FM_HIST_CACHE=0``, or a build that has none)
 both are the plain tick, which is what ``cold`` is compared with.
 
@@ -56,6 +60,7 @@ def main() -> None:
     cached = bool(getattr(sc, "hist_cache", False))
 
     bound = getattr(sc, "_bound", {}).get(id(hist))
+    bcache = sc._base_cache_of(base, cur) if hasattr(sc, "_base_cache_of") else None
     R = cur.shape[0]
     dirty = torch.randperm(R, device=dev)[:max(1, int(R * a.dirty_frac))].sort().values
 
@@ -69,6 +74,8 @@ def main() -> None:
                 inv()
             if touch is not None:
                 touch(dirty)
+            if mode == "basecold" and bcache is not None:
+                bcache.stats.zero_()
             front()
             decide()
         torch.cuda.synchronize(dev)
@@ -78,7 +85,8 @@ def main() -> None:
         run(a.warmup, mode)
         for r in range(a.repeats):
             print(json.dumps({"bench": "hist_cache", "label": a.label, "mode": mode, "cached": cached,
-                              "services": a.services, "hist": a.hist, "steps": a.steps, "repeat": r,
+                              "base_cached": bcache is not None, "services": a.services, "hist": a.hist,
+                              "steps": a.steps, "repeat": r,
                               "hot_wgs": a.hot_wgs or None, "dirty_frac": a.dirty_frac if mode == "mixed" else None,
                               "ms_per_tick": round(run(a.steps, mode), 5)}), flush=True)
 

@@ -37,15 +37,23 @@ constexpr float kPad = INFINITY;
 // steps.
 // TAGGED = false sorts bare keys (the Wilcoxon sort: the sign rides in bit 0
 // of an unsigned key, see pw_compute) and never touches `tag`.
-template <int K, bool SPLIT = false, bool TAGGED = true, typename T>
+//
+// LO, HI: only the stages of sizes LO .. HI of the network run (powers of
+// two; the whole sort is 2 .. 64 K).  REGS (HI <= 64 only, where no stage
+// crosses registers): bit k set = register k takes part.  The split layout
+// with a baseline cache (pw_compute) sorts register 0 alone up to size 64,
+// takes register 1 as it stood at that point from the cache, and then runs
+// the 128-merge by itself.
+template <int K, bool SPLIT = false, bool TAGGED = true, int LO = 2, int HI = 64 * K, unsigned REGS = ~0u, typename T>
 __device__ __forceinline__ void bitonic_sort(T (&v)[K], int (&tag)[K]) {
   // Branch-free compare-exchange (selects, no exec-mask branches): strides
   // >= 64 swap registers inside the lane, smaller strides exchange with the
   // partner lane through DPP / permlane (cmpx_lane_any).
   static_assert(!SPLIT || (K == 2 && TAGGED), "split layout is two tagged 64-lane registers");
+  static_assert(REGS == ~0u || HI <= 64, "a register subset only while no stage crosses registers");
   const int lane = lane_id();
 #pragma unroll
-  for (int size = 2; size <= 64 * K; size <<= 1) {
+  for (int size = LO; size <= HI; size <<= 1) {
     const bool tags = TAGGED && (!SPLIT || size > 64);
     if constexpr (SPLIT) {
       if (size == 128) {
@@ -81,8 +89,12 @@ __device__ __forceinline__ void bitonic_sort(T (&v)[K], int (&tag)[K]) {
           const bool lower = (lane & stride) == 0;
           // keep the smaller value in the lower lane of an ascending pair
           const bool keep_min = lower == asc;
-          if (tags) cmpx_lane_any(v[k], tag[k], stride, keep_min);
-          else cmpx_lane_any(v[k], stride, keep_min);
+          if (REGS != ~0u && ((REGS >> k) & 1u) == 0u) {
+          } else if (tags) {
+            cmpx_lane_any(v[k], tag[k], stride, keep_min);
+          } else {
+            cmpx_lane_any(v[k], stride, keep_min);
+          }
         }
       }
     }
@@ -248,41 +260,120 @@ struct PwNoHook {
   }
 };
 
-template <int K, bool SPLIT = false, class Hook = PwNoHook>
+// Baseline cache of the split layout (tick_front.hip).  A canary job's
+// baseline window is a fixed past interval: tick after tick a row brings the
+// same n_base numbers, and everything pw_compute derives from them alone is
+// the same too -- register 1 as it enters the 128-merge (finite-checked and
+// through the stages up to size 64), the count n2 and the Welch moments m2,
+// q2.  One entry per row keeps exactly those words, next to a bit copy of
+// the baseline they were computed from:
+//   raw[64]     b[lane] as loaded, lanes < n_base
+//   sorted[64]  register 1 right before the size-128 stage, that lane order, pads included
+//   stats       n2, bits(m2), bits(q2), n_base (0: empty entry)
+// The row is a hit if and only if stats.w == n_base and the 32-bit patterns
+// of all n_base raw lanes equal the loaded baseline's (a NaN equals itself,
+// -0.0 against +0.0 is a miss): decided on the device, per row, wave-uniform.
+// A hit takes register 1 and the three statistics from the entry and sorts
+// register 0 alone; the state entering the merge is bit for bit the miss
+// path's, so every output word is.  A miss computes as without a cache and
+// writes the entry (plain vector stores; a row belongs to one wave per
+// launch, and launches that share a cache run one at a time).
+// load() is called between pw_load and pw_compute, so the entry's loads are
+// in flight with the row's; `sorted` is issued ahead of `stats`, whose wait
+// (the hit test, ahead of hook.loaded()) therefore covers it.
+struct PwNoBase {
+  static constexpr bool kOn = false;
+};
+struct PwBaseCache {
+  static constexpr bool kOn = true;
+  // the three arrays and this row's entry in them; 32-bit indices (the host
+  // keeps 64 rows < 2^32), so one lane offset serves raw and sorted
+  unsigned* __restrict__ raw;
+  unsigned* __restrict__ sorted;
+  uint4* __restrict__ stats;
+  unsigned row;
+  unsigned r = 0, s = 0;
+  uint4 st = {0u, 0u, 0u, 0u};
+  __device__ __forceinline__ unsigned at() const { return row * 64u + (unsigned)lane_id(); }
+  __device__ __forceinline__ void load(int n_base) {
+    r = lane_id() < n_base ? raw[at()] : 0u;
+    s = sorted[at()];
+    st = stats[row];
+  }
+  __device__ __forceinline__ bool hit(float b, int n_base) const {
+    const bool differs = (lane_id() < n_base && __float_as_uint(b) != r) || st.w != (unsigned)n_base;
+    return __ballot(differs) == 0ull;
+  }
+};
+
+template <int K, bool SPLIT = false, class Hook = PwNoHook, class Base = PwNoBase>
 __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o,
-                                           Hook hook = Hook()) {
+                                           Hook hook = Hook(), Base bc = Base()) {
   // Everything exact is carried in integers (counts, doubled rank sums, tie
   // terms, the KS numerator); only the Welch moments are floating point.
   // Counts come from ballots (scalar popcounts), the integer sums are reduced
   // after both sorts, packed into as few words as their bounds allow, and
   // every reduction result is wave-uniform (only lane 0 writes the row).
+  static_assert(!Base::kOn || SPLIT, "the baseline cache belongs to the split layout");
   const int lane = lane_id();
   float (&v)[K] = in.v;
   int tag[K];
   float s1 = 0.f, s2 = 0.f;
-  int n1 = 0, n2 = 0;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const int i = k * 64 + lane;
-    int t = SPLIT ? (lane < (k == 0 ? n_cur : n_base) ? k : -1) : (i < n_cur ? 0 : (i < n_cur + n_base ? 1 : -1));
-    float x = v[k];
-    if (!isfinite(x)) { x = kPad; t = -1; }
-    v[k] = x; tag[k] = t;
-    if (t == 0) s1 += x;
-    if (t == 1) s2 += x;
-    n1 += __popcll(__ballot(t == 0));
-    n2 += __popcll(__ballot(t == 1));
+  int n1 = 0, n2 = 0, n;
+  float m1, m2, q1 = 0.f, q2 = 0.f;
+  bool hit = false;   // wave-uniform
+  if constexpr (Base::kOn) {
+    hit = bc.hit(v[1], n_base);
+    if (!hit && lane < n_base) bc.raw[bc.at()] = __float_as_uint(v[1]);
   }
-  const int n = n1 + n2;
-  const float m1 = wave_sum_f32_uniform(s1) / (float)(n1 > 0 ? n1 : 1);
-  const float m2 = wave_sum_f32_uniform(s2) / (float)(n2 > 0 ? n2 : 1);
-  float q1 = 0.f, q2 = 0.f;
+  if (Base::kOn && hit) {
+    if constexpr (Base::kOn) {
+      // register 0 alone, with the operations of the general form below
+      // (tag[1] is rebuilt ahead of the merge, like every tag of the split layout)
+      int t = lane < n_cur ? 0 : -1;
+      float x = v[0];
+      if (!isfinite(x)) { x = kPad; t = -1; }
+      v[0] = x; tag[0] = t; tag[1] = 1;
+      if (t == 0) s1 += x;
+      n1 += __popcll(__ballot(t == 0));
+      m1 = wave_sum_f32_uniform(s1) / (float)(n1 > 0 ? n1 : 1);
+      if (tag[0] == 0) { const float d = v[0] - m1; q1 += d * d; }
+      q1 = wave_sum_f32_uniform(q1);
+      n2 = __builtin_amdgcn_readfirstlane((int)bc.st.x);
+      m2 = __uint_as_float(bc.st.y); q2 = __uint_as_float(bc.st.z);
+      n = n1 + n2;
+      v[1] = __uint_as_float(bc.s);
+      // needed at the merge only, but waited for here: no wait for a load may
+      // follow hook.loaded()
+      asm volatile("" : "+v"(v[1]));
+    }
+  } else {
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    if (tag[k] == 0) { const float d = v[k] - m1; q1 += d * d; }
-    if (tag[k] == 1) { const float d = v[k] - m2; q2 += d * d; }
+    for (int k = 0; k < K; ++k) {
+      const int i = k * 64 + lane;
+      int t = SPLIT ? (lane < (k == 0 ? n_cur : n_base) ? k : -1) : (i < n_cur ? 0 : (i < n_cur + n_base ? 1 : -1));
+      float x = v[k];
+      if (!isfinite(x)) { x = kPad; t = -1; }
+      v[k] = x; tag[k] = t;
+      if (t == 0) s1 += x;
+      if (t == 1) s2 += x;
+      n1 += __popcll(__ballot(t == 0));
+      n2 += __popcll(__ballot(t == 1));
+    }
+    n = n1 + n2;
+    m1 = wave_sum_f32_uniform(s1) / (float)(n1 > 0 ? n1 : 1);
+    m2 = wave_sum_f32_uniform(s2) / (float)(n2 > 0 ? n2 : 1);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      if (tag[k] == 0) { const float d = v[k] - m1; q1 += d * d; }
+      if (tag[k] == 1) { const float d = v[k] - m2; q2 += d * d; }
+    }
+    q1 = wave_sum_f32_uniform(q1); q2 = wave_sum_f32_uniform(q2);
+    if constexpr (Base::kOn) {
+      if (lane == 0)
+        bc.stats[bc.row] = make_uint4((unsigned)n2, __float_as_uint(m2), __float_as_uint(q2), (unsigned)n_base);
+    }
   }
-  q1 = wave_sum_f32_uniform(q1); q2 = wave_sum_f32_uniform(q2);
 
   // ---- Wilcoxon signed-rank on position-paired differences (zero_method='wilcox')
   // One unsigned key per pair: (bits(|d|) << 1) | (d > 0).  |d| > 0 or the
@@ -322,7 +413,18 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
   constexpr bool packA = bTie + bR1 <= 32;                        // tie | r1x2
   constexpr bool packB = bTiew + bRp <= 32;                       // tiew | rplus2
   constexpr bool packC = !packA && !packB && bR1 + bRp <= 32;     // r1x2 | rplus2
-  bitonic_sort<K, SPLIT>(v, tag);
+  if constexpr (Base::kOn) {
+    // a hit: register 1 already stands where these stages would leave it
+    if (hit) {
+      bitonic_sort<K, SPLIT, true, 2, 64, 1u>(v, tag);
+    } else {
+      bitonic_sort<K, SPLIT, true, 2, 64>(v, tag);
+      bc.sorted[bc.at()] = __float_as_uint(v[1]);
+    }
+    bitonic_sort<K, SPLIT, true, 128, 128>(v, tag);
+  } else {
+    bitonic_sort<K, SPLIT>(v, tag);
+  }
   int rk2[K];
   bool en[K];
   const int tie_l = avg_ranks<K, !packA>(v, n, rk2, en);

@@ -83,6 +83,11 @@ struct FrontArgs {
   // ... and their p-values
   float *pvals, *pstats;
   int min_mw, min_wil, min_kru;
+  // the baseline cache of the rank-test rows (fm_pairwise.h PwBaseCache), or
+  // all three null.  Last, so that a kernel without it (BC = false) reads the
+  // fields above exactly where it always did.
+  unsigned *bc_raw, *bc_sorted;
+  uint4* bc_stats;
 };
 
 // Control block of the front kernel's history queue (uint32 words from
@@ -238,6 +243,23 @@ __device__ __forceinline__ void front_raw_to_suff(const unsigned* __restrict__ r
                 __uint_as_float(c.y), __uint_as_float(c.z), __uint_as_float(c.w), (int)d.x, (int)d.y);
 }
 
+// Row `row` of a launch with the baseline cache (the BC = true kernels), with
+// the hook of the caller.  The host starts those kernels only for the split
+// layout (K = 2, n_cur <= 64, n_base <= 64), so they carry no other form of
+// the row, and a launch without a cache runs a kernel without a trace of it.
+// The entry's loads are issued with the row's own, ahead of everything
+// pw_compute does.
+template <class Hook>
+__device__ __forceinline__ void pw_row_cached(const FrontArgs& a, int64_t row, double* __restrict__ o, Hook hook) {
+  const float* __restrict__ c = a.cur + row * a.ld_c;
+  const float* __restrict__ b = a.base + row * a.ld_b;
+  PwIn<2> in;
+  pw_load<2, true>(c, b, a.n_cur, a.n_base, in);
+  PwBaseCache bc{a.bc_raw, a.bc_sorted, a.bc_stats, (unsigned)row};
+  bc.load(a.n_base);
+  pw_compute<2, true>(in, a.n_cur, a.n_base, o, hook, bc);
+}
+
 // pw_row with the request for the wave's next row inside it; the row's
 // statistics go to its LDS slot `raw`.
 template <int K>
@@ -294,11 +316,12 @@ __device__ __forceinline__ void front_pvalues(const FrontArgs& a, int nr, int sl
 
 // The pairwise role of workgroup pb (0 <= pb < nP) with static rows: a wave
 // per row, grid-stride.
-template <int K>
+template <int K, bool BC>
 __device__ __forceinline__ void front_pairwise_static(const FrontArgs& a, const int pb) {
   const int64_t R = a.R, first = (int64_t)pb * 4, stride = (int64_t)a.nP * 4;
   for (int64_t row = first + wave_id(); row < R; row += stride) {
-    pw_row<K>(a.cur + row * a.ld_c, a.base + row * a.ld_b, a.n_cur, a.n_base, a.suff + row * kSuff);
+    if constexpr (BC) pw_row_cached(a, row, a.suff + row * kSuff, PwNoHook());
+    else pw_row<K>(a.cur + row * a.ld_c, a.base + row * a.ld_b, a.n_cur, a.n_base, a.suff + row * kSuff);
   }
   __syncthreads();   // this workgroup's suff rows are visible to all its waves
   FM_FT_MARK(2);
@@ -319,7 +342,7 @@ __device__ __forceinline__ void front_pairwise_static(const FrontArgs& a, const 
 }
 
 // The pairwise role of workgroup pb (0 <= pb < nP) with dynamic rows.
-template <int K>
+template <int K, bool BC>
 __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const FrontDyn& dq, const int pb) {
   __shared__ int s_rows[4][kRowCap];
   __shared__ int s_cnt[4];
@@ -364,8 +387,11 @@ __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const Fro
     // the next index is requested only when the list will have room for its
     // row: every index drawn below nx is ranked by the wave that drew it
     const bool want = nx != 0u && i + 1 >= dq.s && i + 1 < kRowCap;
-    pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base, s_raw[w][i],
-                   want, ctr, next);
+    if constexpr (BC)
+      pw_row_cached(a, (int64_t)row, nullptr, PwGrab{ctr, want, next, s_raw[w][i]});
+    else
+      pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base, s_raw[w][i],
+                     want, ctr, next);
     pending = want;
     if (lane == 0) s_rows[w][i] = row;
     ++i;
@@ -512,7 +538,7 @@ __device__ __forceinline__ void front_hist_queue(const float* __restrict__ hist,
 // lowest block ids: its workgroups are placed first and are gone after a few
 // microseconds, and the pairwise workgroups that inherit their slots start
 // late and simply grab fewer rows.
-template <int NV, int K, bool DYN>
+template <int NV, int K, bool DYN, bool BC>
 __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontDyn& dq) {
   __shared__ double red[4];
   __shared__ int redi[4];
@@ -521,8 +547,8 @@ __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontD
   const int pb = DYN ? (int)blockIdx.x - nH : (int)blockIdx.x;                  // pairwise workgroup index
   const int64_t hb = DYN ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - a.nP;   // history workgroup index
   if (pb >= 0 && pb < a.nP) {
-    if constexpr (DYN) front_pairwise_dyn<K>(a, dq, pb);
-    else front_pairwise_static<K>(a, pb);
+    if constexpr (DYN) front_pairwise_dyn<K, BC>(a, dq, pb);
+    else front_pairwise_static<K, BC>(a, pb);
   } else if (DYN || a.scan) {
     front_hist_scan<NV>(a, hb, nH, red, redi);
   } else if (a.queue == nullptr) {
@@ -533,14 +559,14 @@ __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontD
   FM_FT_MARK(1);
 }
 
-template <int NV, int K>
+template <int NV, int K, bool BC = false>
 __global__ __launch_bounds__(256) void tick_front_kernel(const FrontArgs a) {
-  tick_front_body<NV, K, false>(a, FrontDyn{});
+  tick_front_body<NV, K, false, BC>(a, FrontDyn{});
 }
 
-template <int NV, int K>
+template <int NV, int K, bool BC = false>
 __global__ __launch_bounds__(256) void tick_front_dyn_kernel(const FrontArgs a, const FrontDyn dq) {
-  tick_front_body<NV, K, true>(a, dq);
+  tick_front_body<NV, K, true, BC>(a, dq);
 }
 
 // The host's plan of the pairwise role for R rows, nP requested workgroups
@@ -635,12 +661,33 @@ static unsigned front_lds() {
 //
 // rowmap: history row of each logical row (fm_row_stats.h hist_row), or
 // nullptr for the identity.
-FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
-                         int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
-                         int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
-                         const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
-                         int q_ranges, hipStream_t stream) {
+//
+// bc_raw / bc_sorted / bc_stats (fm_tick_front_bc; all three or none; null:
+// no cache, which is what fm_tick_front passes): the baseline cache of the
+// pairwise role, one entry per logical row -- bc_raw [R, 64] and bc_sorted
+// [R, 64] uint32, bc_stats [R, 4] uint32 (16-byte aligned), zero-initialised
+// (fm_pairwise.h PwBaseCache).  Only the split layout uses it (n_cur <= 64,
+// n_base <= 64 and more than 64 pooled points); every other shape leaves it
+// untouched.  Each row tests its entry against the baseline it loads, on the
+// device: an unchanged baseline row skips its half of the sort and its
+// moments, a changed or new one computes as without a cache and rewrites
+// its entry.  The host expects nothing and tracks nothing; results are the
+// same bits either way.  A row's entry is read and written by the one wave
+// that ranks the row, with no ordering between launches beyond the
+// stream's: launches that share a cache run one at a time (the rule of
+// pqueue, which the same callers already keep).
+FM_API int fm_tick_front_bc(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur,
+                            int64_t ld_c, int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP,
+                            int nH, int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
+                            const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
+                            int q_ranges, unsigned* bc_raw, unsigned* bc_sorted, unsigned* bc_stats,
+                            hipStream_t stream) {
   if (R <= 0) return 0;
+  if ((((uintptr_t)bc_stats) & 15) != 0) return (int)hipErrorInvalidValue;
+  // the split layout alone has a kernel with the cache (entries are indexed in 32 bits)
+  const bool use_bc = bc_raw != nullptr && bc_sorted != nullptr && bc_stats != nullptr && n_cur <= 64 &&
+                      n_base <= 64 && n_cur + n_base > 64 && R <= (int64_t)1 << 25;
+  if (!use_bc) bc_raw = bc_sorted = bc_stats = nullptr;
   if ((ld_h & 3) != 0 || (((uintptr_t)hist) & 15) != 0) return (int)hipErrorInvalidValue;
   const int n = n_cur + n_base;
   if (base == nullptr || n_base <= 0 || n > 256) return (int)hipErrorInvalidValue;
@@ -657,21 +704,36 @@ FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, floa
   const dim3 grid((unsigned)(plan.nP + nH)), block(256);
   const unsigned lds = scan ? 0u : front_lds();
   const FrontArgs a{R, plan.nP, scan, T, hist, ld_h, hs, rowmap, cache, valid, queue, cur, ld_c, base, ld_b, suff,
-                    n_cur, n_base, pvals, pstats, min_mw, min_wil, min_kru};
+                    n_cur, n_base, pvals, pstats, min_mw, min_wil, min_kru, bc_raw, bc_sorted,
+                    reinterpret_cast<uint4*>(bc_stats)};
   const FrontDyn dq{pqueue, plan.q, plan.s, (int)plan.pool0};
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    auto launch = [&](auto k) {
+    auto launch = [&](auto k, auto bc) {
       constexpr int NV = decltype(nv)::value, K = decltype(k)::value;
-      if (plan.q > 0) hipLaunchKernelGGL((tick_front_dyn_kernel<NV, K>), grid, block, lds, stream, a, dq);
-      else hipLaunchKernelGGL((tick_front_kernel<NV, K>), grid, block, lds, stream, a);
+      constexpr bool BC = decltype(bc)::value;
+      if (plan.q > 0) hipLaunchKernelGGL((tick_front_dyn_kernel<NV, K, BC>), grid, block, lds, stream, a, dq);
+      else hipLaunchKernelGGL((tick_front_kernel<NV, K, BC>), grid, block, lds, stream, a);
     };
-    if (n <= 64) launch(std::integral_constant<int, 1>{});
-    else if (n <= 128) launch(std::integral_constant<int, 2>{});
-    else launch(std::integral_constant<int, 4>{});
+    if (n <= 64) launch(std::integral_constant<int, 1>{}, std::false_type{});
+    else if (n > 128) launch(std::integral_constant<int, 4>{}, std::false_type{});
+    else if (use_bc) launch(std::integral_constant<int, 2>{}, std::true_type{});
+    else launch(std::integral_constant<int, 2>{}, std::false_type{});
   });
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
   return 0;
+}
+
+// The front launch without a baseline cache: fm_tick_front_bc with null cache
+// pointers, i.e. the kernels that know nothing of it.
+FM_API int fm_tick_front(const float* hist, int64_t ld_h, int T, int64_t R, float* hs, const float* cur, int64_t ld_c,
+                         int n_cur, const float* base, int64_t ld_b, int n_base, double* suff, int nP, int nH,
+                         int min_mw, int min_wil, int min_kru, float* pvals, float* pstats, unsigned* queue,
+                         const int* rowmap, float* cache, unsigned* valid, int expect_miss, unsigned* pqueue,
+                         int q_ranges, hipStream_t stream) {
+  return fm_tick_front_bc(hist, ld_h, T, R, hs, cur, ld_c, n_cur, base, ld_b, n_base, suff, nP, nH, min_mw, min_wil,
+                          min_kru, pvals, pstats, queue, rowmap, cache, valid, expect_miss, pqueue, q_ranges, nullptr,
+                          nullptr, nullptr, stream);
 }
 
 FM_API int fm_front_timing_read(unsigned long long* host, int n) {

@@ -75,6 +75,22 @@ class _BoundHist:
         return self.cache.expect_miss(T, rows)
 
 
+class _BaseCache:
+    """Baseline cache of one baseline tensor (fm_tick_front_bc, fm_pairwise.h
+    PwBaseCache): per row the baseline as last seen (``raw``), its half of the
+    pooled sort as it enters the final merge (``sorted``) and (n2, m2, q2,
+    n_base) (``stats``; n_base 0 = empty).  The kernel tests and fills it row
+    by row; the host only owns the memory.  ~528 bytes per row."""
+
+    def __init__(self, rows: int, device):
+        self.raw = torch.zeros((rows, 64), dtype=torch.int32, device=device)
+        self.sorted = torch.zeros((rows, 64), dtype=torch.int32, device=device)
+        self.stats = torch.zeros((rows, 4), dtype=torch.int32, device=device)
+
+    def __len__(self) -> int:
+        return self.raw.shape[0]
+
+
 class CanaryScorer:
     """``mode`` (GPU only):
 
@@ -98,6 +114,26 @@ class CanaryScorer:
     the p-values; ``CanaryOutputs.effect`` / ``effect_counts`` /
     ``effect_passed`` report it.  A gated scorer ticks through ``score`` and
     ``score_resident`` only.
+
+    Baseline cache (``base_cache``, env ``FM_BASE_CACHE``; front mode, the
+    usual window shape only: both windows <= 64 points, more than 64
+    together).  A canary job's baseline window is a fixed past interval, so a
+    row's baseline is the same numbers tick after tick while its current
+    window moves.  The front kernel keeps, per row, the baseline it last saw
+    and what the rank tests derive from the baseline alone -- its sorted half
+    of the pooled sort and its moments -- and a row whose baseline still
+    compares equal, bit for bit, skips that work.  The comparison is made on
+    the device for every row of every tick: nothing is expected by the host, a
+    rewritten baseline row simply recomputes and refreshes its entry, and the
+    results are the same bits with and without the cache.  One cache per
+    baseline tensor: ``split_launchers`` / ``capture_front`` hold theirs for
+    the launcher's life, ``score_resident`` keeps it while the tensor lives
+    (a replaced baseline tensor frees its cache); ``score`` and
+    ``front_only`` take whatever tensor the caller brings and use none.
+    A row's entry is read and written by the wave that ranks the row with no
+    ordering beyond the stream's, so launches that share a cache run one at a
+    time -- the rule the pairwise row queue (``_pqueue``) already sets for
+    every front launch of one scorer.
     """
 
     def __init__(self, aliases: list[str], cfg: BrainConfig | None = None, device="cpu", overlap: bool = True,
@@ -105,7 +141,7 @@ class CanaryScorer:
                  front_wgs: tuple[float, float] | None = None, front_queue: bool = True,
                  xcd_balance: bool | None = None, hist_cache: bool = True,
                  front_hot_wgs: tuple[float, float] | None = None, model: str = "moving_average_all",
-                 codes=None, tail_z: float = 2.0):
+                 codes=None, tail_z: float = 2.0, base_cache: bool = True):
         """``model``: what the history statistics ``hs [R, 3]`` are --
         ``moving_average_all`` (mean, std, n) or ``robust_moving_average_all``
         (median, 1.4826 MAD or its mean-deviation fallback, n: K13 / K18).  The
@@ -129,7 +165,11 @@ class CanaryScorer:
         (``score_resident``) or the tensor bound by ``split_launchers`` /
         ``capture_front``.  A tick then reads only the rows written since the
         previous one; results are the same floats.  See
-        :meth:`invalidate_history` for writers the owner cannot see."""
+        :meth:`invalidate_history` for writers the owner cannot see.
+
+        ``base_cache`` (and env ``FM_BASE_CACHE``, ``0`` = off): the baseline
+        cache of the class docstring; off, every front launch passes null
+        cache pointers and runs the kernels without it."""
         self.mode = mode or ("front" if overlap else "serial")
         if self.mode not in MODES:
             raise ValueError(f"mode must be one of {MODES}")
@@ -200,6 +240,9 @@ class CanaryScorer:
         self.hist_cache = hist_cache and os.environ.get("FM_HIST_CACHE", "1") != "0"
         self._bound: dict[int, _BoundHist] = {}            # id(history tensor) -> its cache
         self._store_caches = weakref.WeakSet()             # caches of resident stores this scorer has ticked
+        self.base_cache = base_cache and os.environ.get("FM_BASE_CACHE", "1") != "0"
+        # id(baseline tensor) -> (weak reference to it, its _BaseCache); the entry goes when the tensor dies
+        self._base_caches: dict[int, tuple] = {}
         # dynamic history-row queue (8 per-XCD counters, kept zero between
         # launches by the kernel itself) + the XCD-balance control block
         self._queue = (torch.zeros(8 * 32 + 64, dtype=torch.int32, device=self.device)
@@ -211,7 +254,9 @@ class CanaryScorer:
         if self._queue is not None and xcd_balance:
             self._queue[8 * 32 + 31] = 1      # control block: XCD-balanced history ranges (tick_front.hip kXcdCtl)
         # the pairwise row queue: one counter line per range, kept zero between
-        # launches by the kernel itself
+        # launches by the kernel itself.  One front launch of this scorer at a
+        # time -- which also serialises the launches that share a baseline
+        # cache (_base_caches): its entries are read and rewritten in place
         self._pqueue = (torch.zeros(self._q_ranges * 32, dtype=torch.int32, device=self.device)
                         if self._q_ranges > 0 else None)
         self._cus = (torch.cuda.get_device_properties(self.device).multi_processor_count
@@ -402,8 +447,10 @@ class CanaryScorer:
             self._store_caches.add(cache)
             miss = cache.expect_miss(hview.T, R)
         if has_base and n <= 256:
-            LIB.call("fm_tick_front",
-                     *self._front_args(ptr(hview.hist), hview.ld, hview.T, base, cur, o, rowmap, cache, miss), st)
+            # (the baseline cache lives as long as the caller's baseline tensor does)
+            LIB.call("fm_tick_front_bc",
+                     *self._front_args(ptr(hview.hist), hview.ld, hview.T, base, cur, o, rowmap, cache, miss,
+                                       self._base_cache_of(base, cur)), st)
         else:
             c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
             LIB.call("fm_hist_stats_cached", ptr(hview.hist), hview.ld, hview.T, R, ptr(o.hs), 0, ptr(rowmap),
@@ -598,20 +645,50 @@ class CanaryScorer:
         n_h = int(fh * self._cus) if fh > 0 else 0
         return n_p, (n_h if miss or fh <= 0 else max(1, n_h))
 
-    def _front_args(self, hist_ptr, ld: int, T: int, base, cur, o: CanaryOutputs, rowmap, cache, miss: bool) -> tuple:
-        """Arguments of fm_tick_front, all but the stream: the history (pointer,
-        leading dimension, view length), ``rowmap`` (int32 [R]) or None, its
-        row-statistics cache or None, and whether the tick is expected to miss
-        (the launch streams the rows) or to hit; then the pairwise row queue
-        unless it is switched off."""
+    def _base_cache_of(self, base: torch.Tensor, cur: torch.Tensor) -> _BaseCache | None:
+        """The baseline cache of ``base`` for ticks against ``cur`` (one per
+        baseline tensor, sized to its rows, shared by the launchers of every
+        slot), or None: switched off, or a window shape the kernel has no
+        cache for.  Held through a weak reference to the tensor: when ``base``
+        dies its cache goes with it (a launcher that needs it longer keeps
+        both).  Keyed by the tensor object, like ``_bound``: a caller that
+        builds a new view of its baseline for every tick gets a new, empty
+        cache every tick and pays the miss path each time -- pass the same
+        tensor, as the fast path's groups do with ``base_d``."""
+        n_cur, n_base = cur.shape[1], base.shape[1]
+        if (not self.base_cache or n_cur > 64 or n_base > 64 or n_cur + n_base <= 64
+                or base.shape[0] < cur.shape[0]):
+            return None
+        key = id(base)
+        ent = self._base_caches.get(key)
+        if ent is not None and ent[0]() is base and len(ent[1]) == base.shape[0]:
+            return ent[1]
+        caches = self._base_caches
+
+        def drop(ref, key=key):
+            if key in caches and caches[key][0] is ref:
+                del caches[key]
+        bc = _BaseCache(base.shape[0], base.device)
+        caches[key] = (weakref.ref(base, drop), bc)
+        return bc
+
+    def _front_args(self, hist_ptr, ld: int, T: int, base, cur, o: CanaryOutputs, rowmap, cache, miss: bool,
+                    bcache: _BaseCache | None = None) -> tuple:
+        """Arguments of fm_tick_front_bc, all but the stream: the history
+        (pointer, leading dimension, view length), ``rowmap`` (int32 [R]) or
+        None, its row-statistics cache or None, and whether the tick is
+        expected to miss (the launch streams the rows) or to hit; then the
+        pairwise row queue unless it is switched off, and the three arrays of
+        the baseline cache ``bcache`` or nulls."""
         from ..ops._lib import ptr
         n_p, n_h = self._front_grid(miss)
         c_stats, c_valid = (ptr(cache.stats), ptr(cache.valid)) if cache is not None else (None, None)
         dyn = (ptr(self._pqueue), self._q_ranges) if self._pqueue is not None else (None, 0)
+        bc = (ptr(bcache.raw), ptr(bcache.sorted), ptr(bcache.stats)) if bcache is not None else (None, None, None)
         return (hist_ptr, ld, T, cur.shape[0], ptr(o.hs), ptr(cur), cur.stride(0), cur.shape[1], ptr(base),
                 base.stride(0), base.shape[1], ptr(o.suff), n_p, n_h, self.pcfg.min_mann_white, self.pcfg.min_wilcoxon,
                 self.pcfg.min_kruskal, ptr(o.pvals), ptr(o.pstats), ptr(self._queue), ptr(rowmap), c_stats, c_valid,
-                int(miss), *dyn)
+                int(miss), *dyn, *bc)
 
     def _bind(self, hist: torch.Tensor) -> _BoundHist | None:
         """The row-statistics cache of a history tensor bound to a launcher
@@ -636,7 +713,11 @@ class CanaryScorer:
         or a copy through the tensor's pointer, another process through IPC,
         ``tensor.data`` tricks that do not bump the version -- is a blind
         spot: whoever does that calls this afterwards, on the stream of the
-        write or after synchronising with it."""
+        write or after synchronising with it.
+
+        The baseline caches need none of this and are not touched here: every
+        row compares the baseline it loads with its entry on the device, so
+        it sees every write, however it was made."""
         for bh in self._bound.values():
             bh.version = -1                        # invalidated by the next launch, on its own stream
         for cache in self._store_caches:
@@ -697,13 +778,16 @@ class CanaryScorer:
         if bh is None:
             return capture(lambda: self.front_only(hist, base, cur, n_hist, packed_out, slot)).replay, o
         from ..ops._lib import LIB, ptr, stream_of
+        bc = self._base_cache_of(base, cur)
         graphs = {miss: capture(lambda miss=miss: LIB.call(
-            "fm_tick_front", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, bh.cache, miss),
+            "fm_tick_front_bc", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, bh.cache, miss, bc),
             stream_of(cur))) for miss in (True, False)}
+        keep = (base, bc)                        # the graphs hold the baseline cache's addresses
 
         def replay() -> None:
             graphs[bh.expect_miss(T, R, None)].replay()
             bh.cache.ticked(T)
+        replay.keep = keep
         return replay, o
 
     def _decide_services(self, cur, o: CanaryOutputs, has_base: bool) -> None:
@@ -730,8 +814,8 @@ class CanaryScorer:
         from ..ops._lib import LIB, ptr, stream_of
         T = hist.shape[1] if n_hist is None else int(n_hist)
         C.check(hist.stride(0) % 4 == 0 and hist.data_ptr() % 16 == 0, "history rows must be 16-B aligned")
-        # (a tensor nobody has bound: no cache, every row streams)
-        LIB.call("fm_tick_front", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, None, True),
+        # (tensors nobody has bound: no cache of either kind, every row streams)
+        LIB.call("fm_tick_front_bc", *self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None, None, True),
                  stream_of(cur))
         if decide:
             self._gate_into(cur, base, o)
@@ -762,12 +846,15 @@ class CanaryScorer:
         fs = (front_stream or torch.cuda.current_stream(dev)).cuda_stream
         ds = (decide_stream or torch.cuda.current_stream(dev)).cuda_stream
         lib = LIB.load()
-        f_fn, d_fn, R = lib.fm_tick_front, lib.fm_decide_services, cur.shape[0]
+        f_fn, d_fn, R = lib.fm_tick_front_bc, lib.fm_decide_services, cur.shape[0]
         d_args = self._decide_call_args(cur, o, True) + (ds,)
         # without a cache (hist_cache off) every tick streams: one argument set
         bh = self._bind(hist)
+        # the baseline cache, held (with its tensor) for the launcher's life
+        bc = self._base_cache_of(base, cur)
+        keep = (base, bc)
         f_args = {miss: self._front_args(ptr(hist), hist.stride(0), T, base, cur, o, None,
-                                         bh.cache if bh is not None else None, miss) + (fs,)
+                                         bh.cache if bh is not None else None, miss, bc) + (fs,)
                   for miss in ((True, False) if bh is not None else (True,))}
         expect = bh.expect_miss if bh is not None else (lambda T, R, fs: True)
         ticked = bh.cache.ticked if bh is not None else (lambda T: None)
@@ -775,8 +862,9 @@ class CanaryScorer:
         def front() -> None:
             rc = f_fn(*f_args[expect(T, R, fs)])
             if rc:
-                raise RuntimeError(f"fm_tick_front failed with hipError {rc}")
+                raise RuntimeError(f"fm_tick_front_bc failed with hipError {rc}")
             ticked(T)
+        front.keep = keep
 
         def decide() -> None:
             rc = d_fn(*d_args)

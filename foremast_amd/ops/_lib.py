@@ -165,6 +165,11 @@ _SIGS: dict[str, list] = {
     "fm_tick_front": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
                       c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                       c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p],
+    # fm_tick_front's arguments with the baseline cache ahead of the stream: bc_raw [R, 64] bc_sorted [R, 64]
+    # bc_stats [R, 4] (uint32, zero-initialised; all three or none, null = fm_tick_front)
+    "fm_tick_front_bc": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int,
+                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     # R nP q_ranges scan out[4] (int64: static rows per wave, pool start, ranges, effective nP); host only
     "fm_front_plan": [c_i64, c_int, c_int, c_int, c_void_p],
     "fm_hist_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
