@@ -1,7 +1,8 @@
 // The per-phase stages of the seasonal robust kernels, stated here only: K14
 // (seasonal_robust.hip), K20 (seasonal_trend_robust.hip) and K22
 // (seasonal_scale_robust.hip), whose forecast, profile and sigma0 are K14's bit
-// for bit because they are this code.
+// for bit because they are this code; K26 (seasonal_quantile_robust.hip) runs
+// them through K22's stages (fm_seasonal_scale.h).
 //
 // The span of J cycles of m samples sits in LDS as the keys of
 // fm_radix_select.h, key i at word a + i: a phase is a position, and its J
@@ -27,13 +28,16 @@ __device__ __forceinline__ void cex(unsigned& a, unsigned& b) {
 
 // The J keys col[0], col[m], ... of a phase sorted in registers by an odd-even
 // transposition network, the missing key last: c = how many are finite, klo /
-// kup their lower and upper middle (the missing key when c == 0).
-__device__ __forceinline__ int phase_middles(const unsigned* col, int m, int J, unsigned& klo, unsigned& kup) {
+// kup their lower and upper middle (the missing key when c == 0).  load is
+// applied to every word read (K26 masks the sign bit of its residual keys out).
+template <class Load>
+__device__ __forceinline__ int phase_middles(const unsigned* col, int m, int J, unsigned& klo, unsigned& kup,
+                                             Load load) {
   unsigned s[kMaxCycles];
   int c = 0;
 #pragma unroll
   for (int j = 0; j < kMaxCycles; ++j) {
-    s[j] = j < J ? col[j * m] : kMissing;
+    s[j] = j < J ? load(col[j * m]) : kMissing;
     c += s[j] != kMissing;
   }
 #pragma unroll
@@ -66,13 +70,17 @@ struct DeviationKey {
 // buf[ph] = K13's median rule over the finite keys of phase ph (col0 = the
 // word of key 0), NaN for a phase with none.  The keys are visible on entry;
 // the caller puts a barrier between this and a read of buf.
-template <int NT, class Decode>
-__device__ __forceinline__ void phase_values(const unsigned* col0, int m, int J, float* buf, Decode value) {
+template <int NT, class Decode, class Load>
+__device__ __forceinline__ void phase_values(const unsigned* col0, int m, int J, float* buf, Decode value, Load load) {
   for (int ph = threadIdx.x; ph < m; ph += NT) {
     unsigned klo, kup;
-    const int c = phase_middles(col0 + ph, m, J, klo, kup);
+    const int c = phase_middles(col0 + ph, m, J, klo, kup, load);
     buf[ph] = c == 0 ? quiet_nan() : 0.5f * value(klo) + 0.5f * value(kup);
   }
+}
+template <int NT, class Decode>
+__device__ __forceinline__ void phase_values(const unsigned* col0, int m, int J, float* buf, Decode value) {
+  phase_values<NT>(col0, m, J, buf, value, [](unsigned key) { return key; });
 }
 
 // buf[0..m) -> for each of this thread's phases the mean of the finite values

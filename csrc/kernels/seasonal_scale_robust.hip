@@ -10,7 +10,8 @@
 // the middle of its J residual keys by the same register sorting network
 // (non-negative floats order as their bits, the missing key last); it is
 // smoothed over w phases each side, circular, with fp64 sums, and floored at
-// floor * sigma0 / 1.4826.  The keys are rewritten once more, as the bits of
+// floor * sigma0 / 1.4826.  All of that is fm_seasonal_scale.h, which K26
+// (seasonal_quantile_robust.hip) runs too.  The keys are rewritten once more, as the bits of
 // u = r / scale[phase], and a second radix selection finds kappa = 1.4826
 // middle(u): sigma[phase] = kappa * scale[phase].
 //
@@ -25,7 +26,7 @@
 // forecast, profile and sigma0 are K14's bit for bit, and given the profile the
 // scale is exact up to kappa, which is exact where the middle of u is > 0.
 #include "fm_common.h"
-#include "fm_seasonal_profile.h"
+#include "fm_seasonal_scale.h"
 
 using namespace fm;
 
@@ -47,13 +48,6 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
   __shared__ SelectScratch<NT> s_sc;
   const int tid = threadIdx.x;
   const int64_t row = blockIdx.x;
-  const int N = J * m;                                       // span length
-  const float* p = hist + row * ld + (T - N);
-  const int a = row_word(p);                                 // LDS word of key 0
-  const int nq = row_quads(a, N);
-  unsigned* kw = reinterpret_cast<unsigned*>(s_keys);
-  float* scl = reinterpret_cast<float*>(kw + 4 * nq);        // [m]: raw scale, floored scale, sigma per phase
-  float* prof = m <= kBins ? reinterpret_cast<float*>(s_sc.bins) : scl + m;   // [m]: raw, then smoothed
   const float qnan = quiet_nan();
 
   // a row without a sigma per phase: v in every phase
@@ -68,11 +62,12 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
     }
   };
 
-  // ---- the span -> keys in place; finite count (the key range is not needed)
-  int n = 0;
-  auto count = [&](unsigned key) { n += key != kMissing; };
-  load_row_keys<NT>(p, N, a, s_keys, count);
-  n = uniform(block_sum<NT>(n, s_sc.redi));                  // (barriers: keys visible)
+  // ---- keys, profile, forecast, residual keys |e|, sigma0, the floored scale g' (fm_seasonal_scale.h)
+  const ScaleSpan sp = seasonal_scale_stages<NT, AbsResidual>(
+      hist + row * ld + (T - J * m), m, J, k, w, floor_share, H, s_keys, &s_sc, forecast + row * ldf,
+      profile != nullptr ? profile + row * (int64_t)m : nullptr, nullptr);
+  const int n = sp.n, a = sp.a, nq = sp.nq;
+  float* scl = sp.scl;                                       // [m]: floored scale, then sigma per phase
   if (n == 0) {
     for (int h = tid; h < H; h += NT) forecast[row * ldf + h] = qnan;
     if (profile != nullptr)
@@ -80,45 +75,12 @@ __global__ __launch_bounds__(NT) void seasonal_scale_robust_kernel(const float* 
     flat(qnan, qnan, 0.f);
     return;
   }
-
-  // ---- raw profile: per-phase median of the finite samples
-  phase_values<NT>(kw + a, m, J, prof, SampleKey{});
-  __syncthreads();
-
-  // ---- smoothing in place: mean of the finite raw values within k phases, circular
-  smooth_in_place<NT>(prof, m, k, [&](int ph, float v) {
-    if (profile != nullptr) profile[row * (int64_t)m + ph] = v;
-    return v;
-  });
-
-  // ---- forecast: the profile from phase 0 on, wrapped
-  write_wrapped<NT>(prof, m, H, forecast + row * ldf);
-
-  // ---- residuals about the profile: keys, fp64 sum, range
-  DevTally dev;
-  sweep_phase_keys<NT>(s_keys, nq, a, m, [&](unsigned key, int ph) {
-    const unsigned d = dev_key(key, prof[ph]);
-    dev(d);
-    return d;
-  });
-  const double sum = uniform(block_sum<NT>(dev.sum, s_sc.redd));   // (barriers: the last read of the profile is behind)
-  s_sc.clear_bins();                                         // (made visible by the barriers of mad_sigma's range)
-
-  // ---- sigma0, K14's sigma: the padding words hold the missing key, so the span is swept as a whole row
-  const LdsRow<NT> rk{s_keys, nq};
-  const float sigma0 = mad_sigma(rk, (unsigned)n, sum, dev.range, &s_sc);
-  if (sigma0 == 0.f) {                                       // a perfectly periodic span (uniform: every thread read the same middles)
+  const float sigma0 = sp.sigma0;
+  if (sigma0 == 0.f) {                                       // a perfectly periodic span
     flat(0.f, 0.f, (float)n);
     return;
   }
-
-  // ---- raw scale: per-phase middle of the residuals (the keys are their bits)
-  phase_values<NT>(kw + a, m, J, scl, DeviationKey{});
-  __syncthreads();
-
-  // ---- smoothing in place over w phases each side, then the floor
-  const float f = __fmul_rn(floor_share, __fdiv_rn(sigma0, 1.4826f));
-  smooth_in_place<NT>(scl, m, w, [&](int, float v) { return v == v ? fmaxf(v, f) : f; });
+  const LdsRow<NT> rk{s_keys, nq};
 
   // ---- the residuals in units of their phase's scale: keys, fp64 sum, range
   DevTally rel;

@@ -409,11 +409,24 @@ class Brain(BrainStateMixin):
             return {}
         return {"tail_z": min(3.0, max(0.5, float(self.cfg.quantile_tail_z)))}
 
+    def _seasonal_quantile_args(self, algorithm: str) -> dict:
+        """``period`` / ``smooth`` / ``scale_smooth`` / ``scale_floor`` /
+        ``tail_z`` of a zoo call: SEASONAL_PERIOD, SEASONAL_SMOOTH,
+        SEASONAL_SCALE_SMOOTH, SEASONAL_SCALE_FLOOR and QUANTILE_TAIL_Z (within
+        [0.5, 3.0]) for ``seasonal_quantile_robust``, nothing for any other
+        model."""
+        if zoo.canonical(algorithm) != "seasonal_quantile_robust":
+            return {}
+        return {"period": self.cfg.seasonal_period_for(self.step), "smooth": self.cfg.seasonal_smooth,
+                "scale_smooth": self.cfg.seasonal_scale_smooth, "scale_floor": max(1e-3, self.cfg.seasonal_scale_floor),
+                "tail_z": min(3.0, max(0.5, float(self.cfg.quantile_tail_z)))}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
                 **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm),
-                **self._auto_args(algorithm), **self._quantile_args(algorithm)}
+                **self._auto_args(algorithm), **self._quantile_args(algorithm),
+                **self._seasonal_quantile_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -951,7 +964,8 @@ class Brain(BrainStateMixin):
                                  **self._seasonal_args(self.cfg.hpa_forecast_algorithm),
                                  **self._trend_args(self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm),
-                                 **self._seasonal_scale_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._seasonal_scale_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._seasonal_quantile_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

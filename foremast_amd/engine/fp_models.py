@@ -637,6 +637,10 @@ class ModelsMixin:
             # the span is seasonal_robust's: no column before it is gathered; sigma comes back [R, H]
             kw = b._seasonal_scale_args(algo)
             return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
+        elif algo == "seasonal_quantile_robust":
+            # the span is seasonal_robust's: no column before it is gathered; sigma comes back as a pair
+            kw = b._seasonal_quantile_args(algo)
+            return zoo.forecast(algo, lazy.materialize(zoo.seasonal_start(sub.T, kw["period"])), sub.T, H, **kw)
         elif algo == "trend_robust":
             # only the columns the kernel holds are gathered
             return zoo.forecast(algo, lazy.materialize(zoo.trend_start(sub.T)), sub.T, H, **b._trend_args(algo))

@@ -29,6 +29,8 @@ seasonal_scale_robust           phase profile + a sigma per phase       K22 + ba
 auto_robust                     per row, the robust model that back-    K13-K22 fits + K23 + band
                                 tests best on the end of its history    decide (per point)
 quantile_robust                 median + a sigma per side, tail ranks   K24 + band decide (two sigmas)
+seasonal_quantile_robust        phase profile + a sigma per phase and   K26 + band decide (per point,
+                                per side, tail ranks                    two sigmas)
 ==============================  ======================================  ==================
 
 The exponential-smoothing family goes through the brain's fitted-model cache
@@ -58,7 +60,7 @@ ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
               "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust",
-              "quantile_robust")
+              "quantile_robust", "seasonal_quantile_robust")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -86,6 +88,9 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "auto_select": "auto_robust",
            "quantile_robust": "quantile_robust", "skew_robust": "quantile_robust",
            "asymmetric_robust": "quantile_robust", "tail_quantile": "quantile_robust",
+           "seasonal_quantile_robust": "seasonal_quantile_robust", "seasonal_skew_robust": "seasonal_quantile_robust",
+           "seasonal_asymmetric_robust": "seasonal_quantile_robust",
+           "robust_seasonal_quantile": "seasonal_quantile_robust",
            "robust_multivariate": "robust_multivariate", "robust_mvn": "robust_multivariate",
            "mvn_robust": "robust_multivariate", "multivariate_robust": "robust_multivariate"}
 
@@ -176,7 +181,9 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     candidates (``trend_block``: its ``trend_robust``'s block where that
     differs from ``block``); ``auto`` is its memory of earlier choices, when
     there is one.  ``tail_z`` is ``quantile_robust``'s: the threshold at which
-    its band ends on the history's own tail quantiles."""
+    its band ends on the history's own tail quantiles;
+    ``seasonal_quantile_robust`` takes it too, with ``seasonal_scale_robust``'s
+    parameters."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -241,6 +248,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "seasonal_quantile_robust":
+        # gated on the span's finite count, as seasonal_scale_robust; sigma is a pair, [R, H] each ([R] from the fallback)
+        fc, sigma, nfin = _seasonal_quantile_robust(hist, T, H, period, smooth, scale_smooth, scale_floor, tail_z)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
     if algo == "auto_robust":
         # gated, row by row, on the finite count of the model the row chose
         fc, sigma, nfin, choice = _auto_remembered(auto, hist, T, H, period, smooth, block, shift_threshold,
@@ -260,16 +273,23 @@ def band(fc: torch.Tensor, sigma, horizon: torch.Tensor, cur: torch.Tensor, M: i
     """Forecast -> per-point bands and decisions: each current point is
     judged against the forecast at its own horizon, centre +/- thr * sigma.
     ``sigma`` is [R], or [R, H] with a sigma per forecast step, which is
-    gathered at the horizon like the centre, or a pair (sigma_lo [R],
-    sigma_up [R]) with a sigma per side of the centre.  Rows without enough
-    history (``valid`` bit 0) flag nothing."""
+    gathered at the horizon like the centre, or a pair (sigma_lo, sigma_up)
+    with a sigma per side of the centre, both [R] or both [R, H] and gathered
+    at the horizon.  Rows without enough history (``valid`` bit 0) flag
+    nothing."""
     H = fc.shape[1]
     idx = (horizon.clamp(1, H) - 1).to(fc.device)
     center = torch.gather(fc, 1, idx).contiguous()
     if isinstance(sigma, (tuple, list)):
         sigma_lo, sigma_up = sigma
-        up, lo, flags, cnt, sc = SM.band_decide_2s(cur, center, sigma_lo.contiguous(), sigma_up.contiguous(), M,
-                                                   tables.thr, tables.bound, tables.minlb, diff, tables.pair_factor)
+        if sigma_lo.dim() == 2:
+            up, lo, flags, cnt, sc = SM.band_decide_pp_2s(cur, center, torch.gather(sigma_lo, 1, idx).contiguous(),
+                                                          torch.gather(sigma_up, 1, idx).contiguous(), M, tables.thr,
+                                                          tables.bound, tables.minlb, diff, tables.pair_factor)
+        else:
+            up, lo, flags, cnt, sc = SM.band_decide_2s(cur, center, sigma_lo.contiguous(), sigma_up.contiguous(), M,
+                                                       tables.thr, tables.bound, tables.minlb, diff,
+                                                       tables.pair_factor)
     elif sigma.dim() == 2:
         up, lo, flags, cnt, sc = SM.band_decide_pp(cur, center, torch.gather(sigma, 1, idx).contiguous(), M,
                                                    tables.thr, tables.bound, tables.minlb, diff, tables.pair_factor)
@@ -312,7 +332,7 @@ def _quantile_robust(hist, T, cur, horizon, M, tables, diff, tail_z=2.0) -> RowD
     with two sigmas then applies the per-metric thresholds, bounds and canary
     factor, each side in its own sigma units.  The history gate is the
     kernel's finite count, as ``_robust``'s.  Whole history only: no window,
-    no cache, no seasonal form."""
+    no cache; the seasonal form is ``seasonal_quantile_robust``."""
     from ..ops import misc as MI
     center, sigma_lo, sigma_up, nfin = MI.quantile_robust_stats(hist[:, :T], T, MI.quantile_tail_z(tail_z))
     has_cur = torch.isfinite(cur).any(1).to(torch.int32)
@@ -347,7 +367,7 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
 FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust",
-                                 "seasonal_scale_robust", "auto_robust")
+                                 "seasonal_scale_robust", "auto_robust", "seasonal_quantile_robust")
 
 
 def seasonal_start(T: int, period: int | None) -> int:
@@ -428,6 +448,26 @@ def _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, floor):
         return fc, sigma_h, nfin
     center, sigma, nfin = MI.robust_stats(hist, T)
     return center[:, None].expand(-1, H), sigma, nfin
+
+
+def _seasonal_quantile_robust(hist, T, H, period, smooth, scale_smooth, floor, tail_z=2.0):
+    """``seasonal_scale_robust``'s profile and per-phase scale with a sigma
+    per side: each side's tail order statistic of the signed residuals over
+    their phase's scale calibrates it, so that the band at ``thr = tail_z``
+    ends on the history's own tail quantiles in every phase, K26 -> (forecast
+    [R, H], (sigma_lo [R, H], sigma_up [R, H]), finite count [R]).  The span
+    and ``period`` None are ``seasonal_robust``'s.  A history shorter than two
+    periods, or a period too long for the kernel's budget, gets
+    ``quantile_robust``'s flat band: the whole-history median with K24's pair
+    of sigmas, [R] each."""
+    from ..ops import misc as MI
+    m = int(period or _detect_period(hist, T))
+    z0 = MI.quantile_tail_z(tail_z)
+    if MI.seasonal_cycles(T, m) >= 2:
+        fc, slo, sup, nfin = MI.seasonal_quantile_robust(hist, T, m, H, smooth, int(scale_smooth), float(floor), z0)[:4]
+        return fc, (slo, sup), nfin
+    center, sigma_lo, sigma_up, nfin = MI.quantile_robust_stats(hist[:, :T], T, z0)
+    return center[:, None].expand(-1, H), (sigma_lo, sigma_up), nfin
 
 
 # auto_robust's candidates in order of parsimony: a later one must back-test
@@ -584,10 +624,12 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
              trend_min_blocks: int = 3, scale_smooth: int = 30,
              scale_floor: float = 0.1, shift_threshold: float = 4.0, min_blocks: int = 2, holdout: int = 0,
              candidates=None, zcap: float = 8.0, margin: float = 0.05,
-             auto: AutoContext | None = None, trend_block: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+             auto: AutoContext | None = None, trend_block: int | None = None,
+             tail_z: float = 2.0) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]; sigma [R, H],
-    one per step, from ``seasonal_scale_robust`` unless it fell back).  Used by the
+    one per step, from ``seasonal_scale_robust`` unless it fell back; a pair
+    (sigma_lo, sigma_up) of those from ``seasonal_quantile_robust``).  Used by the
     band decision and, for HPA jobs, to publish the load forecast a cluster
     autoscaler can act on ahead of time (README.md:58-59 "ClusterAutoScaler
     prediction"; BASELINE config 4)."""
@@ -620,6 +662,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return _seasonal_trend_robust(hist, T, H, period, smooth, trend_min_blocks)[:2]
     if algo == "seasonal_scale_robust":
         return _seasonal_scale_robust(hist, T, H, period, smooth, scale_smooth, scale_floor)[:2]
+    if algo == "seasonal_quantile_robust":
+        return _seasonal_quantile_robust(hist, T, H, period, smooth, scale_smooth, scale_floor, tail_z)[:2]
     if algo == "auto_robust":
         return _auto_remembered(auto, hist, T, H, period, smooth, block, shift_threshold, min_blocks,
                                 trend_min_blocks, scale_smooth, scale_floor, holdout, candidates, zcap, margin,

@@ -120,6 +120,15 @@ _SIGS: dict[str, list] = {
     "fm_band_decide_2s": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                           c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                           c_void_p],
+    # hist ld T R m J k w floor p inv_z0 H forecast sigma_lo_h sigma_up_h ldf stats profile gscale stream (K26)
+    "fm_seasonal_quantile_robust": [c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_float,
+                                    ctypes.c_double, c_float, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p,
+                                    c_void_p, c_void_p, c_void_p],
+    # cur ld_c n center ld_f sigma_lo sigma_up ld_s R M thr bound minlb diff pair_factor upper lower flags NW count
+    # score stream
+    "fm_band_decide_pp_2s": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_i64, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int,
+                             c_void_p, c_void_p, c_void_p],
     # hist ld T R M codes code_mask p inv_z0 out rowmap cache valid expect_miss blocks stream (K25)
     "fm_band_stats_cached": [c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_int, ctypes.c_double, c_float,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p],

@@ -1,6 +1,7 @@
 """K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
 K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K22 seasonal scale robust
-model, K23 hold-out score, K24 quantile robust statistics (csrc/kernels/quantile_robust.hip), K8 HPA score,
+model, K23 hold-out score, K24 quantile robust statistics (csrc/kernels/quantile_robust.hip), K26 seasonal
+quantile robust model (csrc/kernels/seasonal_quantile_robust.hip), K8 HPA score,
 K9 downstream impact (csrc/kernels/bivariate.hip, csrc/kernels/mvn.hip,
 csrc/kernels/mvn_robust.hip, csrc/kernels/robust_stats.hip, csrc/kernels/seasonal_robust.hip,
 csrc/kernels/level_shift.hip, csrc/kernels/trend_robust.hip, csrc/kernels/seasonal_scale_robust.hip,
@@ -1100,6 +1101,118 @@ def quantile_robust_stats(hist: torch.Tensor, T: int, z0: float = QUANTILE_TAIL_
         LIB.call("fm_quantile_robust_stats", ptr(hist), hist.stride(0), int(T), R, p, float(iz), ptr(out),
                  stream_of(hist))
     return out[:, 0], out[:, 1], out[:, 2], out[:, 3].to(torch.int32)
+
+
+# --------------------------------------------------------------------------- K26
+def ref_seasonal_quantile_robust(hist, T: int, m: int, H: int, smooth: int = 5, scale_smooth: int = 30,
+                                 floor: float = 0.1, z0: float = QUANTILE_TAIL_Z):
+    """:func:`ref_seasonal_scale_robust`'s profile and per-phase scale with a
+    sigma per side, from tail order statistics -> (forecast [R, H] f32,
+    sigma_lo_h [R, H] f32, sigma_up_h [R, H] f32, n [R] int32, sigma0 [R] f32,
+    kappa_lo [R] f32, kappa_up [R] f32, profile [R, m] f32, gscale [R, m] f32),
+    fp32 unless it says otherwise.
+
+    The span, the phases, ``forecast``, ``profile``, ``n`` and ``sigma0`` are
+    ``ref_seasonal_robust(hist, T, m, H, smooth)``'s, and ``gscale`` is the
+    floored, smoothed per-phase scale ``g'`` of
+    :func:`ref_seasonal_scale_robust`, as itself.  With ``e_i = x_i -
+    profile[phase_i]`` of the finite samples, signed, ``v_i = e_i /
+    g'[phase_i]`` clamped to +-FLT_MAX (``|v_i|`` is that model's ``u_i``).
+    ``p, iz =`` :func:`quantile_tail_params` ``(z0)``; ``k_up = min(ceil(p (n -
+    1)), n - 1)`` in fp64, ``k_lo = (n - 1) - k_up``; with ``s`` the sorted
+    ``v``, ``d_up = s[k_up]`` and ``d_lo = -s[k_lo]``: single order
+    statistics, nothing interpolated and nothing re-centred, the profile is
+    the centre.  ``kappa_up = d_up * iz`` where ``d_up > 0``, else ``1.2533``
+    times the mean of ``v`` over ``v >= 0``, summed and divided in fp64 and
+    rounded once (0 where there is none); ``kappa_lo`` mirrors it over ``v <=
+    0``.  ``scale_up[p] = kappa_up * g'[p]``, ``sigma_up_h[:, h - 1] =
+    scale_up[(h - 1) % m]``, and likewise below: the band at ``thr = z0`` ends
+    on the history's own tail quantiles, phase by phase.  A row with ``sigma0
+    == 0`` has both scales (and ``gscale``) 0 and both kappas NaN; ``n == 0``
+    gives NaN everywhere.
+
+    ``v`` is a number wherever ``e`` is finite and ``g'`` is not 0: that holds
+    for every row whose finite ``|x|`` stay below 2^126 (about 8.5e37: then
+    ``|e| < 2^127``) and whose floor ``fp32(floor) * (sigma0 / 1.4826)`` does
+    not underflow to 0.  Beyond that ``inf / inf`` or ``0 / 0`` may make a NaN,
+    and what the kernel does with it is not part of the contract."""
+    p, iz = quantile_tail_params(z0)
+    x = np.asarray(hist, np.float32)[:, :T]
+    R = x.shape[0]
+    T, m, H = int(T), int(m), int(H)
+    forecast, _, n, sigma0, _, profile, _ = ref_seasonal_scale_robust(x, T, m, H, smooth, scale_smooth, floor)
+    J = seasonal_cycles(T, m)
+    w = scale_halfwidth(m, scale_smooth)
+    span = x[:, T - J * m:T]
+    fin = np.isfinite(span)
+    nan, big = np.float32(np.nan), np.finfo(np.float32).max
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        e = (span - np.tile(profile, (1, J))).astype(np.float32)
+        fin3 = fin.reshape(R, J, m)
+        c = fin3.sum(1)
+        raw = np.where(c > 0, _middle(np.abs(e).reshape(R, J, m), fin3, c, 1), nan).astype(np.float32)
+        g = _smooth_circular(raw, w)
+        f = (np.float32(floor) * (sigma0 / np.float32(1.4826)).astype(np.float32)).astype(np.float32)
+        gp = np.where(np.isfinite(g), np.maximum(g, f[:, None]), f[:, None]).astype(np.float32)
+        v = np.clip((e / np.tile(gp, (1, J))).astype(np.float32), -big, big)
+        n1 = (np.maximum(n, 1) - 1).astype(np.int64)
+        k_up = np.minimum(np.ceil(p * n1.astype(np.float64)).astype(np.int64), n1)
+        k_lo = n1 - k_up
+        s = np.sort(np.where(fin, v, np.float32(np.inf)), axis=1)      # missing samples sort last
+        at = lambda k: np.take_along_axis(s, k[:, None], 1)[:, 0]      # noqa: E731
+        d_up, d_lo = at(k_up), -at(k_lo)
+        above, below = fin & (v >= 0), fin & (v <= 0)
+        m_up = (np.where(above, v, 0).astype(np.float64).sum(1) / np.maximum(above.sum(1), 1)).astype(np.float32)
+        m_lo = (np.where(below, -v, 0).astype(np.float64).sum(1) / np.maximum(below.sum(1), 1)).astype(np.float32)
+        kappa_up = np.where(d_up > 0, d_up * iz, np.float32(1.2533) * m_up).astype(np.float32)
+        kappa_lo = np.where(d_lo > 0, d_lo * iz, np.float32(1.2533) * m_lo).astype(np.float32)
+        scale_up = (kappa_up[:, None] * gp).astype(np.float32)
+        scale_lo = (kappa_lo[:, None] * gp).astype(np.float32)
+    flat, none = sigma0 == 0, n == 0
+    kappa_lo[flat | none] = kappa_up[flat | none] = nan
+    scale_lo[flat] = scale_up[flat] = gp[flat] = 0
+    scale_lo[none] = scale_up[none] = gp[none] = nan
+    wrap = np.arange(H) % m
+    return (forecast, np.ascontiguousarray(scale_lo[:, wrap]), np.ascontiguousarray(scale_up[:, wrap]), n, sigma0,
+            kappa_lo, kappa_up, profile, gp)
+
+
+def seasonal_quantile_robust(hist: torch.Tensor, T: int, m: int, H: int, smooth: int = 5, scale_smooth: int = 30,
+                             floor: float = 0.1, z0: float = QUANTILE_TAIL_Z, want_profile: bool = False):
+    """K26: (forecast [R, H], sigma_lo_h [R, H], sigma_up_h [R, H], n [R]
+    int32, sigma0 [R], kappa_lo [R], kappa_up [R]) of
+    :func:`ref_seasonal_quantile_robust` over ``hist[:, :T]``, and the profile
+    and the per-phase scale ``g'`` [R, m] behind them when ``want_profile``.
+    ``hist`` may be any column view with unit column stride: rows need 4-byte
+    alignment only."""
+    check(hist.dim() == 2 and hist.dtype == torch.float32 and 0 <= T <= hist.shape[1],
+          "hist must be fp32 [R, >= T]")
+    T, m, H = int(T), int(m), int(H)
+    J = seasonal_cycles(T, m)
+    check(J >= 2, f"seasonal_quantile_robust needs two whole cycles within its budget (T = {T}, m = {m}: J = {J})")
+    check(H >= 0, "H must be >= 0")
+    check(float(floor) > 0, "floor must be > 0")
+    p, iz = quantile_tail_params(z0)
+    if not hist.is_cuda:
+        out = tuple(torch.from_numpy(a) for a in ref_seasonal_quantile_robust(hist.numpy(), T, m, H, smooth,
+                                                                             scale_smooth, floor, z0))
+        return out if want_profile else out[:7]
+    require_native(hist)
+    check(hist.stride(1) == 1 or hist.shape[1] <= 1, "rows must have unit column stride")
+    R = hist.shape[0]
+    fc = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    slo = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    sup = torch.empty((R, H), dtype=torch.float32, device=hist.device)
+    stats = torch.empty((R, 4), dtype=torch.float32, device=hist.device)
+    prof = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    gscale = torch.empty((R, m), dtype=torch.float32, device=hist.device) if want_profile else None
+    if R:
+        LIB.call("fm_seasonal_quantile_robust", ptr(hist), hist.stride(0), T, R, m, J, seasonal_halfwidth(m, smooth),
+                 scale_halfwidth(m, scale_smooth), float(floor), p, float(iz), H, ptr(fc), ptr(slo), ptr(sup),
+                 max(H, 1), ptr(stats), ptr(prof), ptr(gscale), stream_of(hist))
+    out = (fc, slo, sup, stats[:, 1].to(torch.int32), stats[:, 0], stats[:, 2], stats[:, 3])
+    return out + (prof, gscale) if want_profile else out
 
 
 # --------------------------------------------------------------------------- K25

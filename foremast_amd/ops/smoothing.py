@@ -603,3 +603,67 @@ def ref_band_decide_2s(cur, center, sigma_lo, sigma_up, M, thr, bound, minlb, di
     t = torch.from_numpy
     return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
             t(flag.sum(1).astype(np.int32)), t(score))
+
+
+def band_decide_pp_2s(cur: torch.Tensor, center: torch.Tensor, sigma_lo: torch.Tensor, sigma_up: torch.Tensor, M: int,
+                      thr, bound, minlb, diff: torch.Tensor | None = None, pair_factor: float = 0.8):
+    """:func:`band_decide` with a sigma per point and per side, ``sigma_lo [R,
+    n]`` and ``sigma_up [R, n]`` (any row stride): point ``i`` of a row is
+    judged against [centre - thr * sigma_lo[:, i], centre + thr * sigma_up[:,
+    i]] and a flagged point scores its excess in units of its own sigma of the
+    side it left.  A NaN sigma flags nothing on its side.  With ``sigma_lo ==
+    sigma_up`` the outputs are :func:`band_decide_pp`'s, with sigmas constant
+    along each row :func:`band_decide_2s`'s."""
+    R, n = cur.shape
+    for s in (sigma_lo, sigma_up):
+        check(s.dim() == 2 and tuple(s.shape) == (R, n) and s.dtype == torch.float32,
+              "sigma_lo and sigma_up must be fp32 [R, n], one per current point")
+    NW = max(1, (n + 63) // 64)
+    if not cur.is_cuda:
+        return ref_band_decide_pp_2s(cur.numpy(), center.numpy(), sigma_lo.numpy(), sigma_up.numpy(), M, thr.numpy(),
+                                     bound.numpy(), minlb.numpy(), None if diff is None else diff.numpy(), pair_factor)
+    require_native(cur)
+    if (n > 1 and (sigma_lo.stride(1) != 1 or sigma_up.stride(1) != 1)) or sigma_lo.stride(0) != sigma_up.stride(0):
+        sigma_lo, sigma_up = sigma_lo.contiguous(), sigma_up.contiguous()      # one leading dimension for both
+    d = cur.device
+    up = torch.empty((R, n), dtype=torch.float32, device=d)
+    lo = torch.empty_like(up)
+    flags = torch.empty((R, NW), dtype=torch.int64, device=d)
+    cnt = torch.empty((R,), dtype=torch.int32, device=d)
+    sc = torch.empty((R,), dtype=torch.float32, device=d)
+    LIB.call("fm_band_decide_pp_2s", ptr(cur), cur.stride(0), n, ptr(center), center.stride(0), ptr(sigma_lo),
+             ptr(sigma_up), sigma_lo.stride(0), R, M, ptr(thr), ptr(bound), ptr(minlb), ptr(diff), float(pair_factor),
+             ptr(up), ptr(lo), ptr(flags), NW, ptr(cnt), ptr(sc), stream_of(cur))
+    return up, lo, flags, cnt, sc
+
+
+def ref_band_decide_pp_2s(cur, center, sigma_lo, sigma_up, M, thr, bound, minlb, diff, pair_factor):
+    """:func:`ref_band_decide_pp` with ``sigma_lo [R, n]`` below the centre and
+    ``sigma_up [R, n]`` above it: a point over its upper bound scores ``(x -
+    upper) / sigma_up``, one under its lower bound ``(lower - x) / sigma_lo``,
+    of its own sigmas (1e30 where that side's sigma is not > 0)."""
+    R, n = cur.shape
+    m = np.arange(R) % M
+    th = thr[m].astype(np.float32)
+    if diff is not None:
+        th = np.where(diff != 0, th * np.float32(pair_factor), th)
+    sigma_lo, sigma_up = np.asarray(sigma_lo, np.float32), np.asarray(sigma_up, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        up = center + th[:, None] * sigma_up
+        lo = np.maximum(center - th[:, None] * sigma_lo, minlb[m][:, None])
+    bd = bound[m]
+    ok = np.isfinite(cur) & np.isfinite(center)
+    hi = ((bd & 1) != 0)[:, None] & (cur > up) & ok
+    lw = ((bd & 2) != 0)[:, None] & (cur < lo) & ok
+    flag = hi | lw
+    sd = np.where(hi, sigma_up, sigma_lo)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        z = np.where(sd > 0, np.where(hi, cur - up, lo - cur) / np.where(sd > 0, sd, 1), 1e30)
+    score = np.where(flag, z, 0).max(1, initial=0).astype(np.float32)
+    NW = max(1, (n + 63) // 64)
+    padded = np.zeros((R, NW * 64), bool)
+    padded[:, :n] = flag
+    words = np.packbits(padded.reshape(R, NW, 64), axis=2, bitorder="little").view(np.uint64).reshape(R, NW)
+    t = torch.from_numpy
+    return (t(up.astype(np.float32)), t(lo.astype(np.float32)), t(words.view(np.int64)),
+            t(flag.sum(1).astype(np.int32)), t(score))
