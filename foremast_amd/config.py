@@ -71,6 +71,12 @@ class BrainConfig:
     pairwise_min_shift: float = 0.0          # ML_PAIRWISE_MIN_SHIFT (fraction of the baseline median)
     pairwise_min_shift_abs: float = 0.0      # ML_PAIRWISE_MIN_SHIFT_ABS (metric units)
     pairwise_directional: bool = False       # ML_PAIRWISE_DIRECTIONAL
+    # scale test of the pairwise verdict (docs/BRAIN_SPEC.md 4.2, K27; off by default): Brown-Forsythe on the
+    # spread of current vs baseline; a row it flags is "different" whatever the location tests and the gate say
+    pairwise_scale_test: str = ""            # ML_PAIRWISE_SCALE_TEST: "" | OFF | BROWN_FORSYTHE (alias LEVENE)
+    min_scale_points: int = 20               # MIN_SCALE_DATA_POINTS (finite samples per side)
+    pairwise_scale_min_ratio: float = 1.0    # ML_PAIRWISE_SCALE_MIN_RATIO (>= 1; a design default, not measured)
+    pairwise_scale_both: bool = False        # ML_PAIRWISE_SCALE_BOTH (a narrower current window flags too)
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -228,6 +234,11 @@ class BrainConfig:
         c.pairwise_min_shift_abs = _f(env, "ML_PAIRWISE_MIN_SHIFT_ABS", c.pairwise_min_shift_abs)
         c.pairwise_directional = str(env.get("ML_PAIRWISE_DIRECTIONAL", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_directional
+        c.pairwise_scale_test = str(env.get("ML_PAIRWISE_SCALE_TEST", "") or "").strip() or c.pairwise_scale_test
+        c.min_scale_points = _i(env, "MIN_SCALE_DATA_POINTS", c.min_scale_points)
+        c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
+        c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
+            "1", "true", "yes", "on") or c.pairwise_scale_both
         if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
         c.multivariate_reject = _f(env, "ML_MULTIVARIATE_REJECT", c.multivariate_reject)

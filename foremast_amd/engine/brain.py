@@ -147,6 +147,7 @@ class Brain(BrainStateMixin):
         self.spans = Spans(exporter.registry if exporter is not None else None)
         zoo.canonical(self.cfg.ml_algorithm)   # validate early
         zoo.auto_candidates(self.cfg.auto_candidates)
+        C.ScaleTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_SCALE_TEST or a ratio below 1 fails here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -268,6 +269,8 @@ class Brain(BrainStateMixin):
             # effect-size gate (K19, off by default): rows are in no fixed
             # metric order here, so every row brings its own bound code
             diff = C.gate_diff(diff, cur, base, C.EffectGate.from_config(self.cfg), tables.bound, R)
+            # scale test (K27, off by default), after the gate: the gate never clears a scale verdict
+            diff = C.scale_diff(diff, cur, base, C.ScaleTest.from_config(self.cfg))
         # Model dispatch: rows are grouped by their metric type's algorithm
         # (ml_algorithmN, else ML_ALGORITHM) and each group is ONE batched zoo
         # call over its rows (per-series model selection as a

@@ -288,6 +288,8 @@ class ModelsMixin:
                 # effect-size gate (K19): a verdict the tests set is kept only where the difference is large enough
                 bound = torch.tensor([cfg.rule_for(a).bound for a in p0.aliases], dtype=torch.int32, device=dev)
                 diff = C.gate_diff(diff, ga.cur_dev, ga.base_d, gate, bound, M)
+            # scale test (K27, off by default): a row whose spread differs is "different" whatever the gate said
+            diff = C.scale_diff(diff, ga.cur_dev, ga.base_d, C.ScaleTest.from_config(cfg))
         NW = max(1, (n + 63) // 64)
         single = len(md.subs) == 1
         hpa_algo = zoo.canonical(cfg.hpa_forecast_algorithm) if (p0.hpa and cfg.hpa_forecast_algorithm) else None

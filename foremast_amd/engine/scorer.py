@@ -42,6 +42,11 @@ class CanaryOutputs:
     effect_passed: torch.Tensor | None = None   # [R] int8
     pvals_gated: torch.Tensor | None = None     # [R, 6] what the decision reads: pvals, NaN where the gate failed
     bs: torch.Tensor | None = None              # [R, 4] band records (centre, sigma_lo, sigma_up, n): model="band_mix"
+    # scale test (K27), None when it is off or the tick has no baseline
+    scale: torch.Tensor | None = None           # [R, 6] W, p, ratio, current median, baseline median, N
+    scale_diff: torch.Tensor | None = None      # [R] int8: the spread differs
+    pvals_scaled: torch.Tensor | None = None    # [R, 6] what the decision reads: 0 in a flagged row, else pvals / gated
+    scale_moments: torch.Tensor | None = None   # [R, 8] fp64 scratch of K27
 
 
 MODES = ("front", "fused", "overlap", "serial")
@@ -114,6 +119,15 @@ class CanaryScorer:
     the p-values; ``CanaryOutputs.effect`` / ``effect_counts`` /
     ``effect_passed`` report it.  A gated scorer ticks through ``score`` and
     ``score_resident`` only.
+
+    Scale test (``cfg.pairwise_scale_test``, off by default): when it is set
+    and the tick has a baseline, K27 (``fm_pairwise_scale``) runs on the tick's
+    stream after the p-values (and K19) and before the decision; it takes the
+    p-values the decision would read and hands on a copy with 0 in all six
+    columns of a row whose spread differs, so that row is "different" under
+    every ``ML_PAIRWISE_ALGORITHM`` and the gate never clears it;
+    ``CanaryOutputs.scale`` / ``scale_diff`` report it, ``pvals`` stay what
+    the tests computed.  Refused where the gate is.
 
     Baseline cache (``base_cache``, env ``FM_BASE_CACHE``; front mode, the
     usual window shape only: both windows <= 64 points, more than 64
@@ -198,6 +212,10 @@ class CanaryScorer:
         if self.gate.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the pairwise effect gate (ML_PAIRWISE_MIN_EFFECT / "
                              "_MIN_SHIFT / _MIN_SHIFT_ABS / _DIRECTIONAL) enabled")
+        self.scale = C.ScaleTest.from_config(cfg or BrainConfig())
+        if self.scale.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the pairwise scale test (ML_PAIRWISE_SCALE_TEST) "
+                             "enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -288,6 +306,10 @@ class CanaryScorer:
                 e = C.alloc_effect(R, d)
                 o = self._out[key]
                 o.effect, o.effect_counts, o.effect_passed, o.pvals_gated = e.effect, e.counts, e.passed, e.pvals_gated
+            if self.scale.enabled:
+                s = C.alloc_scale(R, d)
+                o = self._out[key]
+                o.scale, o.scale_diff, o.pvals_scaled, o.scale_moments = s.scale, s.scale_diff, s.pvals_scaled, s.moments
             if self.band:
                 self._out[key].bs = torch.empty((R, 4), dtype=torch.float32, device=d)
         return self._out[key]
@@ -297,37 +319,61 @@ class CanaryScorer:
         if self.gate.enabled:
             raise ValueError(f"{what} is not available with the pairwise effect gate enabled "
                              "(it ticks through score / score_resident only)")
+        if self.scale.enabled:
+            raise ValueError(f"{what} is not available with the pairwise scale test enabled "
+                             "(it ticks through score / score_resident only)")
 
     def _gate_into(self, cur, base, o: CanaryOutputs) -> CanaryOutputs:
         """K19 on the current stream, after the p-values of ``o`` exist and
         before the decision reads them: fills the gate buffers of ``o``
         (``pvals_gated`` is what ``_decide_call_args`` then hands on).
         Returns ``o``, or its copy without gate outputs when the tick has no
-        gate or no baseline."""
-        if not self.gate.enabled:
+        gate or no baseline.  The scale test (K27), where it is on, runs right
+        behind it on what the gate hands on and fills ``scale`` /
+        ``scale_diff`` / ``pvals_scaled`` the same way."""
+        if not (self.gate.enabled or self.scale.enabled):
             return o
         if base is None or base.shape[1] == 0:
-            return dataclasses.replace(o, effect=None, effect_counts=None, effect_passed=None, pvals_gated=None)
-        buf = C.EffectResult(o.effect, o.effect_counts, o.effect_passed, o.pvals_gated)
-        r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, o.pvals, out=buf)
-        if r is not buf:                      # padded wider than C.PAIRWISE_MAX: bucketed, its own tensors
-            o.effect.copy_(r.effect)
-            o.effect_counts.copy_(r.counts)
-            o.effect_passed.copy_(r.passed)
-            o.pvals_gated.copy_(r.pvals_gated)
+            return dataclasses.replace(o, effect=None, effect_counts=None, effect_passed=None, pvals_gated=None,
+                                       scale=None, scale_diff=None, pvals_scaled=None)
+        if self.gate.enabled:
+            buf = C.EffectResult(o.effect, o.effect_counts, o.effect_passed, o.pvals_gated)
+            r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, o.pvals, out=buf)
+            if r is not buf:                      # padded wider than C.PAIRWISE_MAX: bucketed, its own tensors
+                o.effect.copy_(r.effect)
+                o.effect_counts.copy_(r.counts)
+                o.effect_passed.copy_(r.passed)
+                o.pvals_gated.copy_(r.pvals_gated)
+        if self.scale.enabled:
+            buf = C.ScaleResult(o.scale, o.scale_diff, o.pvals_scaled, o.scale_moments)
+            r = C.pairwise_scale(cur, base, self.scale, o.pvals_gated if self.gate.enabled else o.pvals, out=buf)
+            if r is not buf:                      # padded wider than K27 takes: bucketed, its own tensors
+                o.scale.copy_(r.scale)
+                o.scale_diff.copy_(r.scale_diff)
+                o.pvals_scaled.copy_(r.pvals_scaled)
         return o
 
     def _gate_cpu(self, cur, base, pv, df):
-        """CPU branches: (diff & passed, EffectResult or None)."""
-        if not self.gate.enabled or base is None or base.shape[1] == 0:
-            return df, None
-        r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, pv.contiguous())
-        return df & r.passed, r
+        """CPU branches: ((diff & passed) | scale_diff, (EffectResult or None,
+        ScaleResult or None))."""
+        if base is None or base.shape[1] == 0:
+            return df, (None, None)
+        eff = sc = None
+        if self.gate.enabled:
+            eff = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, pv.contiguous())
+            df = df & eff.passed
+        if self.scale.enabled:
+            sc = C.pairwise_scale(cur, base, self.scale, pv.contiguous() if eff is None else eff.pvals_gated)
+            df = df | sc.scale_diff
+        return df, (eff, sc)
 
     @staticmethod
-    def _with_effect(o: CanaryOutputs, r) -> CanaryOutputs:
+    def _with_effect(o: CanaryOutputs, got) -> CanaryOutputs:
+        r, s = got
         if r is not None:
             o.effect, o.effect_counts, o.effect_passed, o.pvals_gated = r.effect, r.counts, r.passed, r.pvals_gated
+        if s is not None:
+            o.scale, o.scale_diff, o.pvals_scaled = s.scale, s.scale_diff, s.pvals_scaled
         return o
 
     def score(self, hist: torch.Tensor, base: torch.Tensor | None, cur: torch.Tensor,
@@ -369,10 +415,13 @@ class CanaryScorer:
         elif self.mode == "serial":
             if has_base:
                 self._pairwise_into(cur, base, o)
-                if self.gate.enabled:
+                if self.gate.enabled or self.scale.enabled:
                     # this mode's decision kernel reads `diff`, not the p-values
                     self._gate_into(cur, base, o)
-                    o.diff.mul_(o.effect_passed)
+                    if self.gate.enabled:
+                        o.diff.mul_(o.effect_passed)
+                    if self.scale.enabled:
+                        o.diff.bitwise_or_(o.scale_diff)
             C.stats_decide(hist, cur, n_hist, self.M, self.thr, self.bound, self.minlb,
                            o.diff if has_base else None, self.cfg.pairwise_threshold_factor,
                            self.cfg.min_historical_points, out=o.decide)
@@ -803,7 +852,10 @@ class CanaryScorer:
         mask, anyc = self.pcfg.mask_and_combine()
         d = o.decide
         # with the effect gate on, the decision combines the gated copy (NaN rows: "no test applies")
+        # with the scale test on, its copy of that (0 in a flagged row: "different" under every algorithm)
         pv = o.pvals if o.pvals_gated is None else o.pvals_gated
+        if o.pvals_scaled is not None:
+            pv = o.pvals_scaled
         return (ptr(o.bs if self.band else o.hs), ptr(cur), cur.stride(0), cur.shape[1], cur.shape[0] // self.M,
                 self.M, ptr(self.thr), ptr(self.bound), ptr(self.minlb), float(self.cfg.pairwise_threshold_factor),
                 ptr(pv) if has_base else None, mask, anyc, float(self.pcfg.p_threshold),

@@ -35,6 +35,10 @@ _SIGS: dict[str, list] = {
     # passed pvals_gated stream (bound, pvals_in / pvals_gated may be null)
     "fm_pairwise_effect": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_float, c_float, c_float, c_int,
                            c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # cur ld_c n_cur base ld_b n_base R min_points p_thr min_ratio inv_ratio both tier pvals_in moments scale
+    # scale_diff pvals_out stream (pvals_in / pvals_out may be null)
+    "fm_pairwise_scale": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_float, c_float, c_float,
+                          c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -346,6 +346,156 @@ def _effect_bucketed(cur, base, gate: EffectGate, bound, M: int, pvals) -> Effec
     if pvals is not None:
         pg = torch.where(passed[:, None] != 0, pvals, torch.full_like(pvals, float("nan")))
     return EffectResult(eff, cnt, passed, pg)
+
+
+# widest side (columns) K27's wave tier sorts in registers (csrc/kernels/pairwise_scale.hip kScaleWaveMax); wider
+# batches take its workgroup tier up to PAIRWISE_WIDE_MAX pooled columns and the numpy definition beyond
+SCALE_WAVE_MAX = 1024
+SCALE_TESTS = {"": "", "OFF": "", "BROWN_FORSYTHE": "BROWN_FORSYTHE", "LEVENE": "BROWN_FORSYTHE"}
+
+
+@dataclass(frozen=True)
+class ScaleTest:
+    """Pairwise scale test (K27, docs/BRAIN_SPEC.md 4.2): Brown-Forsythe on the
+    spread of current vs baseline.  A row it flags counts as "different"
+    whatever the location tests (and the effect gate) say.  ``test == ""`` = off."""
+
+    test: str = ""                  # ML_PAIRWISE_SCALE_TEST: "" | OFF | BROWN_FORSYTHE (alias LEVENE)
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD
+    min_points: int = 20            # MIN_SCALE_DATA_POINTS: finite samples needed on each side
+    min_ratio: float = 1.0          # ML_PAIRWISE_SCALE_MIN_RATIO: mean deviation of current / baseline, >= 1
+    both: bool = False              # ML_PAIRWISE_SCALE_BOTH: a narrower current window (ratio <= 1 / min_ratio) too
+
+    def __post_init__(self):
+        name = str(self.test or "").strip().upper()
+        if name not in SCALE_TESTS:
+            raise ValueError(f"unknown pairwise scale test {self.test!r} (BROWN_FORSYTHE, LEVENE or OFF)")
+        object.__setattr__(self, "test", SCALE_TESTS[name])
+        r = float(self.min_ratio)
+        if not (r >= 1.0 and r != float("inf")):          # (NaN fails the comparison too)
+            raise ValueError(f"min_ratio must be finite and >= 1, got {self.min_ratio!r}")
+        if int(self.min_points) < 0:
+            raise ValueError(f"min_points must be >= 0, got {self.min_points!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.test != ""
+
+    @classmethod
+    def from_config(cls, cfg) -> "ScaleTest":
+        """The scale test of a ``BrainConfig`` (its ``pairwise_scale_*`` settings and the pairwise threshold)."""
+        return cls(cfg.pairwise_scale_test, float(cfg.pairwise_threshold), int(cfg.min_scale_points),
+                   float(cfg.pairwise_scale_min_ratio), bool(cfg.pairwise_scale_both))
+
+
+@dataclass
+class ScaleResult:
+    scale: torch.Tensor                  # [R, 6] fp32: W, p, ratio, current median, baseline median, N
+    scale_diff: torch.Tensor             # [R] int8
+    pvals_scaled: torch.Tensor | None    # [R, 6] fp32: pvals, 0 in the six columns of a flagged row (None without pvals)
+    moments: torch.Tensor | None = None  # [R, 8] fp64 scratch of the kernel
+
+
+def alloc_scale(R: int, device, with_pvals: bool = True) -> ScaleResult:
+    return ScaleResult(
+        scale=torch.empty((R, 6), dtype=torch.float32, device=device),
+        scale_diff=torch.empty((R,), dtype=torch.int8, device=device),
+        pvals_scaled=torch.empty((R, N_TESTS), dtype=torch.float32, device=device) if with_pvals else None,
+        moments=torch.empty((R, 8), dtype=torch.float64, device=device),
+    )
+
+
+def _scale_host(cur, base, test: ScaleTest):
+    """The numpy definition: (scale [R, 6] fp32, scale_diff [R] int8)."""
+    s = ref.pairwise_scale(cur, base, test.min_points)
+    return s, ref.scale_verdict(s, test.p_threshold, test.min_ratio, test.both)
+
+
+def _force_pvals(pvals: torch.Tensor, flagged: torch.Tensor) -> torch.Tensor:
+    return torch.where(flagged[:, None] != 0, torch.zeros_like(pvals), pvals)
+
+
+def pairwise_scale(cur: torch.Tensor, base: torch.Tensor, test: ScaleTest = ScaleTest("BROWN_FORSYTHE"),
+                   pvals: torch.Tensor | None = None, out: ScaleResult | None = None,
+                   tier: str = "auto") -> ScaleResult:
+    """Brown-Forsythe scale test of current vs baseline per row and its verdict.
+
+    ``pvals`` ([R, 6] fp32, optional: what the decision would read, the effect
+    gate's copy where it ran): ``pvals_scaled`` is its copy with 0 in all six
+    columns of a flagged row, which every ``ML_PAIRWISE_ALGORITHM`` reads as
+    "different".  CPU tensors run the numpy definition, GPU tensors K27: its
+    wave tier while each side has at most SCALE_WAVE_MAX columns, its
+    workgroup tier up to PAIRWISE_WIDE_MAX pooled columns (``tier="wide"``
+    runs it for any batch that fits), and a batch padded wider than that is
+    bucketed by the rows' own used widths like the pairwise tests."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
+    if pvals is not None:
+        check(pvals.shape == (R, N_TESTS) and pvals.dtype == torch.float32 and pvals.is_contiguous()
+              and pvals.device == cur.device, "pvals must be a contiguous fp32 [R, 6] tensor on the samples' device")
+    if not cur.is_cuda:
+        s, d = _scale_host(cur.numpy(), base.numpy(), test)
+        sd = torch.from_numpy(d)
+        return ScaleResult(torch.from_numpy(s), sd, None if pvals is None else _force_pvals(pvals, sd))
+    require_native(cur)
+    n_cur, n_base = cur.shape[1], base.shape[1]
+    wave = tier == "auto" and max(n_cur, n_base) <= SCALE_WAVE_MAX
+    if not wave and n_cur + n_base > PAIRWISE_WIDE_MAX:
+        return _scale_bucketed(cur, base, test, pvals)
+    o = out if out is not None else alloc_scale(R, cur.device, pvals is not None)
+    check(pvals is None or o.pvals_scaled is not None, "out has no pvals_scaled buffer")
+    if o.moments is None:
+        o.moments = torch.empty((R, 8), dtype=torch.float64, device=cur.device)
+    f = np.float32
+    LIB.call("fm_pairwise_scale", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, int(test.min_points),
+             float(test.p_threshold), float(test.min_ratio), float(f(1.0) / f(test.min_ratio)), int(test.both),
+             0 if tier == "auto" else 2, ptr(pvals), ptr(o.moments), ptr(o.scale), ptr(o.scale_diff),
+             ptr(o.pvals_scaled) if pvals is not None else None, stream_of(cur))
+    return o
+
+
+def scale_diff(diff: torch.Tensor, cur: torch.Tensor, base: torch.Tensor, test: ScaleTest) -> torch.Tensor:
+    """``diff | flagged`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``, after ``gate_diff`` where the effect gate is on: the
+    gate never clears a scale verdict)."""
+    if not test.enabled:
+        return diff
+    return diff | pairwise_scale(cur, base, test).scale_diff.to(diff.dtype)
+
+
+def _scale_bucketed(cur, base, test: ScaleTest, pvals) -> ScaleResult:
+    """A batch padded wider than K27 takes: rows bucketed by their own used
+    widths exactly as ``_pairwise_bucketed`` does (the wave tier, then the
+    workgroup tier, each on a narrowed copy); only rows really wider than
+    PAIRWISE_WIDE_MAX run the numpy definition on the host."""
+    R = cur.shape[0]
+    dev = cur.device
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    every = torch.ones((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, every, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~fit, PAIRWISE_WIDE_MAX)
+    sc = torch.empty((R, 6), dtype=torch.float32, device=dev)
+    sd = torch.empty((R,), dtype=torch.int8, device=dev)
+    for rows in (fit, wide):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            r1 = pairwise_scale(cur.index_select(0, kd)[:, :a].contiguous(),
+                                base.index_select(0, kd)[:, :b].contiguous(), test)
+            sc.index_copy_(0, kd, r1.scale)
+            sd.index_copy_(0, kd, r1.scale_diff)
+    w = torch.nonzero(~(fit | wide)).flatten()
+    if len(w):
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        s2, d2 = _scale_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
+                             base.index_select(0, wd)[:, :b].cpu().numpy(), test)
+        sc.index_copy_(0, wd, torch.from_numpy(s2).to(dev))
+        sd.index_copy_(0, wd, torch.from_numpy(d2).to(dev))
+    return ScaleResult(sc, sd, None if pvals is None else _force_pvals(pvals, sd))
 
 
 @dataclass

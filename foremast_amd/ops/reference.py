@@ -453,3 +453,82 @@ def effect_gate(effect, bound_per_row, min_effect, min_shift, min_shift_abs, dir
             fail |= ((b == 1) & (shift <= 0)) | ((b == 2) & (shift >= 0))
     fail &= ~(np.isnan(delta) | np.isnan(shift))
     return (~fail).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# scale test of current vs baseline (K27): Brown-Forsythe, i.e. Levene's test
+# on the absolute deviations from each side's median, straight from the
+# definitions in docs/BRAIN_SPEC.md section 4.2
+
+
+def pairwise_scale(cur, base, min_points: int = 20):
+    """scale [R, 6] fp32 = (W, p, ratio, med_c, med_b, N) per row.
+
+    Over the finite samples of each side (NaN / +-inf are missing): the
+    medians in fp32 (``_mid_sorted``), the deviations u = fl32(|fl32(x -
+    med_c)|) and v likewise, and from there everything in fp64: the means
+    ubar, vbar, SSW = sum (u - ubar)^2 + sum (v - vbar)^2 (two passes), SSB =
+    n1 (ubar - zbar)^2 + n2 (vbar - zbar)^2 about the pooled mean zbar, nu =
+    N - 2, W = nu SSB / SSW, p = the two-sided Student t tail of sqrt(W) at nu
+    degrees of freedom (F(1, nu)), ratio = ubar / vbar; rounded to fp32 once.
+    W, p and ratio are NaN where a side has fewer than max(min_points, 1)
+    finite samples, a deviation overflows, or SSW == SSB == 0; SSW == 0 < SSB
+    gives W = +inf, p = 0.  The medians are NaN for an empty side only; N =
+    n1 + n2 always."""
+    f = np.float32
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    R = cur.shape[0]
+    out = np.full((R, 6), np.nan, dtype=np.float32)
+    if R == 0:
+        return out
+    x = np.where(np.isfinite(cur), cur, f(np.nan))
+    y = np.where(np.isfinite(base), base, f(np.nan))
+    n1 = np.isfinite(cur).sum(1).astype(np.int64)
+    n2 = np.isfinite(base).sum(1).astype(np.int64)
+    N = n1 + n2
+    med_c = _mid_sorted(np.sort(x, axis=1), n1)         # NaN sorts last
+    med_b = _mid_sorted(np.sort(y, axis=1), n2)
+    out[:, 3], out[:, 4], out[:, 5] = med_c, med_b, N.astype(np.float32)
+    need = max(int(min_points), 1)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        u = np.abs((x - med_c[:, None]).astype(np.float32)).astype(np.float64)
+        v = np.abs((y - med_b[:, None]).astype(np.float32)).astype(np.float64)
+        su = np.nansum(u, axis=1) if u.shape[1] else np.zeros(R)
+        sv = np.nansum(v, axis=1) if v.shape[1] else np.zeros(R)
+        d1, d2, dn = n1.astype(np.float64), n2.astype(np.float64), N.astype(np.float64)
+        ubar, vbar = su / d1, sv / d2
+        ssw = np.zeros(R)
+        if u.shape[1]:
+            ssw = ssw + np.nansum((u - ubar[:, None]) ** 2, axis=1)
+        if v.shape[1]:
+            ssw = ssw + np.nansum((v - vbar[:, None]) ** 2, axis=1)
+        zbar = (su + sv) / dn
+        ssb = d1 * (ubar - zbar) ** 2 + d2 * (vbar - zbar) ** 2
+        nu = dn - 2.0
+        W = nu * ssb / ssw                               # SSW == 0 < SSB: +inf
+        t = np.sqrt(W)
+        p = special.betainc(0.5 * nu, 0.5, nu / (nu + t * t))
+        p = np.where(np.isinf(W), 0.0, p)
+        ratio = ubar / vbar                              # vbar == 0 < ubar: +inf
+        ok = (n1 >= need) & (n2 >= need) & np.isfinite(su) & np.isfinite(sv) & ~((ssw == 0) & (ssb == 0))
+        out[:, 0] = np.where(ok, W, np.nan).astype(np.float32)
+        out[:, 1] = np.where(ok, p, np.nan).astype(np.float32)
+        out[:, 2] = np.where(ok, ratio, np.nan).astype(np.float32)
+    return out
+
+
+def scale_verdict(scale, p_thr, min_ratio: float = 1.0, both: bool = False):
+    """scale_diff [R] int8 of the scale test: 1 where the test applies (p is a
+    number), p < fp32(p_thr) (the comparison the decision makes on the six
+    tests' p-values) and the current window is the wider one by at least
+    min_ratio (ratio >= min_ratio) or, with ``both``, the narrower one by as
+    much (ratio <= fl32(1 / min_ratio)); all in fp32."""
+    f = np.float32
+    s = np.asarray(scale, dtype=np.float32)
+    p, ratio = s[:, 1], s[:, 2]
+    with np.errstate(invalid="ignore"):
+        hit = ratio >= f(min_ratio)
+        if both:
+            hit = hit | (ratio <= f(1.0) / f(min_ratio))
+        return (~np.isnan(p) & (p < f(p_thr)) & hit).astype(np.int8)
