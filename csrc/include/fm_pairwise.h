@@ -24,6 +24,9 @@ using namespace fm;
 // bitonic network (in-register swaps for strides >= 64, __shfl_xor below),
 // average ranks with ties come from a max-scan / suffix-min-scan over tie runs
 // (a sorted array without ties skips them: the run-free path of avg_ranks).
+// The front kernels with a baseline cache leave the last merge of the split
+// layout out for a row without ties: each current value is searched in the
+// sorted baseline instead (pw_rank_search).
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -274,7 +277,8 @@ struct PwNoHook {
 // of all n_base raw lanes equal the loaded baseline's (a NaN equals itself,
 // -0.0 against +0.0 is a miss): decided on the device, per row, wave-uniform.
 // A hit takes register 1 and the three statistics from the entry and sorts
-// register 0 alone; the state entering the merge is bit for bit the miss
+// register 0 alone; the state entering the merge (or, with SEARCH, the rank
+// search that stands in for it: pw_rank_search) is bit for bit the miss
 // path's, so every output word is.  A miss computes as without a cache and
 // writes the entry (plain vector stores; a row belongs to one wave per
 // launch, and launches that share a cache run one at a time).
@@ -306,7 +310,86 @@ struct PwBaseCache {
   }
 };
 
-template <int K, bool SPLIT = false, class Hook = PwNoHook, class Base = PwNoBase>
+// Search form of the pooled ranks (split layout with a baseline cache,
+// SEARCH = true).  When the size-64 stages are done both registers are sorted:
+// x = register 0 holds the n1 finite current values ascending (pads behind
+// them), b = register 1 the n2 finite baseline values descending (pads in
+// front).  Nothing a row outputs needs the two interleaved; it needs the
+// doubled rank sum of the current sample, the pooled tie term and the KS
+// numerator, and without a tie in the pooled sample all three follow from
+//   c_i = #{finite baseline y : y < x_i},   c_-1 = 0
+// of the current lanes i < n1 alone:
+//   tie  = 0
+//   r1x2 = sum_i 2 (i + c_i) + 2            (the doubled pooled rank of x_i)
+//   dnum = max_i of |(i + 1) n2 - c_i n1|                          (at x_i)
+//                   |i n2 - c_i n1|, |i n2 - (c_(i-1) + 1) n1|     (c_i > c_(i-1) only)
+//                   |n1 n2 - (c_i + 1) n1|                         (i = n1 - 1 and c_i < n2 only)
+// |F1 - F2| is linear in the baseline count between two current points, so
+// over the baseline points of a gap it peaks at the gap's first or last one:
+// the second line; the third is the gap above the largest current value.
+// (docs/PERF.md, "Rank search"; tests/test_rank_search.py checks both
+// identities, and the shorter form of the maximum computed below, against
+// the pooled order.)  n1 and n2 are wave-uniform.
+// c_i comes from a branch-free binary search, seven probes for the 65
+// outcomes, each a per-lane read of register 1 (ds_bpermute_b32: the LDS
+// crossbar, no LDS memory).  The search keeps the byte address a = 4 (64 - c)
+// of the first lane of b known to be below x: b is descending, so c counts
+// lanes from the top, and a pad (+inf) is never below a finite value.  The
+// seventh probe reads the smallest baseline value not below x_i (when there
+// is one): it equals x_i exactly when x_i has a tie across the samples.
+// Returns false, with r1x2 and dnum untouched, when the pooled sample has a
+// tie -- between neighbours of x, between neighbours of b (real lanes only:
+// pads equal each other) or across; float ==, the comparison of avg_ranks,
+// so -0.0 ties +0.0.  That is exactly when avg_ranks would leave its
+// run-free arm on the merged array, and the caller then takes the merge.
+// Wave-uniform result; one scalar branch.
+__device__ __forceinline__ bool pw_rank_search(float x, float b, int n1, int n2, unsigned& r1x2, int& dnum) {
+  const unsigned long long real0 = n1 >= 64 ? ~0ull : (1ull << n1) - 1ull;          // lanes i < n1
+  const unsigned long long pairs1 = n2 >= 2 ? ~0ull << (65 - n2) : 0ull;           // lanes 65 - n2 .. 63
+  const float xp = lane_prev(x, 0.f), bp = lane_prev(b, 0.f);
+  int a = 256;
+  float y = 0.f;
+#pragma unroll
+  for (int s = 0; s < 7; ++s) {
+    const int t = a - (s < 6 ? (128 >> s) : 4);   // steps of 32, 16, 8, 4, 2, 1 and 1 lanes
+    y = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(t, __builtin_bit_cast(int, b)));
+    a = y < x ? t : a;
+  }
+  const unsigned long long tied =
+      (__ballot(x == xp) & real0 & ~1ull) | (__ballot(b == bp) & pairs1) | (__ballot(y == x) & real0);
+  if (tied != 0ull) return false;
+  // Branch-free from here, in terms of g = 64 - c = a / 4 (seven known bits,
+  // so the products are 24-bit multiplies without a mask).  With
+  //   e_i = i n2 - c_i n1
+  // the candidates of lane i are |e_i + n2|, |e_i| and |e'_i|,
+  //   e'_i = i n2 - (c_(i-1) + 1) n1 = e_(i-1) + n2 - n1   (e'_0 = -n1),
+  // the last only when c_i > c_(i-1), which is e'_i >= e_i.  |e_i| needs no
+  // condition: where c_i = c_(i-1) it is lane i - 1's first candidate over
+  // again (and e_0 = 0 there).  The gap above the largest current value needs
+  // no candidate either: n1 (n2 - c - 1) is below that lane's first candidate
+  // n1 (n2 - c).
+  const int i = lane_id();
+  const unsigned g = ((unsigned)a >> 2) & 127u;
+  // g n1 + (i n2 - 64 n1) as one full-rate v_mad_u32_u24 (left to itself the
+  // compiler, knowing every factor small, picks the 64-bit v_mad_u64_u32)
+  const unsigned t0 = __umul24((unsigned)i, (unsigned)n2 & 127u) - 64u * (unsigned)n1;
+  unsigned eu;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(eu) : "v"(g), "s"(n1), "v"(t0));
+  const int e = (int)eu;
+  const int e1 = lane_prev(e, -n2) + (n2 - n1);
+  const int ea = abs(e + n2), eb = abs(e), ec = e1 >= e ? abs(e1) : 0;
+  int d = ea > eb ? ea : eb;
+  d = ec > d ? ec : d;
+  const bool real = i < n1;
+  r1x2 = real ? 2u * (unsigned)(i - (int)g) + 130u : 0u;   // 2 (i + c) + 2
+  dnum = real && n2 > 0 ? d : 0;
+  return true;
+}
+
+// SEARCH (the split layout with a baseline cache only): a row without a tie
+// in its pooled sample is ranked by pw_rank_search instead of the size-128
+// merge; a tied row takes the merge as without it.  Same output words.
+template <int K, bool SPLIT = false, class Hook = PwNoHook, class Base = PwNoBase, bool SEARCH = false>
 __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, double* __restrict__ o,
                                            Hook hook = Hook(), Base bc = Base()) {
   // Everything exact is carried in integers (counts, doubled rank sums, tie
@@ -413,6 +496,12 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
   constexpr bool packA = bTie + bR1 <= 32;                        // tie | r1x2
   constexpr bool packB = bTiew + bRp <= 32;                       // tiew | rplus2
   constexpr bool packC = !packA && !packB && bR1 + bRp <= 32;     // r1x2 | rplus2
+  static_assert(!SEARCH || (Base::kOn && !packA), "the search form: split layout with a baseline cache, unpacked tie term");
+  unsigned r1x2 = 0;
+  int dnum = 0;   // max |a1 n2 - a2 n1| over tie-run ends = D n1 n2
+  int tie_l = 0;
+  int dt_unused[KW];
+  bool ranked = false;   // wave-uniform: the search form gave r1x2 and dnum (and the tie term is 0)
   if constexpr (Base::kOn) {
     // a hit: register 1 already stands where these stages would leave it
     if (hit) {
@@ -421,33 +510,38 @@ __device__ __forceinline__ void pw_compute(PwIn<K>& in, int n_cur, int n_base, d
       bitonic_sort<K, SPLIT, true, 2, 64>(v, tag);
       bc.sorted[bc.at()] = __float_as_uint(v[1]);
     }
-    bitonic_sort<K, SPLIT, true, 128, 128>(v, tag);
+    if constexpr (SEARCH) {
+      // the Wilcoxon sort ahead of the branch: it is independent of the probe
+      // chain (seven dependent crossbar reads), and in one block with it the
+      // scheduler can fill the chain's latency with the sort's exchanges
+      bitonic_sort<KW, false, false>(dk, dt_unused);
+      ranked = pw_rank_search(v[0], v[1], n1, n2, r1x2, dnum);
+    }
+    if (!ranked) bitonic_sort<K, SPLIT, true, 128, 128>(v, tag);
   } else {
     bitonic_sort<K, SPLIT>(v, tag);
   }
-  int rk2[K];
-  bool en[K];
-  const int tie_l = avg_ranks<K, !packA>(v, n, rk2, en);
-
-  unsigned r1x2 = 0;
-  int dnum = 0;   // max |a1 n2 - a2 n1| over tie-run ends = D n1 n2
-  int base12 = 0;
+  if (!ranked) {
+    int rk2[K];
+    bool en[K];
+    tie_l = avg_ranks<K, !packA>(v, n, rk2, en);
+    int base12 = 0;
 #pragma unroll
-  for (int k = 0; k < K; ++k) {
-    if (tag[k] == 0) r1x2 += (unsigned)rk2[k];
-    // KS: inclusive prefix counts of both samples along the sorted order, one packed scan
-    const int a12 = wave_incl_sum(tag[k] == 0 ? 1 : (tag[k] == 1 ? (1 << 16) : 0)) + base12;
-    base12 = lane_bcast(a12, 63);
-    if (en[k] && n1 > 0 && n2 > 0) {
-      const int a1 = a12 & 0xFFFF, a2 = a12 >> 16;
-      const int dd = abs(__mul24(a1, n2) - __mul24(a2, n1));   // counts <= 1024
-      dnum = dd > dnum ? dd : dnum;
+    for (int k = 0; k < K; ++k) {
+      if (tag[k] == 0) r1x2 += (unsigned)rk2[k];
+      // KS: inclusive prefix counts of both samples along the sorted order, one packed scan
+      const int a12 = wave_incl_sum(tag[k] == 0 ? 1 : (tag[k] == 1 ? (1 << 16) : 0)) + base12;
+      base12 = lane_bcast(a12, 63);
+      if (en[k] && n1 > 0 && n2 > 0) {
+        const int a1 = a12 & 0xFFFF, a2 = a12 >> 16;
+        const int dd = abs(__mul24(a1, n2) - __mul24(a2, n1));   // counts <= 1024
+        dnum = dd > dnum ? dd : dnum;
+      }
     }
   }
   dnum = wave_max_uniform(dnum);
 
-  int dt_unused[KW];
-  bitonic_sort<KW, false, false>(dk, dt_unused);
+  if constexpr (!SEARCH) bitonic_sort<KW, false, false>(dk, dt_unused);
   unsigned dmag[KW];
 #pragma unroll
   for (int k = 0; k < KW; ++k) dmag[k] = dk[k] >> 1;

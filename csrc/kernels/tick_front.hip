@@ -248,8 +248,11 @@ __device__ __forceinline__ void front_raw_to_suff(const unsigned* __restrict__ r
 // layout (K = 2, n_cur <= 64, n_base <= 64), so they carry no other form of
 // the row, and a launch without a cache runs a kernel without a trace of it.
 // The entry's loads are issued with the row's own, ahead of everything
-// pw_compute does.
-template <class Hook>
+// pw_compute does.  RS: a row without a tie in its pooled sample is ranked by
+// searching each current value in the sorted baseline instead of the
+// size-128 merge (fm_pairwise.h pw_rank_search); RS = false compiles the row
+// without a trace of the search (FM_RANK_SEARCH=0, rank_search() below).
+template <bool RS, class Hook>
 __device__ __forceinline__ void pw_row_cached(const FrontArgs& a, int64_t row, double* __restrict__ o, Hook hook) {
   const float* __restrict__ c = a.cur + row * a.ld_c;
   const float* __restrict__ b = a.base + row * a.ld_b;
@@ -257,7 +260,7 @@ __device__ __forceinline__ void pw_row_cached(const FrontArgs& a, int64_t row, d
   pw_load<2, true>(c, b, a.n_cur, a.n_base, in);
   PwBaseCache bc{a.bc_raw, a.bc_sorted, a.bc_stats, (unsigned)row};
   bc.load(a.n_base);
-  pw_compute<2, true>(in, a.n_cur, a.n_base, o, hook, bc);
+  pw_compute<2, true, Hook, PwBaseCache, RS>(in, a.n_cur, a.n_base, o, hook, bc);
 }
 
 // pw_row with the request for the wave's next row inside it; the row's
@@ -316,11 +319,11 @@ __device__ __forceinline__ void front_pvalues(const FrontArgs& a, int nr, int sl
 
 // The pairwise role of workgroup pb (0 <= pb < nP) with static rows: a wave
 // per row, grid-stride.
-template <int K, bool BC>
+template <int K, bool BC, bool RS>
 __device__ __forceinline__ void front_pairwise_static(const FrontArgs& a, const int pb) {
   const int64_t R = a.R, first = (int64_t)pb * 4, stride = (int64_t)a.nP * 4;
   for (int64_t row = first + wave_id(); row < R; row += stride) {
-    if constexpr (BC) pw_row_cached(a, row, a.suff + row * kSuff, PwNoHook());
+    if constexpr (BC) pw_row_cached<RS>(a, row, a.suff + row * kSuff, PwNoHook());
     else pw_row<K>(a.cur + row * a.ld_c, a.base + row * a.ld_b, a.n_cur, a.n_base, a.suff + row * kSuff);
   }
   __syncthreads();   // this workgroup's suff rows are visible to all its waves
@@ -342,7 +345,7 @@ __device__ __forceinline__ void front_pairwise_static(const FrontArgs& a, const 
 }
 
 // The pairwise role of workgroup pb (0 <= pb < nP) with dynamic rows.
-template <int K, bool BC>
+template <int K, bool BC, bool RS>
 __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const FrontDyn& dq, const int pb) {
   __shared__ int s_rows[4][kRowCap];
   __shared__ int s_cnt[4];
@@ -388,7 +391,7 @@ __device__ __forceinline__ void front_pairwise_dyn(const FrontArgs& a, const Fro
     // row: every index drawn below nx is ranked by the wave that drew it
     const bool want = nx != 0u && i + 1 >= dq.s && i + 1 < kRowCap;
     if constexpr (BC)
-      pw_row_cached(a, (int64_t)row, nullptr, PwGrab{ctr, want, next, s_raw[w][i]});
+      pw_row_cached<RS>(a, (int64_t)row, nullptr, PwGrab{ctr, want, next, s_raw[w][i]});
     else
       pw_row_grab<K>(a.cur + (int64_t)row * a.ld_c, a.base + (int64_t)row * a.ld_b, a.n_cur, a.n_base, s_raw[w][i],
                      want, ctr, next);
@@ -538,7 +541,7 @@ __device__ __forceinline__ void front_hist_queue(const float* __restrict__ hist,
 // lowest block ids: its workgroups are placed first and are gone after a few
 // microseconds, and the pairwise workgroups that inherit their slots start
 // late and simply grab fewer rows.
-template <int NV, int K, bool DYN, bool BC>
+template <int NV, int K, bool DYN, bool BC, bool RS>
 __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontDyn& dq) {
   __shared__ double red[4];
   __shared__ int redi[4];
@@ -547,8 +550,8 @@ __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontD
   const int pb = DYN ? (int)blockIdx.x - nH : (int)blockIdx.x;                  // pairwise workgroup index
   const int64_t hb = DYN ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - a.nP;   // history workgroup index
   if (pb >= 0 && pb < a.nP) {
-    if constexpr (DYN) front_pairwise_dyn<K, BC>(a, dq, pb);
-    else front_pairwise_static<K, BC>(a, pb);
+    if constexpr (DYN) front_pairwise_dyn<K, BC, RS>(a, dq, pb);
+    else front_pairwise_static<K, BC, RS>(a, pb);
   } else if (DYN || a.scan) {
     front_hist_scan<NV>(a, hb, nH, red, redi);
   } else if (a.queue == nullptr) {
@@ -559,14 +562,15 @@ __device__ __forceinline__ void tick_front_body(const FrontArgs& a, const FrontD
   FM_FT_MARK(1);
 }
 
-template <int NV, int K, bool BC = false>
+template <int NV, int K, bool BC = false, bool RS = false>
 __global__ __launch_bounds__(256) void tick_front_kernel(const FrontArgs a) {
-  tick_front_body<NV, K, false, BC>(a, FrontDyn{});
+  static_assert(BC || !RS, "the rank search belongs to the kernels with the baseline cache");
+  tick_front_body<NV, K, false, BC, RS>(a, FrontDyn{});
 }
 
-template <int NV, int K, bool BC = false>
+template <int NV, int K, bool BC = false, bool RS = false>
 __global__ __launch_bounds__(256) void tick_front_dyn_kernel(const FrontArgs a, const FrontDyn dq) {
-  tick_front_body<NV, K, true, BC>(a, dq);
+  tick_front_body<NV, K, true, BC, RS>(a, dq);
 }
 
 // The host's plan of the pairwise role for R rows, nP requested workgroups
@@ -635,6 +639,19 @@ static unsigned front_lds() {
     return e != nullptr ? (unsigned)atoi(e) : 33u * 1024u;
   }();
   return b;
+}
+
+// FM_RANK_SEARCH=0 (environment, read once): the launches with a baseline
+// cache start the BC kernels compiled without the search form of the pooled
+// ranks (fm_pairwise.h pw_rank_search), i.e. every row takes the size-128
+// merge.  The switch is the kernels' template parameter RS, not a branch in
+// the row; the outputs are the same words either way.
+static bool rank_search() {
+  static const bool on = [] {
+    const char* e = getenv("FM_RANK_SEARCH");
+    return e == nullptr || atoi(e) != 0;
+  }();
+  return on;
 }
 
 // nP / nH: workgroups of each role (0 = one pairwise workgroup per 4 rows /
@@ -708,16 +725,17 @@ FM_API int fm_tick_front_bc(const float* hist, int64_t ld_h, int T, int64_t R, f
                     reinterpret_cast<uint4*>(bc_stats)};
   const FrontDyn dq{pqueue, plan.q, plan.s, (int)plan.pool0};
   const int rc = row_stats_dispatch_nv(nq, [&](auto nv) {
-    auto launch = [&](auto k, auto bc) {
+    auto launch = [&](auto k, auto bc, auto rs) {
       constexpr int NV = decltype(nv)::value, K = decltype(k)::value;
-      constexpr bool BC = decltype(bc)::value;
-      if (plan.q > 0) hipLaunchKernelGGL((tick_front_dyn_kernel<NV, K, BC>), grid, block, lds, stream, a, dq);
-      else hipLaunchKernelGGL((tick_front_kernel<NV, K, BC>), grid, block, lds, stream, a);
+      constexpr bool BC = decltype(bc)::value, RS = decltype(rs)::value;
+      if (plan.q > 0) hipLaunchKernelGGL((tick_front_dyn_kernel<NV, K, BC, RS>), grid, block, lds, stream, a, dq);
+      else hipLaunchKernelGGL((tick_front_kernel<NV, K, BC, RS>), grid, block, lds, stream, a);
     };
-    if (n <= 64) launch(std::integral_constant<int, 1>{}, std::false_type{});
-    else if (n > 128) launch(std::integral_constant<int, 4>{}, std::false_type{});
-    else if (use_bc) launch(std::integral_constant<int, 2>{}, std::true_type{});
-    else launch(std::integral_constant<int, 2>{}, std::false_type{});
+    if (n <= 64) launch(std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{});
+    else if (n > 128) launch(std::integral_constant<int, 4>{}, std::false_type{}, std::false_type{});
+    else if (use_bc && rank_search()) launch(std::integral_constant<int, 2>{}, std::true_type{}, std::true_type{});
+    else if (use_bc) launch(std::integral_constant<int, 2>{}, std::true_type{}, std::false_type{});
+    else launch(std::integral_constant<int, 2>{}, std::false_type{}, std::false_type{});
   });
   if (rc != 0) return rc;
   FM_LAUNCH_CHECK();
