@@ -36,30 +36,10 @@
 // their key order even across a tie run of mixed zeros.  fp32 denormals are
 // kept in this build (see fm_pairwise.h), so subtraction and compare tell
 // subnormal differences apart exactly as the keys do.
+#include "fm_effect.h"
 #include "fm_pairwise.h"
 
 namespace {
-
-// Order-preserving key of a float, +-inf included (an overflowed difference
-// sorts at its end).  No NaN reaches it: both operands are finite.
-__device__ __forceinline__ unsigned eff_key(float x) {
-  const unsigned b = __float_as_uint(x);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float eff_val(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-constexpr unsigned kKeyNegInf = 0x007FFFFFu;    // keys below it decode to NaN: no difference is <= them
-constexpr unsigned kKeyNegZero = 0x7FFFFFFFu;   // every d < 0 has a key <= this one
-
-// The float t with  key(d) > T  <=>  d > t  for every difference d (never
-// -0, never NaN), for T >= kKeyNegInf.  T above key(+inf) decodes to NaN and
-// d > NaN is false for all d, which is the right answer there too.
-__device__ __forceinline__ float eff_threshold(unsigned T) {
-  // key(d) > key(-0)  <=>  d >= +0  <=>  d > the largest negative subnormal
-  return eff_val(T == kKeyNegZero ? kKeyNegZero - 1u : T);
-}
 
 // One counting step: for every current sample x[k] of this lane, the length
 // p[k] of the baseline prefix with x - ys[j] > t, searched inside the lane's
@@ -199,28 +179,9 @@ __global__ __launch_bounds__(256) void pairwise_effect_kernel(
     }
     __builtin_amdgcn_wave_barrier();   // the LDS slot is reused by the next row
 
-    bool pass = true;
-    if (N > 0 && !isnan(delta) && !isnan(shift)) {
-      if (min_effect > 0.f && fabsf(delta) < min_effect) pass = false;
-      if (min_shift > 0.f || min_shift_abs > 0.f) {
-        const float a = fabsf(shift);
-        const float need_shift = min_shift * fabsf(bmed) + min_shift_abs;
-        if (!(a > 0.f && a >= need_shift)) pass = false;
-      }
-      if (directional != 0 && bound != nullptr) {
-        const int bc = bound[(int)(row % M)];
-        if (bc == 1 && shift <= 0.f) pass = false;
-        if (bc == 2 && shift >= 0.f) pass = false;
-      }
-    }
-    if (lane == 0) {
-      float4 e;
-      e.x = delta; e.y = shift; e.z = bmed; e.w = (float)N;
-      *reinterpret_cast<float4*>(effect + row * 4) = e;
-      counts[row * 2] = gt;
-      counts[row * 2 + 1] = lt;
-      passed[row] = pass ? 1 : 0;
-    }
+    const bool pass = effect_passes(N, delta, shift, bmed, row, min_effect, min_shift, min_shift_abs, directional,
+                                    bound, M);
+    if (lane == 0) effect_store(row, delta, shift, bmed, N, gt, lt, pass, effect, counts, passed);
     if (pvals_in != nullptr && lane < N_TESTS)
       pvals_gated[row * N_TESTS + lane] = pass ? pvals_in[row * N_TESTS + lane] : qnan;
   }

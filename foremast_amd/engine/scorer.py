@@ -114,7 +114,8 @@ class CanaryScorer:
 
     Effect gate (``cfg.pairwise_min_effect`` / ``_min_shift`` / ``_min_shift_abs``
     / ``_directional``, all off by default): when any is set and the tick has a
-    baseline, K19 (``fm_pairwise_effect``) runs on the tick's stream between
+    baseline, K19 (``fm_pairwise_effect``; K28, ``fm_pairwise_effect_wide``,
+    for windows of 1,025 to 8,192 pooled points) runs on the tick's stream between
     the p-values and the decision, and the decision combines the gated copy of
     the p-values; ``CanaryOutputs.effect`` / ``effect_counts`` /
     ``effect_passed`` report it.  A gated scorer ticks through ``score`` and
@@ -339,7 +340,7 @@ class CanaryScorer:
         if self.gate.enabled:
             buf = C.EffectResult(o.effect, o.effect_counts, o.effect_passed, o.pvals_gated)
             r = C.pairwise_effect(cur, base, self.gate, self.bound, self.M, o.pvals, out=buf)
-            if r is not buf:                      # padded wider than C.PAIRWISE_MAX: bucketed, its own tensors
+            if r is not buf:                      # padded wider than C.PAIRWISE_WIDE_MAX: bucketed, its own tensors
                 o.effect.copy_(r.effect)
                 o.effect_counts.copy_(r.counts)
                 o.effect_passed.copy_(r.passed)

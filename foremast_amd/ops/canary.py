@@ -255,21 +255,39 @@ def alloc_effect(R: int, device, with_pvals: bool = True) -> EffectResult:
     )
 
 
+# rows ``pairwise_effect`` has sent down each route since the last reset:
+# "wave" (K19), "wide" (K28), "oracle" (the numpy definition on the host)
+_EFFECT_ROUTE_ROWS = {"wave": 0, "wide": 0, "oracle": 0}
+
+
+def effect_route_rows() -> dict[str, int]:
+    """Rows of GPU batches per effect-gate route so far (a copy)."""
+    return dict(_EFFECT_ROUTE_ROWS)
+
+
+def reset_effect_route_rows() -> None:
+    for k in _EFFECT_ROUTE_ROWS:
+        _EFFECT_ROUTE_ROWS[k] = 0
+
+
 def pairwise_effect(cur: torch.Tensor, base: torch.Tensor, gate: EffectGate = EffectGate(),
                     bound: torch.Tensor | None = None, M: int = 1, pvals: torch.Tensor | None = None,
-                    out: EffectResult | None = None) -> EffectResult:
+                    out: EffectResult | None = None, tier: str = "auto") -> EffectResult:
     """Effect size of current vs baseline per row and the gate's verdict on it.
 
     ``bound`` (int32 [M], the bound code of metric r % M; needed when the gate
     is directional) and ``pvals`` ([R, 6] fp32, optional: ``pvals_gated`` is
     its copy with the failing rows set to NaN, which ``fm_decide_services``
     reads as "no test applies").  CPU tensors run the numpy reference, GPU
-    tensors K19 (wider than PAIRWISE_MAX pooled: bucketed by used width like
-    the pairwise tests)."""
+    tensors K19 up to PAIRWISE_MAX pooled columns and its workgroup tier K28
+    up to PAIRWISE_WIDE_MAX (``tier="wide"`` runs K28 for any batch that fits
+    it); a batch padded wider than that is bucketed by the rows' own used
+    widths like the pairwise tests."""
     R, ldc = _rows(cur)
     Rb, ldb = _rows(base)
     check(R == Rb, "current/baseline row mismatch")
     check(M >= 1, "M must be >= 1")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
     check(not gate.directional or (bound is not None and bound.numel() == M),
           "a directional gate needs the per-metric bound codes [M]")
     if pvals is not None:
@@ -285,13 +303,16 @@ def pairwise_effect(cur: torch.Tensor, base: torch.Tensor, gate: EffectGate = Ef
         return EffectResult(torch.from_numpy(eff), torch.from_numpy(cnt), torch.from_numpy(ps), pg)
     require_native(cur)
     n_cur, n_base = cur.shape[1], base.shape[1]
-    if n_cur + n_base > PAIRWISE_MAX:
+    if n_cur + n_base > PAIRWISE_WIDE_MAX:
         return _effect_bucketed(cur, base, gate, bound, M, pvals)
+    wide = tier == "wide" or n_cur + n_base > PAIRWISE_MAX
+    _EFFECT_ROUTE_ROWS["wide" if wide else "wave"] += R
     o = out if out is not None else alloc_effect(R, cur.device, pvals is not None)
     if bound is not None:
         check(bound.is_cuda and bound.dtype == torch.int32 and bound.is_contiguous(), "bound must be a device int32 [M]")
     check(pvals is None or o.pvals_gated is not None, "out has no pvals_gated buffer")
-    LIB.call("fm_pairwise_effect", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, float(gate.min_effect),
+    LIB.call("fm_pairwise_effect_wide" if wide else "fm_pairwise_effect", ptr(cur), ldc, n_cur, ptr(base), ldb,
+             n_base, R, float(gate.min_effect),
              float(gate.min_shift), float(gate.min_shift_abs), int(gate.directional), ptr(bound), M, ptr(pvals),
              ptr(o.effect), ptr(o.counts), ptr(o.passed), ptr(o.pvals_gated) if pvals is not None else None,
              stream_of(cur))
@@ -308,28 +329,32 @@ def gate_diff(diff: torch.Tensor, cur: torch.Tensor, base: torch.Tensor, gate: E
 
 
 def _effect_bucketed(cur, base, gate: EffectGate, bound, M: int, pvals) -> EffectResult:
-    """A batch padded wider than PAIRWISE_MAX pooled columns: rows bucketed by
-    their own used widths exactly as ``_pairwise_bucketed`` does; rows that
-    fit run K19 on a narrowed copy, only really wider rows the CPU oracle.
-    The gate is per row, so it is evaluated once over the assembled effects
-    (bound codes follow the ORIGINAL row index r % M)."""
+    """A batch padded wider than PAIRWISE_WIDE_MAX pooled columns: rows
+    bucketed by their own used widths exactly as ``_pairwise_bucketed`` does;
+    rows that fit run K19 on a narrowed copy, of the rest those that fit
+    PAIRWISE_WIDE_MAX run K28 the same way, only really wider rows the numpy
+    definition on the host.  The gate is per row, so it is evaluated once over
+    the assembled effects (bound codes follow the ORIGINAL row index r % M)."""
     R = cur.shape[0]
     dev = cur.device
     lc, lb = used_width(cur).cpu(), used_width(base).cpu()
-    fit = (lc + lb) <= PAIRWISE_MAX
-    if fit.any() and int(lc[fit].max()) + int(lb[fit].max()) > PAIRWISE_MAX:
-        fit &= (lc <= PAIRWISE_MAX // 2) & (lb <= PAIRWISE_MAX // 2)
+    every = torch.ones((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, every, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~fit, PAIRWISE_WIDE_MAX)
     eff = torch.empty((R, 4), dtype=torch.float32, device=dev)
     cnt = torch.empty((R, 2), dtype=torch.int32, device=dev)
-    k = torch.nonzero(fit).flatten()
-    if len(k):
-        a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
-        kd = k.to(dev)
-        r1 = pairwise_effect(cur.index_select(0, kd)[:, :a].contiguous(), base.index_select(0, kd)[:, :b].contiguous())
-        eff.index_copy_(0, kd, r1.effect)
-        cnt.index_copy_(0, kd, r1.counts)
-    w = torch.nonzero(~fit).flatten()
+    for rows, tier in ((fit, "auto"), (wide, "wide")):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            r1 = pairwise_effect(cur.index_select(0, kd)[:, :a].contiguous(),
+                                 base.index_select(0, kd)[:, :b].contiguous(), tier=tier)
+            eff.index_copy_(0, kd, r1.effect)
+            cnt.index_copy_(0, kd, r1.counts)
+    w = torch.nonzero(~(fit | wide)).flatten()
     if len(w):
+        _EFFECT_ROUTE_ROWS["oracle"] += len(w)
         a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
         wd = w.to(dev)
         e2, c2 = ref.pairwise_effect(cur.index_select(0, wd)[:, :a].cpu().numpy(),

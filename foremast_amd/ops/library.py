@@ -60,7 +60,8 @@ def pairwise_effect(cur: torch.Tensor, base: torch.Tensor, bound: torch.Tensor, 
                     directional: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(effect [R, 4] = Cliff's delta, Hodges-Lehmann shift, baseline median, N;
     counts [R, 2] int32 = #{d > 0}, #{d < 0}; passed [R] int8) of current vs
-    baseline; row r is judged by bound code ``bound[r % len(bound)]`` (K19)."""
+    baseline; row r is judged by bound code ``bound[r % len(bound)]`` (K19; K28 for
+    windows of 1,025 to 8,192 pooled points)."""
     _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
     _need(bound.dim() == 1 and bound.numel() >= 1 and bound.dtype == torch.int32, "bound must be int32 [M]")
     gate = C.EffectGate(min_effect, min_shift, min_shift_abs, directional)
