@@ -356,10 +356,11 @@ __host__ __device__ __forceinline__ float u01(uint32_t h) { return ((float)(h >>
 // Special functions for p-values (double precision; one evaluation per row).
 __device__ __forceinline__ double norm_sf(double z) { return 0.5 * erfc(z * 0.70710678118654752440); }
 
-// Regularized lower incomplete gamma P(a,x) / upper Q(a,x).
-__device__ inline double gamma_q(double a, double x) {
+// Regularized lower incomplete gamma P(a,x) / upper Q(a,x); gln = lgamma(a),
+// from the caller: the one user (K29) has it for a = k / 2 as a sum of a few
+// logarithms, and the general lgamma costs over a hundred registers.
+__device__ inline double gamma_q(double a, double x, double gln) {
   if (!(x > 0.0)) return 1.0;
-  const double gln = lgamma(a);
   if (x < a + 1.0) {  // series for P
     double ap = a, sum = 1.0 / a, del = sum;
     for (int n = 0; n < 500; ++n) {
@@ -383,7 +384,7 @@ __device__ inline double gamma_q(double a, double x) {
   }
   return exp(-x + a * log(x) - gln) * h;
 }
-__device__ __forceinline__ double chi2_sf(double x, double df) { return gamma_q(0.5 * df, 0.5 * x); }
+__device__ __forceinline__ double chi2_sf(double x, double df, double gln) { return gamma_q(0.5 * df, 0.5 * x, gln); }
 
 // 1/x from the hardware reciprocal estimate refined by two Newton steps
 // (4 dependent FMAs) instead of the IEEE division sequence (div_scale x2,

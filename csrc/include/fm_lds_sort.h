@@ -1,6 +1,8 @@
 // The LDS sort of the 256-thread workgroup kernels that hold the two samples of
-// a row as order-preserving keys: K21 (pairwise_wide.hip, the rank tests) and
-// K28 (pairwise_effect_wide.hip, the effect-size gate).
+// a row as order-preserving keys: K21 (pairwise_wide.hip, the rank tests),
+// K28 (pairwise_effect_wide.hip, the effect-size gate) and K29
+// (pairwise_pods.hip, the per-pod test), and the counting searches and the
+// workgroup sums K21 and K29 rank a sorted run with.
 //
 // A bitonic network whose comparators all put the smaller key at the lower
 // index (the first step of a merge pairs i with i ^ (size - 1), the rest i
@@ -137,6 +139,47 @@ __device__ __forceinline__ void sort_sides(Side a, Side b) {
     if ((1 << lsz) <= b.P) chunk_pass(b, [](unsigned (&e)[kChunk]) { merge_tail_regs(e); });
     __syncthreads();
   }
+}
+
+// #(k[0..n) < x) and #(k[0..n) <= x) of a sorted run
+__device__ __forceinline__ int count_lt(const unsigned* k, int n, unsigned x) {
+  int lo = 0, len = n;
+  while (len > 0) {
+    const int half = len >> 1;
+    const bool r = k[lo + half] < x;
+    lo = r ? lo + half + 1 : lo;
+    len = r ? len - half - 1 : half;
+  }
+  return lo;
+}
+__device__ __forceinline__ int count_le(const unsigned* k, int n, unsigned x) {
+  int lo = 0, len = n;
+  while (len > 0) {
+    const int half = len >> 1;
+    const bool r = k[lo + half] <= x;
+    lo = r ? lo + half + 1 : lo;
+    len = r ? len - half - 1 : half;
+  }
+  return lo;
+}
+
+// N sums over the workgroup behind one pair of barriers
+template <int N, typename T>
+__device__ __forceinline__ void block_sums(T (&v)[N], T (*scratch)[kWideWaves]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const T w = wave_sum(v[j]);
+    if (lane_id() == 0) scratch[j][wave_id()] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    T r = 0;
+#pragma unroll
+    for (int w = 0; w < kWideWaves; ++w) r += scratch[j][w];
+    v[j] = r;
+  }
+  __syncthreads();
 }
 
 // The key a sample is sorted by: -0.0 is made +0.0 first, so it ties with 0.0

@@ -43,47 +43,6 @@ struct WideShared {
 // 32.3 KiB: within the plain launch limit, four workgroups per CU by LDS
 static_assert(sizeof(WideShared) <= kLaunchLds && 4 * sizeof(WideShared) <= 160 * 1024, "LDS of a workgroup");
 
-// #(k[0..n) < x) and #(k[0..n) <= x) of a sorted run
-__device__ __forceinline__ int count_lt(const unsigned* k, int n, unsigned x) {
-  int lo = 0, len = n;
-  while (len > 0) {
-    const int half = len >> 1;
-    const bool r = k[lo + half] < x;
-    lo = r ? lo + half + 1 : lo;
-    len = r ? len - half - 1 : half;
-  }
-  return lo;
-}
-__device__ __forceinline__ int count_le(const unsigned* k, int n, unsigned x) {
-  int lo = 0, len = n;
-  while (len > 0) {
-    const int half = len >> 1;
-    const bool r = k[lo + half] <= x;
-    lo = r ? lo + half + 1 : lo;
-    len = r ? len - half - 1 : half;
-  }
-  return lo;
-}
-
-// N sums over the workgroup behind one pair of barriers
-template <int N, typename T>
-__device__ __forceinline__ void block_sums(T (&v)[N], T (*scratch)[kWideWaves]) {
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    const T w = wave_sum(v[j]);
-    if (lane_id() == 0) scratch[j][wave_id()] = w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    T r = 0;
-#pragma unroll
-    for (int w = 0; w < kWideWaves; ++w) r += scratch[j][w];
-    v[j] = r;
-  }
-  __syncthreads();
-}
-
 // The sorted sides a (n1 finite keys) and b (n2): doubled rank sum of side a,
 // pooled tie term and the KS numerator, over the workgroup.
 __device__ __forceinline__ void rank_sides(const unsigned* a, int n1, const unsigned* b, int n2, WideShared* sh,

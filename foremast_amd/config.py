@@ -77,6 +77,10 @@ class BrainConfig:
     min_scale_points: int = 20               # MIN_SCALE_DATA_POINTS (finite samples per side)
     pairwise_scale_min_ratio: float = 1.0    # ML_PAIRWISE_SCALE_MIN_RATIO (>= 1; a design default, not measured)
     pairwise_scale_both: bool = False        # ML_PAIRWISE_SCALE_BOTH (a narrower current window flags too)
+    # per-pod test of the pairwise verdict (docs/BRAIN_SPEC.md 4.3, K29; off by default): Kruskal-Wallis over the
+    # baseline and the canary's pods, then Dunn's contrast per pod; a row it flags is "different"
+    pairwise_pod_test: str = ""              # ML_PAIRWISE_POD_TEST: "" | OFF | KRUSKAL_DUNN
+    min_pod_points: int = 5                  # MIN_POD_DATA_POINTS (finite samples a pod, and the baseline, need; >= 1)
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -236,6 +240,8 @@ class BrainConfig:
             "1", "true", "yes", "on") or c.pairwise_directional
         c.pairwise_scale_test = str(env.get("ML_PAIRWISE_SCALE_TEST", "") or "").strip() or c.pairwise_scale_test
         c.min_scale_points = _i(env, "MIN_SCALE_DATA_POINTS", c.min_scale_points)
+        c.pairwise_pod_test = str(env.get("ML_PAIRWISE_POD_TEST", "") or "").strip() or c.pairwise_pod_test
+        c.min_pod_points = _i(env, "MIN_POD_DATA_POINTS", c.min_pod_points)
         c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
         c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_scale_both

@@ -72,6 +72,7 @@ class Row:
     base: np.ndarray
     tags: str = ""
     series: str = ""        # "<namespace>/<app>": identity of the history across jobs (model cache key)
+    cur_pods: np.ndarray | None = None   # samples per pod series of ``cur``, in its pod-major order (None: one pod)
 
 
 @dataclass
@@ -148,6 +149,7 @@ class Brain(BrainStateMixin):
         zoo.canonical(self.cfg.ml_algorithm)   # validate early
         zoo.auto_candidates(self.cfg.auto_candidates)
         C.ScaleTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_SCALE_TEST or a ratio below 1 fails here
+        C.PodTest.from_config(self.cfg)        # an unknown ML_PAIRWISE_POD_TEST or MIN_POD_DATA_POINTS < 1 fails here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -230,7 +232,8 @@ class Brain(BrainStateMixin):
                 wk.namespace = _label(q, "namespace")
             if not wk.cluster:
                 wk.cluster = _label(q, "cluster")
-            wk.rows.append(Row(-1, alias, base_metric, hv, ht, cv, ct, bv))
+            wk.rows.append(Row(-1, alias, base_metric, hv, ht, cv, ct, bv,
+                               cur_pods=np.asarray([len(s.values) for s in cur.get(alias, [])], np.int64)))
         return wk
 
     # ------------------------------------------------------------------ score
@@ -250,12 +253,18 @@ class Brain(BrainStateMixin):
             base[i, :len(r.base)] = r.base
             if len(r.cur_t) and r.hist_t_last:
                 hor[i, :len(r.cur_t)] = np.maximum(1, np.rint((r.cur_t - r.hist_t_last) / self.step)).astype(np.int64)
+        # pod g of row i owns the columns [seg[i, g - 1], seg[i, g]) of cur (K29); a row without pod lengths is one pod
+        pods = [np.asarray([len(r.cur)] if r.cur_pods is None else r.cur_pods, np.int64) for r in rows]
+        seg = np.zeros((R, max([len(p) for p in pods] + [1])), np.int32)
+        for i, p in enumerate(pods):
+            seg[i, :len(p)] = np.cumsum(p)
+            seg[i, len(p):] = seg[i, len(p) - 1] if len(p) else 0
         dev = self.device
         t = lambda a: torch.from_numpy(a).to(dev)
-        return t(hist), T, t(cur), t(base), t(hor)
+        return t(hist), T, t(cur), t(base), t(hor), t(seg)
 
     def score_rows(self, rows: list[Row]):
-        hist, T, cur, base, hor = self._pack(rows)
+        hist, T, cur, base, hor, seg_end = self._pack(rows)
         tables = zoo.make_tables([r.alias for r in rows], self.cfg, self.device)
         R = len(rows)
         diff = None
@@ -271,6 +280,8 @@ class Brain(BrainStateMixin):
             diff = C.gate_diff(diff, cur, base, C.EffectGate.from_config(self.cfg), tables.bound, R)
             # scale test (K27, off by default), after the gate: the gate never clears a scale verdict
             diff = C.scale_diff(diff, cur, base, C.ScaleTest.from_config(self.cfg))
+            # per-pod test (K29, off by default), last: it only ever sets a verdict
+            diff = C.pods_diff(diff, cur, seg_end, base, C.PodTest.from_config(self.cfg))
         # Model dispatch: rows are grouped by their metric type's algorithm
         # (ml_algorithmN, else ML_ALGORITHM) and each group is ONE batched zoo
         # call over its rows (per-series model selection as a

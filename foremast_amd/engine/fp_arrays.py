@@ -388,6 +388,9 @@ class ArraysMixin:
         store = self.sliding if p0.sliding else self.static
         ga = self._arrays(works, key if key is not None else ("adhoc",) + p0.group)
         model = "moving_average_all"
+        if ga.base_d is not None and C.PodTest.from_config(self.b.cfg).enabled:
+            # the per-pod test (K29) needs the pod boundaries, which the resident tick's rows do not carry
+            return self._score_models(works, now, ga, store)
         band = self._band_route(p0, M, store)
         if band is not None:
             # a static group judged by the static band models, quantile_robust

@@ -290,6 +290,14 @@ class ModelsMixin:
                 diff = C.gate_diff(diff, ga.cur_dev, ga.base_d, gate, bound, M)
             # scale test (K27, off by default): a row whose spread differs is "different" whatever the gate said
             diff = C.scale_diff(diff, ga.cur_dev, ga.base_d, C.ScaleTest.from_config(cfg))
+            pods = C.PodTest.from_config(cfg)
+            if pods.enabled:
+                # per-pod test (K29): the window table keeps one slot per pod; windows fetched per job were
+                # concatenated before they got here and count as one pod each (the test then does not apply)
+                ends = (self.wt.pod_ends(ga.wcur) if ga.wcur is not None
+                        else np.asarray(ga.cur_len, np.int32).reshape(-1, 1))
+                seg = torch.from_numpy(np.minimum(ends, n).astype(np.int32)).to(dev)
+                diff = C.pods_diff(diff, ga.cur_dev, seg, ga.base_d, pods)
         NW = max(1, (n + 63) // 64)
         single = len(md.subs) == 1
         hpa_algo = zoo.canonical(cfg.hpa_forecast_algorithm) if (p0.hpa and cfg.hpa_forecast_algorithm) else None

@@ -716,6 +716,23 @@ class WindowTable:
         w = w[w >= 0]
         return int((self.nslot[w] * self.ncol[w]).max()) if len(w) else 0
 
+    def pod_ends(self, wids, G: int | None = None) -> np.ndarray:
+        """[R, G] int32: the column of :meth:`pack`'s row r at which the samples
+        of window ``wids[r]``'s slot (pod) g end -- the per-slot finite counts,
+        cumulated; a window with fewer slots repeats its last end, ``wids[r] <
+        0`` is all zero.  ``G`` defaults to the most slots of any window."""
+        w = np.ascontiguousarray(wids, np.int64).reshape(-1)
+        ok = w >= 0
+        wz = np.where(ok, w, 0)
+        nslot = np.where(ok, self.nslot[wz], 0).astype(np.int64)
+        G = max(1, int(nslot.max()) if len(w) else 1) if G is None else int(G)
+        cnt = np.zeros((len(w), G), np.int64)
+        for r in np.nonzero(nslot)[0]:
+            k = min(int(nslot[r]), G)
+            s0 = int(self.slot0[wz[r]])
+            cnt[r, :k] = np.isfinite(self.V[s0:s0 + k, :self.ncol[wz[r]]]).sum(1)
+        return np.cumsum(cnt, 1).astype(np.int32)
+
     def times_at(self, wids: np.ndarray, k: np.ndarray) -> np.ndarray:
         """Time of the ``k[i]``-th packed sample of window ``wids[i]`` (the
         order :meth:`pack` lays them out; NaN past the window's samples)."""

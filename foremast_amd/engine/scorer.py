@@ -217,6 +217,11 @@ class CanaryScorer:
         if self.scale.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the pairwise scale test (ML_PAIRWISE_SCALE_TEST) "
                              "enabled")
+        # per-pod test (K29): the scorer's rows carry no pod boundaries, so a tick with a baseline refuses the
+        # setting (_no_pods); without a baseline the test cannot apply and the tick is what it is with it off
+        self.pods = C.PodTest.from_config(cfg or BrainConfig())
+        if self.pods.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the per-pod test (ML_PAIRWISE_POD_TEST) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -323,6 +328,14 @@ class CanaryScorer:
         if self.scale.enabled:
             raise ValueError(f"{what} is not available with the pairwise scale test enabled "
                              "(it ticks through score / score_resident only)")
+        if self.pods.enabled:
+            raise ValueError(f"{what} is not available with the per-pod test (ML_PAIRWISE_POD_TEST) enabled")
+
+    def _no_pods(self, base) -> None:
+        if self.pods.enabled and base is not None and base.shape[1] > 0:
+            raise ValueError("CanaryScorer does not run the per-pod test (ML_PAIRWISE_POD_TEST): its rows carry no pod "
+                             "boundaries; score groups with a baseline op by op (ops.canary.pods_diff after "
+                             "pairwise_tests)")
 
     def _gate_into(self, cur, base, o: CanaryOutputs) -> CanaryOutputs:
         """K19 on the current stream, after the p-values of ``o`` exist and
@@ -382,6 +395,7 @@ class CanaryScorer:
         """``packed_out`` ([S, 4] fp32, optional): where the service verdicts
         go instead of the scorer's own buffer (one per in-flight tick when
         the consumer of tick k overlaps tick k+1)."""
+        self._no_pods(base)
         R = cur.shape[0]
         if self.robust:
             return self._score_robust(hist, base, cur, n_hist, packed_out)
@@ -469,6 +483,7 @@ class CanaryScorer:
         A view that carries a row-statistics cache (a static store's) has only
         the rows written since their last tick reduced again; a hand-made
         ``HistView`` without one streams every row, as does ``hist_cache=False``."""
+        self._no_pods(base)
         R = cur.shape[0]
         has_base = base is not None and base.shape[1] > 0
         if not cur.is_cuda:

@@ -39,6 +39,10 @@ _SIGS: dict[str, list] = {
     # scale_diff pvals_out stream (pvals_in / pvals_out may be null)
     "fm_pairwise_scale": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_float, c_float, c_float,
                           c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # K29: cur ld_c n_cur seg_end G base ld_b n_base R min_points p_thr tier pods pod_z pod_n pod_rank2 base_rank2
+    # tie pod_diff stream (seg_end and the [R, G] outputs may be null with G == 0)
+    "fm_pairwise_pods": [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_float,
+                         c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -521,6 +521,176 @@ def _scale_bucketed(cur, base, test: ScaleTest, pvals) -> ScaleResult:
         sc.index_copy_(0, wd, torch.from_numpy(s2).to(dev))
         sd.index_copy_(0, wd, torch.from_numpy(d2).to(dev))
     return ScaleResult(sc, sd, None if pvals is None else _force_pvals(pvals, sd))
+
+
+# most pods per row K29 takes (csrc/kernels/pairwise_pods.hip kPodMax: one lane per pod in its finishing pass)
+POD_MAX = 64
+POD_TESTS = {"": "", "OFF": "", "KRUSKAL_DUNN": "KRUSKAL_DUNN"}
+
+
+@dataclass(frozen=True)
+class PodTest:
+    """Per-pod canary test (K29, docs/BRAIN_SPEC.md 4.3): Kruskal-Wallis over the
+    baseline and the canary's pods, then Dunn's contrast of every pod against
+    the baseline.  A row it flags counts as "different" whatever the pooled
+    tests say; it never clears a verdict.  ``test == ""`` = off."""
+
+    test: str = ""                  # ML_PAIRWISE_POD_TEST: "" | OFF | KRUSKAL_DUNN
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD (the omnibus and the worst pod's p-value)
+    min_points: int = 5             # MIN_POD_DATA_POINTS: finite samples a pod, and the baseline, need
+
+    def __post_init__(self):
+        name = str(self.test or "").strip().upper()
+        if name not in POD_TESTS:
+            raise ValueError(f"unknown pairwise pod test {self.test!r} (KRUSKAL_DUNN or OFF)")
+        object.__setattr__(self, "test", POD_TESTS[name])
+        if int(self.min_points) < 1:
+            raise ValueError(f"min_points must be >= 1, got {self.min_points!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.test != ""
+
+    @classmethod
+    def from_config(cls, cfg) -> "PodTest":
+        """The pod test of a ``BrainConfig`` (``pairwise_pod_test``, ``min_pod_points`` and the pairwise threshold)."""
+        return cls(cfg.pairwise_pod_test, float(cfg.pairwise_threshold), int(cfg.min_pod_points))
+
+
+@dataclass
+class PodResult:
+    pods: torch.Tensor                   # [R, 6] fp32: H, p_H, z_worst, p_worst, worst, k
+    pod_z: torch.Tensor                  # [R, G] fp32: Dunn's z of every kept pod against the baseline
+    pod_n: torch.Tensor                  # [R, G] int32: finite samples of every kept pod
+    pod_rank2: torch.Tensor              # [R, G] int64: doubled rank sums
+    base_rank2: torch.Tensor             # [R] int64
+    tie: torch.Tensor                    # [R] int64: sum of t^3 - t over tie runs
+    pod_diff: torch.Tensor               # [R] int8
+
+    def tensors(self) -> tuple:
+        return (self.pods, self.pod_z, self.pod_n, self.pod_rank2, self.base_rank2, self.tie, self.pod_diff)
+
+
+def alloc_pods(R: int, G: int, device, fill: bool = False) -> PodResult:
+    """Output buffers of K29, which writes all of them for every row; ``fill``:
+    holding what a row without pods gets (NaN, worst = -1, zeros)."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+    o = PodResult(new((R, 6), torch.float32), new((R, G), torch.float32), new((R, G), torch.int32),
+                  new((R, G), torch.int64), new((R,), torch.int64), new((R,), torch.int64), new((R,), torch.int8))
+    if fill:
+        for t in o.tensors():
+            t.fill_(float("nan") if t.dtype == torch.float32 else 0)
+        o.pods[:, 4], o.pods[:, 5] = -1.0, 0.0
+    return o
+
+
+# rows ``pairwise_pods`` has sent down each route since the last reset:
+# "wave" / "wide" (K29's tiers), "host" (the numpy definition)
+_POD_ROUTE_ROWS = {"wave": 0, "wide": 0, "host": 0}
+
+
+def pod_route_rows() -> dict[str, int]:
+    """Rows of GPU batches per pod-test route so far (a copy)."""
+    return dict(_POD_ROUTE_ROWS)
+
+
+def reset_pod_route_rows() -> None:
+    for k in _POD_ROUTE_ROWS:
+        _POD_ROUTE_ROWS[k] = 0
+
+
+def _pods_host(cur, seg_end, base, test: PodTest) -> PodResult:
+    """The numpy definition on host arrays, as CPU tensors."""
+    o = ref.pairwise_pods(cur, seg_end, base, test.min_points)
+    return PodResult(*(torch.from_numpy(a) for a in o), torch.from_numpy(ref.pods_verdict(o[0], test.p_threshold)))
+
+
+def pairwise_pods(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+                  test: PodTest = PodTest("KRUSKAL_DUNN"), tier: str = "auto",
+                  out: PodResult | None = None) -> PodResult:
+    """Per-pod test of current vs baseline per row and its verdict.
+
+    ``cur`` [R, n_cur] is pod-major; ``seg_end`` [R, G] int32 holds the column
+    at which pod g's segment ends (cumulative; an empty pod repeats the
+    previous end).  CPU tensors run the numpy definition, GPU tensors K29: its
+    wave tier up to PAIRWISE_MAX pooled columns, its workgroup tier up to
+    PAIRWISE_WIDE_MAX (``tier="wide"`` runs it for any batch that fits); a
+    batch padded wider than that, or with more than POD_MAX pod columns, is
+    bucketed by the rows' own used widths like the pairwise tests, and only
+    rows really wider, or with more than POD_MAX pods, run the definition on
+    the host."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
+    check(seg_end.dim() == 2 and seg_end.shape[0] == R and seg_end.dtype == torch.int32 and seg_end.is_contiguous()
+          and seg_end.device == cur.device, "seg_end must be a contiguous int32 [R, G] tensor on the samples' device")
+    if not cur.is_cuda:
+        return _pods_host(cur.numpy(), seg_end.numpy(), base.numpy(), test)
+    require_native(cur)
+    n_cur, n_base, G = cur.shape[1], base.shape[1], seg_end.shape[1]
+    if n_cur + n_base > PAIRWISE_WIDE_MAX or G > POD_MAX:
+        return _pods_bucketed(cur, seg_end, base, test)
+    wide = tier == "wide" or n_cur + n_base > PAIRWISE_MAX
+    _POD_ROUTE_ROWS["wide" if wide else "wave"] += R
+    o = out if out is not None else alloc_pods(R, G, cur.device)
+    LIB.call("fm_pairwise_pods", ptr(cur), ldc, n_cur, ptr(seg_end) if G else None, G, ptr(base), ldb, n_base, R,
+             int(test.min_points), float(test.p_threshold), 2 if wide else 0, ptr(o.pods), ptr(o.pod_z), ptr(o.pod_n),
+             ptr(o.pod_rank2), ptr(o.base_rank2), ptr(o.tie), ptr(o.pod_diff), stream_of(cur))
+    return o
+
+
+def pods_diff(diff: torch.Tensor, cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+              test: PodTest) -> torch.Tensor:
+    """``diff | pod_diff`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``, after ``gate_diff`` and ``scale_diff``: the pod test
+    only ever sets a verdict)."""
+    if not test.enabled:
+        return diff
+    return diff | pairwise_pods(cur, seg_end, base, test).pod_diff.to(diff.dtype)
+
+
+def _pods_bucketed(cur, seg_end, base, test: PodTest) -> PodResult:
+    """A batch padded wider than K29 takes, or with more than POD_MAX pod
+    columns: rows bucketed by their own used widths exactly as
+    ``_pairwise_bucketed`` does (the wave tier, then the workgroup tier, each
+    on a narrowed copy whose segment ends are cut at the copy's width: the
+    columns cut off hold no finite sample).  A row whose pods past POD_MAX are
+    all empty loses only those columns; rows with more pods, and rows really
+    wider than PAIRWISE_WIDE_MAX, run the numpy definition on the host."""
+    R, G = seg_end.shape
+    dev = cur.device
+    Gk = min(G, POD_MAX)
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    many = (seg_end[:, POD_MAX - 1] != seg_end[:, -1]).cpu() if G > POD_MAX else torch.zeros((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, ~many, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~many & ~fit, PAIRWISE_WIDE_MAX)
+    o = alloc_pods(R, G, dev, fill=True)
+
+    def put(k, r):
+        for dst, src in zip(o.tensors(), r.tensors()):
+            if dst.dim() == 2 and dst.shape[1] == G:
+                dst[k, :src.shape[1]] = src.to(dev)
+            else:
+                dst[k] = src.to(dev)
+
+    for rows in (fit, wide):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            put(kd, pairwise_pods(cur.index_select(0, kd)[:, :a].contiguous(),
+                                  seg_end.index_select(0, kd)[:, :Gk].clamp(max=a).contiguous(),
+                                  base.index_select(0, kd)[:, :b].contiguous(), test))
+    w = torch.nonzero(~(fit | wide)).flatten()
+    if len(w):
+        _POD_ROUTE_ROWS["host"] += len(w)
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        put(wd, _pods_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
+                           seg_end.index_select(0, wd).clamp(max=a).cpu().numpy(),
+                           base.index_select(0, wd)[:, :b].cpu().numpy(), test))
+    return o
 
 
 @dataclass

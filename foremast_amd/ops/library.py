@@ -75,6 +75,27 @@ def _(cur, base, bound, min_effect, min_shift, min_shift_abs, directional):
     return (cur.new_empty((R, 4)), cur.new_empty((R, 2), dtype=torch.int32), cur.new_empty((R,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K29
+@custom_op(f"{NS}::pairwise_pods", mutates_args=())
+def pairwise_pods(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor, p_threshold: float,
+                  min_points: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(pods [R, 6] = H, p_H, z_worst, p_worst, worst, k; pod_z [R, G]; pod_diff
+    [R] int8) of the per-pod Kruskal-Wallis / Dunn test; pod g of a row owns
+    the columns [seg_end[g - 1], seg_end[g]) of ``cur`` (K29)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(seg_end.dim() == 2 and seg_end.shape[0] == cur.shape[0] and seg_end.dtype == torch.int32,
+          "seg_end must be int32 [R, G]")
+    r = C.pairwise_pods(cur.contiguous(), seg_end.contiguous(), base.contiguous(),
+                        C.PodTest("KRUSKAL_DUNN", p_threshold, min_points))
+    return r.pods.clone(), r.pod_z.clone(), r.pod_diff.clone()
+
+
+@register_fake(f"{NS}::pairwise_pods")
+def _(cur, seg_end, base, p_threshold, min_points):
+    R = cur.shape[0]
+    return (cur.new_empty((R, 6)), cur.new_empty((R, seg_end.shape[1])), cur.new_empty((R,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -201,5 +222,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

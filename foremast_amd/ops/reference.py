@@ -532,3 +532,91 @@ def scale_verdict(scale, p_thr, min_ratio: float = 1.0, both: bool = False):
         if both:
             hit = hit | (ratio <= f(1.0) / f(min_ratio))
         return (~np.isnan(p) & (p < f(p_thr)) & hit).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# per-pod test of current vs baseline (K29): Kruskal-Wallis over the baseline
+# and the canary's pods as groups, then Dunn's contrast of every pod against
+# the baseline, straight from the definitions in docs/BRAIN_SPEC.md section 4.3
+
+
+def pairwise_pods(cur, seg_end, base, min_points: int = 5):
+    """(pods [R, 6] fp32 = (H, p_H, z_worst, p_worst, worst, k), pod_z [R, G]
+    fp32, pod_n [R, G] int32, pod_rank2 [R, G] int64, base_rank2 [R] int64,
+    tie [R] int64) per row.
+
+    ``cur`` is pod-major and pod g owns the columns [seg_end[g - 1],
+    seg_end[g]); NaN / +-inf are missing.  A pod with fewer than
+    max(min_points, 1) finite samples is dropped (n = 0, z = NaN, rank2 = 0).
+    Over the N pooled values of the baseline (group 0) and the k kept pods:
+    average ranks, as exact integers the doubled rank sums and the tie term
+    sum(t^3 - t); then in fp64, each line left to right, rounded to fp32 once:
+    C = 1 - tie / (N^3 - N), H = (12 / (N (N + 1)) sum_g (rank2_g / 2)^2 / n_g
+    - 3 (N + 1)) / C, p_H = the chi-square tail of H at k degrees of freedom,
+    sigma2 = N (N + 1) / 12 - tie / (12 (N - 1)), z_g = (rank2_g / (2 n_g) -
+    rank2_0 / (2 n_0)) / sqrt(sigma2 (1 / n_g + 1 / n_0)), p_g = min(1, k
+    erfc(|z_g| / sqrt 2)); worst = the kept pod with the largest |z_g| (the
+    lowest on ties).  Not applicable (H, p_H, z_worst, p_worst and every z_g
+    NaN, worst = -1) when k < 2, the baseline has fewer than max(min_points,
+    1) finite samples or C <= 0; the integers and k are reported regardless."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    seg = np.asarray(seg_end, dtype=np.int64)
+    R, G = seg.shape
+    pods = np.full((R, 6), np.nan, dtype=np.float32)
+    pods[:, 4], pods[:, 5] = -1.0, 0.0
+    pod_z = np.full((R, G), np.nan, dtype=np.float32)
+    pod_n = np.zeros((R, G), dtype=np.int32)
+    pod_rank2 = np.zeros((R, G), dtype=np.int64)
+    base_rank2 = np.zeros(R, dtype=np.int64)
+    tie = np.zeros(R, dtype=np.int64)
+    need = max(int(min_points), 1)
+    for r in range(R):
+        groups, kept, lo = [base[r][np.isfinite(base[r])]], [], 0
+        for g in range(G):
+            x = cur[r, lo:max(lo, seg[r, g])]
+            lo = max(lo, int(seg[r, g]))
+            x = x[np.isfinite(x)]
+            if len(x) >= need:
+                kept.append(g)
+                groups.append(x)
+        k = len(kept)
+        pods[r, 5] = k
+        pooled = np.concatenate(groups).astype(np.float64)          # (-0.0 == 0.0: one tie run)
+        srt = np.sort(pooled)
+        lt, le = np.searchsorted(srt, pooled, "left"), np.searchsorted(srt, pooled, "right")
+        t = (le - lt).astype(np.int64)
+        rank2 = 2 * lt.astype(np.int64) + t + 1
+        n = np.array([len(x) for x in groups], dtype=np.int64)
+        r2 = np.add.reduceat(rank2, np.concatenate([[0], np.cumsum(n)[:-1]])) * (n > 0) if len(pooled) else 0 * n
+        tie[r] = int((t * t - 1).sum())
+        base_rank2[r] = r2[0]
+        pod_n[r, kept], pod_rank2[r, kept] = n[1:], r2[1:]
+        if k < 2 or n[0] < need:
+            continue
+        dN, dt = float(n.sum()), float(tie[r])
+        C = 1.0 - dt / (dN * dN * dN - dN)
+        if not C > 0.0:
+            continue
+        dn, dr = n.astype(np.float64), r2.astype(np.float64)
+        s = 0.0
+        for g in range(k + 1):
+            s += (dr[g] / 2.0) ** 2 / dn[g]
+        H = (12.0 / (dN * (dN + 1.0)) * s - 3.0 * (dN + 1.0)) / C
+        var = dN * (dN + 1.0) / 12.0 - dt / (12.0 * (dN - 1.0))
+        z = (dr[1:] / (2.0 * dn[1:]) - dr[0] / (2.0 * dn[0])) / np.sqrt(var * (1.0 / dn[1:] + 1.0 / dn[0]))
+        w = int(np.argmax(np.abs(z)))
+        pods[r, :5] = (H, special.chdtrc(k, H) if H > 0 else 1.0, z[w],
+                       min(1.0, k * special.erfc(abs(z[w]) / np.sqrt(2.0))), kept[w])
+        pod_z[r, kept] = z
+    return pods, pod_z, pod_n, pod_rank2, base_rank2, tie
+
+
+def pods_verdict(pods, p_thr):
+    """pod_diff [R] int8 of the per-pod test: 1 where the test applies (p_H is
+    a number) and both the omnibus p_H and the worst pod's Bonferroni p-value
+    are below fp32(p_thr), compared in fp32 as the decision compares the six
+    tests' p-values."""
+    p = np.asarray(pods, dtype=np.float32)
+    with np.errstate(invalid="ignore"):
+        return (~np.isnan(p[:, 1]) & (p[:, 1] < np.float32(p_thr)) & (p[:, 3] < np.float32(p_thr))).astype(np.int8)
