@@ -81,6 +81,10 @@ class BrainConfig:
     # baseline and the canary's pods, then Dunn's contrast per pod; a row it flags is "different"
     pairwise_pod_test: str = ""              # ML_PAIRWISE_POD_TEST: "" | OFF | KRUSKAL_DUNN
     min_pod_points: int = 5                  # MIN_POD_DATA_POINTS (finite samples a pod, and the baseline, need; >= 1)
+    # joint multi-metric test of the pairwise verdict (docs/BRAIN_SPEC.md 4.4, K30; off by default): the multivariate
+    # rank-sum statistic over the metrics of a job; a group it flags is "different" on every member row
+    pairwise_joint_test: str = ""            # ML_PAIRWISE_JOINT_TEST: "" | OFF | RANK_SUM
+    min_joint_points: int = 20               # MIN_JOINT_DATA_POINTS (kept columns each side needs; >= 1)
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -242,6 +246,8 @@ class BrainConfig:
         c.min_scale_points = _i(env, "MIN_SCALE_DATA_POINTS", c.min_scale_points)
         c.pairwise_pod_test = str(env.get("ML_PAIRWISE_POD_TEST", "") or "").strip() or c.pairwise_pod_test
         c.min_pod_points = _i(env, "MIN_POD_DATA_POINTS", c.min_pod_points)
+        c.pairwise_joint_test = str(env.get("ML_PAIRWISE_JOINT_TEST", "") or "").strip() or c.pairwise_joint_test
+        c.min_joint_points = _i(env, "MIN_JOINT_DATA_POINTS", c.min_joint_points)
         c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
         c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_scale_both

@@ -150,6 +150,7 @@ class Brain(BrainStateMixin):
         zoo.auto_candidates(self.cfg.auto_candidates)
         C.ScaleTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_SCALE_TEST or a ratio below 1 fails here
         C.PodTest.from_config(self.cfg)        # an unknown ML_PAIRWISE_POD_TEST or MIN_POD_DATA_POINTS < 1 fails here
+        C.JointTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_JOINT_TEST or MIN_JOINT_DATA_POINTS < 1 fails here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -282,6 +283,11 @@ class Brain(BrainStateMixin):
             diff = C.scale_diff(diff, cur, base, C.ScaleTest.from_config(self.cfg))
             # per-pod test (K29, off by default), last: it only ever sets a verdict
             diff = C.pods_diff(diff, cur, seg_end, base, C.PodTest.from_config(self.cfg))
+            # joint test over the metrics of a job (K30, off by default), last: it only ever sets a verdict
+            joint = C.JointTest.from_config(self.cfg)
+            if joint.enabled:
+                jrows, jk = self._joint_groups(rows)
+                diff = C.joint_diff(diff, cur, base, jrows.to(self.device), jk.to(self.device), joint)
         # Model dispatch: rows are grouped by their metric type's algorithm
         # (ml_algorithmN, else ML_ALGORITHM) and each group is ONE batched zoo
         # call over its rows (per-series model selection as a
@@ -502,6 +508,23 @@ class Brain(BrainStateMixin):
         for i, r in enumerate(rows):
             by_job.setdefault(r.job, []).append(i)
         return zoo.mvn_groups(by_job.values())
+
+    @staticmethod
+    def _joint_groups(rows: list[Row]):
+        """Groups of the joint canary test (K30): ``_groups`` over the rows
+        whose columns line up with those of their job's first row (the same pod
+        lengths, sample times and baseline length); a job left with fewer than
+        two such rows has no group.  Returns (rows [G, 8] int32, K [G])."""
+        def lined_up(a: Row, b: Row) -> bool:
+            pa = [len(a.cur)] if a.cur_pods is None else a.cur_pods
+            pb = [len(b.cur)] if b.cur_pods is None else b.cur_pods
+            return np.array_equal(pa, pb) and np.array_equal(a.cur_t, b.cur_t) and len(a.base) == len(b.base)
+
+        by_job: dict[int, list[int]] = {}
+        for i, r in enumerate(rows):
+            by_job.setdefault(r.job, []).append(i)
+        g, k, _ = zoo.mvn_groups([[i for i in idx if lined_up(rows[idx[0]], rows[i])] for idx in by_job.values()])
+        return g, k
 
     # ------------------------------------------------------------------ cycle
     def run_once(self) -> dict:

@@ -298,6 +298,17 @@ class ModelsMixin:
                         else np.asarray(ga.cur_len, np.int32).reshape(-1, 1))
                 seg = torch.from_numpy(np.minimum(ends, n).astype(np.int32)).to(dev)
                 diff = C.pods_diff(diff, ga.cur_dev, seg, ga.base_d, pods)
+            joint = C.JointTest.from_config(cfg)
+            if joint.enabled and M >= 2:
+                # joint test (K30): the M rows of a job whose columns line up with its first row's -- the same
+                # per-pod counts (table windows) or length, sample times and baseline length -- in chunks of 8
+                ends = (self.wt.pod_ends(ga.wcur) if ga.wcur is not None
+                        else np.asarray(ga.cur_len, np.int64).reshape(-1, 1))
+                key = np.concatenate([ends.astype(np.float64), C.used_width(ga.base_d).cpu().numpy()[:, None],
+                                      np.nan_to_num(np.asarray(ga.cur_t, np.float64), nan=-1.0)], 1).reshape(S, M, -1)
+                same = (key == key[:, :1]).all(2)
+                jrows, jk, _ = zoo.mvn_groups([np.flatnonzero(same[s]) + s * M for s in range(S)])
+                diff = C.joint_diff(diff, ga.cur_dev, ga.base_d, jrows.to(dev), jk.to(dev), joint)
         NW = max(1, (n + 63) // 64)
         single = len(md.subs) == 1
         hpa_algo = zoo.canonical(cfg.hpa_forecast_algorithm) if (p0.hpa and cfg.hpa_forecast_algorithm) else None

@@ -222,6 +222,10 @@ class CanaryScorer:
         self.pods = C.PodTest.from_config(cfg or BrainConfig())
         if self.pods.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the per-pod test (ML_PAIRWISE_POD_TEST) enabled")
+        # joint test (K30): not part of the tick yet; refused like the per-pod test (_no_pods)
+        self.joint = C.JointTest.from_config(cfg or BrainConfig())
+        if self.joint.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the joint test (ML_PAIRWISE_JOINT_TEST) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -330,8 +334,13 @@ class CanaryScorer:
                              "(it ticks through score / score_resident only)")
         if self.pods.enabled:
             raise ValueError(f"{what} is not available with the per-pod test (ML_PAIRWISE_POD_TEST) enabled")
+        if self.joint.enabled:
+            raise ValueError(f"{what} is not available with the joint test (ML_PAIRWISE_JOINT_TEST) enabled")
 
     def _no_pods(self, base) -> None:
+        if self.joint.enabled and base is not None and base.shape[1] > 0:
+            raise ValueError("CanaryScorer does not run the joint test (ML_PAIRWISE_JOINT_TEST) yet; score groups "
+                             "with a baseline op by op (ops.canary.joint_diff after pairwise_tests)")
         if self.pods.enabled and base is not None and base.shape[1] > 0:
             raise ValueError("CanaryScorer does not run the per-pod test (ML_PAIRWISE_POD_TEST): its rows carry no pod "
                              "boundaries; score groups with a baseline op by op (ops.canary.pods_diff after "

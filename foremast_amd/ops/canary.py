@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -690,6 +690,177 @@ def _pods_bucketed(cur, seg_end, base, test: PodTest) -> PodResult:
         put(wd, _pods_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
                            seg_end.index_select(0, wd).clamp(max=a).cpu().numpy(),
                            base.index_select(0, wd)[:, :b].cpu().numpy(), test))
+    return o
+
+
+# most members per group K30 takes (csrc/kernels/pairwise_joint.hip kJointMembers: one wave per member)
+JOINT_MAX_K = ref.JOINT_MAX_K
+JOINT_TESTS = {"": "", "OFF": "", "RANK_SUM": "RANK_SUM"}
+
+
+@dataclass(frozen=True)
+class JointTest:
+    """Joint multi-metric canary test (K30, docs/BRAIN_SPEC.md 4.4): the
+    Puri-Sen multivariate rank-sum statistic over the metrics of a job.  A
+    group it flags counts as "different" on every member row whatever the
+    per-row tests say; it never clears a verdict.  ``test == ""`` = off."""
+
+    test: str = ""                  # ML_PAIRWISE_JOINT_TEST: "" | OFF | RANK_SUM
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD
+    min_points: int = 20            # MIN_JOINT_DATA_POINTS: kept columns each side needs
+
+    def __post_init__(self):
+        name = str(self.test or "").strip().upper()
+        if name not in JOINT_TESTS:
+            raise ValueError(f"unknown pairwise joint test {self.test!r} (RANK_SUM or OFF)")
+        object.__setattr__(self, "test", JOINT_TESTS[name])
+        if int(self.min_points) < 1:
+            raise ValueError(f"min_points must be >= 1, got {self.min_points!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.test != ""
+
+    @classmethod
+    def from_config(cls, cfg) -> "JointTest":
+        """The joint test of a ``BrainConfig`` (``pairwise_joint_test``, ``min_joint_points`` and the pairwise
+        threshold)."""
+        return cls(cfg.pairwise_joint_test, float(cfg.pairwise_threshold), int(cfg.min_joint_points))
+
+
+@dataclass
+class JointResult:
+    joint: torch.Tensor                  # [G, 6] fp32: L, p, dof, z_worst, worst, N
+    n12: torch.Tensor                    # [G, 2] int32: kept current / baseline columns
+    T: torch.Tensor                      # [G, 8] int64: centred doubled rank sums of the current side
+    A: torch.Tensor                      # [G, 8, 8] int64: Gram matrix of the centred doubled ranks
+    member_z: torch.Tensor               # [G, 8] fp32: every member's marginal z
+    joint_diff: torch.Tensor             # [G] int8
+
+    def tensors(self) -> tuple:
+        return (self.joint, self.n12, self.T, self.A, self.member_z, self.joint_diff)
+
+
+def alloc_joint(G: int, device) -> JointResult:
+    """Output buffers of K30, which writes all of them for every group."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+    return JointResult(new((G, 6), torch.float32), new((G, 2), torch.int32), new((G, JOINT_MAX_K), torch.int64),
+                       new((G, JOINT_MAX_K, JOINT_MAX_K), torch.int64), new((G, JOINT_MAX_K), torch.float32),
+                       new((G,), torch.int8))
+
+
+# groups ``pairwise_joint`` has sent down each route since the last reset:
+# "wave" (K30), "host" (the numpy definition)
+_JOINT_ROUTE_ROWS = {"wave": 0, "host": 0}
+
+
+def joint_route_rows() -> dict[str, int]:
+    """Groups of GPU batches per joint-test route so far (a copy)."""
+    return dict(_JOINT_ROUTE_ROWS)
+
+
+def reset_joint_route_rows() -> None:
+    for k in _JOINT_ROUTE_ROWS:
+        _JOINT_ROUTE_ROWS[k] = 0
+
+
+def _joint_host(cur, base, rows, K, test: JointTest) -> JointResult:
+    """The numpy definition on host arrays, as CPU tensors."""
+    o = ref.pairwise_joint(cur, base, rows, K, test.min_points)
+    return JointResult(*(torch.from_numpy(a) for a in o), torch.from_numpy(ref.joint_verdict(o[0], test.p_threshold)))
+
+
+def pairwise_joint(cur: torch.Tensor, base: torch.Tensor, rows: torch.Tensor, K: torch.Tensor,
+                   test: JointTest = JointTest("RANK_SUM"), out: JointResult | None = None) -> JointResult:
+    """Joint rank-sum test of current vs baseline per group and its verdict.
+
+    ``rows`` [G, 8] int32 (-1 padded) names the member rows of every group,
+    ``K`` [G] their number (1..8), as ``zoo.mvn_groups`` makes them; column c
+    of every member of a group is the same sample.  CPU tensors run the numpy
+    definition, GPU tensors K30 for up to PAIRWISE_MAX pooled columns.  A batch
+    padded wider than that is narrowed by the used widths of the groups' rows
+    (the columns cut off are missing in every member), and only groups really
+    wider run the definition on the host."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(rows.dim() == 2 and rows.shape[1] == JOINT_MAX_K and rows.dtype == torch.int32 and rows.is_contiguous()
+          and rows.device == cur.device, "rows must be a contiguous int32 [G, 8] tensor on the samples' device")
+    G = rows.shape[0]
+    check(K.dim() == 1 and K.shape[0] == G and not K.is_floating_point(), "K must be an integer [G] tensor")
+    K = K.to(device=cur.device, dtype=torch.int32).contiguous()
+    if not cur.is_cuda:
+        check(G == 0 or (int(K.min()) >= 1 and int(K.max()) <= JOINT_MAX_K), "K must lie in 1..8")
+        return _joint_host(cur.numpy(), base.numpy(), rows.numpy(), K.numpy(), test)
+    require_native(cur)
+    n_cur, n_base = cur.shape[1], base.shape[1]
+    if n_cur + n_base > PAIRWISE_MAX:
+        return _joint_bucketed(cur, base, rows, K, test)
+    _JOINT_ROUTE_ROWS["wave"] += G
+    o = out if out is not None else alloc_joint(G, cur.device)
+    LIB.call("fm_pairwise_joint", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, ptr(rows), ptr(K), G,
+             int(test.min_points), float(test.p_threshold), ptr(o.joint), ptr(o.n12), ptr(o.T), ptr(o.A),
+             ptr(o.member_z), ptr(o.joint_diff), stream_of(cur))
+    return o
+
+
+def joint_diff(diff: torch.Tensor, cur: torch.Tensor, base: torch.Tensor, rows: torch.Tensor, K: torch.Tensor,
+               test: JointTest) -> torch.Tensor:
+    """``diff`` with the verdict of every group ORed into all of its member
+    rows, for the op-by-op model paths (``diff`` from ``pairwise_tests``, after
+    ``gate_diff``, ``scale_diff`` and ``pods_diff``: the joint test only ever
+    sets a verdict).  ``diff`` itself when the test is off or there is no group."""
+    if not test.enabled or rows.shape[0] == 0:
+        return diff
+    hit = pairwise_joint(cur, base, rows, K, test).joint_diff.to(device=diff.device, dtype=diff.dtype)
+    member = (torch.arange(JOINT_MAX_K, device=diff.device)[None, :] < K.to(diff.device)[:, None]) & (rows >= 0)
+    flagged = torch.zeros_like(diff).index_put_((rows[member].long(),), hit[:, None].expand(-1, JOINT_MAX_K)[member],
+                                                accumulate=True)
+    return diff | (flagged > 0).to(diff.dtype)
+
+
+def _joint_bucketed(cur, base, rows, K, test: JointTest) -> JointResult:
+    """A batch padded wider than K30 takes: a group is as wide as the widest
+    used width among its member rows, per side.  The groups that fit
+    PAIRWISE_MAX by ``_bucket``'s rule run K30 on the batch cut to their
+    widths (a view: a column cut off is missing in every member of such a
+    group); groups really
+    wider run the numpy definition on the host, on their own rows."""
+    G = rows.shape[0]
+    dev = cur.device
+    member = (torch.arange(JOINT_MAX_K, device=dev)[None, :] < K[:, None]) & (rows >= 0)
+    at = rows.clamp(min=0).long()
+    width = lambda x: (used_width(x)[at] * member).amax(1).cpu()  # noqa: E731
+    lc, lb = width(cur), width(base)
+    o = alloc_joint(G, dev)
+    left = (lc + lb) <= PAIRWISE_MAX
+    host = ~left
+    while left.any():
+        # (groups that fit alone but not next to each other, a wide current beside a wide baseline, take turns)
+        fit = _bucket(lc, lb, left, PAIRWISE_MAX)
+        if not fit.any():
+            fit = left & (torch.cumsum(left.to(torch.int64), 0) == 1)
+        left = left & ~fit
+        k = torch.nonzero(fit).flatten()
+        a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+        kd = k.to(dev)
+        r = pairwise_joint(cur[:, :a], base[:, :b], rows.index_select(0, kd).contiguous(), K.index_select(0, kd), test)
+        for dst, src in zip(o.tensors(), r.tensors()):
+            dst[kd] = src
+    w = torch.nonzero(host).flatten()
+    if len(w):
+        _JOINT_ROUTE_ROWS["host"] += len(w)
+        wd = w.to(dev)
+        # the host gets the member rows alone, renumbered in group order
+        sel = member.index_select(0, wd)
+        idx = at.index_select(0, wd)[sel]
+        sub = torch.full((len(w), JOINT_MAX_K), -1, dtype=torch.int32)
+        sub[sel.cpu()] = torch.arange(len(idx), dtype=torch.int32)
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        r = _joint_host(cur.index_select(0, idx)[:, :a].cpu().numpy(), base.index_select(0, idx)[:, :b].cpu().numpy(),
+                        sub.numpy(), K.index_select(0, wd).cpu().numpy(), test)
+        for dst, src in zip(o.tensors(), r.tensors()):
+            dst[wd] = src.to(dev)
     return o
 
 

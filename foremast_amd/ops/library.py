@@ -96,6 +96,27 @@ def _(cur, seg_end, base, p_threshold, min_points):
     return (cur.new_empty((R, 6)), cur.new_empty((R, seg_end.shape[1])), cur.new_empty((R,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K30
+@custom_op(f"{NS}::pairwise_joint", mutates_args=())
+def pairwise_joint(cur: torch.Tensor, base: torch.Tensor, rows: torch.Tensor, K: torch.Tensor, p_threshold: float,
+                   min_points: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(joint [G, 6] = L, p, dof, z_worst, worst, N; member_z [G, 8]; joint_diff
+    [G] int8) of the multivariate rank-sum test over the member rows ``rows``
+    [G, 8] int32 (-1 padded, ``K`` [G] of them) of every group (K30)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(rows.dim() == 2 and rows.shape[1] == C.JOINT_MAX_K and rows.dtype == torch.int32 and
+          K.shape == rows.shape[:1], "rows must be int32 [G, 8] and K [G]")
+    r = C.pairwise_joint(cur.contiguous(), base.contiguous(), rows.contiguous(), K,
+                         C.JointTest("RANK_SUM", p_threshold, min_points))
+    return r.joint.clone(), r.member_z.clone(), r.joint_diff.clone()
+
+
+@register_fake(f"{NS}::pairwise_joint")
+def _(cur, base, rows, K, p_threshold, min_points):
+    G = rows.shape[0]
+    return (cur.new_empty((G, 6)), cur.new_empty((G, C.JOINT_MAX_K)), cur.new_empty((G,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -222,5 +243,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

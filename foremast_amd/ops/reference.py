@@ -620,3 +620,103 @@ def pods_verdict(pods, p_thr):
     p = np.asarray(pods, dtype=np.float32)
     with np.errstate(invalid="ignore"):
         return (~np.isnan(p[:, 1]) & (p[:, 1] < np.float32(p_thr)) & (p[:, 3] < np.float32(p_thr))).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# joint multi-metric test of current vs baseline (K30): the Puri-Sen
+# multivariate rank-sum statistic over the metrics of a job, straight from the
+# definition in docs/BRAIN_SPEC.md section 4.4
+
+JOINT_MAX_K = 8
+
+
+def pairwise_joint(cur, base, rows, K, min_points: int = 20):
+    """(joint [G, 6] fp32 = (L, p, dof, z_worst, worst, N), n12 [G, 2] int32,
+    T [G, 8] int64, A [G, 8, 8] int64, member_z [G, 8] fp32) per group.
+
+    Member j of group g is row ``rows[g, j]`` (j < K[g] <= 8) of ``cur`` /
+    ``base``; column c of every member is the same sample.  NaN / +-inf are
+    missing, and a column counts only where every member is finite (n1 current
+    and n2 baseline columns kept, N = n1 + n2).  Per member the midranks over
+    its N kept pooled values (-0.0 == 0.0) as exact integers rank2 = 2 lt + t +
+    1, centred: a_j = rank2_j - (N + 1).  T_j = sum of a_j over the kept
+    current columns, A_jk = sum of a_j a_k over all kept columns (int64).  Then
+    in fp64, in member order, each line left to right, over the members kept
+    so far: l_jk = (A_jk - sum_{m<k} l_jm l_km d_m) / d_k, d_j = A_jj - sum_k
+    l_jk^2 d_k, y_j = T_j - sum_k l_jk y_k; member j is dropped when A_jj == 0
+    or d_j <= 1e-9 A_jj (constant, or rank-collinear with those before it);
+    dof = the number kept.  L = N (N - 1) / (n1 n2) sum_j y_j^2 / d_j, p = the
+    chi-square tail of L at dof degrees of freedom (1 where L <= 0); z_j = T_j
+    / sqrt(n1 n2 / (N (N - 1)) A_jj) (NaN where A_jj == 0), worst = the member
+    with the largest |z_j| (the lowest on ties).  Not applicable (L, p,
+    z_worst and every z_j NaN, worst = -1) when n1 or n2 < max(min_points, 1)
+    or dof == 0; the integers are reported regardless.  Everything is rounded
+    to fp32 once."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, JOINT_MAX_K)
+    K = np.asarray(K, dtype=np.int64).reshape(-1)
+    G = len(K)
+    joint = np.full((G, 6), np.nan, dtype=np.float32)
+    joint[:, 2], joint[:, 4], joint[:, 5] = 0.0, -1.0, 0.0
+    n12 = np.zeros((G, 2), dtype=np.int32)
+    T = np.zeros((G, JOINT_MAX_K), dtype=np.int64)
+    A = np.zeros((G, JOINT_MAX_K, JOINT_MAX_K), dtype=np.int64)
+    member_z = np.full((G, JOINT_MAX_K), np.nan, dtype=np.float32)
+    need = max(int(min_points), 1)
+    for g in range(G):
+        k = int(K[g])
+        c, b = cur[rows[g, :k]], base[rows[g, :k]]
+        kc, kb = np.isfinite(c).all(0), np.isfinite(b).all(0)
+        n1, n2 = int(kc.sum()), int(kb.sum())
+        N = n1 + n2
+        x = np.concatenate([c[:, kc], b[:, kb]], axis=1).astype(np.float64)
+        a = np.zeros((k, N), dtype=np.int64)
+        for j in range(k):
+            srt = np.sort(x[j])
+            a[j] = np.searchsorted(srt, x[j], "left") + np.searchsorted(srt, x[j], "right") - N   # rank2 - (N + 1)
+        T[g, :k], A[g, :k, :k] = a[:, :n1].sum(1), a @ a.T
+        n12[g], joint[g, 5] = (n1, n2), N
+        Tg, Ag = T[g].astype(np.float64), A[g].astype(np.float64)
+        kept, d, y, l = [], np.zeros(k), np.zeros(k), np.zeros((k, k))
+        q = 0.0
+        for j in range(k):
+            for kk in kept:
+                s = 0.0
+                for m in kept:
+                    if m < kk:
+                        s += l[j, m] * l[kk, m] * d[m]
+                l[j, kk] = (Ag[j, kk] - s) / d[kk]
+            s, t = 0.0, 0.0
+            for kk in kept:
+                s += l[j, kk] * l[j, kk] * d[kk]
+            for kk in kept:
+                t += l[j, kk] * y[kk]
+            dj, yj = Ag[j, j] - s, Tg[j] - t
+            if Ag[j, j] == 0.0 or dj <= 1e-9 * Ag[j, j]:
+                continue
+            kept.append(j)
+            d[j], y[j] = dj, yj
+            q += yj * yj / dj
+        dof = len(kept)
+        joint[g, 2] = dof
+        if n1 < need or n2 < need or dof == 0:
+            continue
+        dN, d12 = float(N), float(n1) * float(n2)
+        L = dN * (dN - 1.0) / d12 * q
+        z = np.full(k, np.nan)
+        nz = np.diag(Ag)[:k] != 0.0
+        z[nz] = Tg[:k][nz] / np.sqrt(d12 / (dN * (dN - 1.0)) * np.diag(Ag)[:k][nz])
+        w = int(np.argmax(np.nan_to_num(np.abs(z), nan=-1.0)))
+        joint[g, :5] = (L, special.chdtrc(dof, L) if L > 0 else 1.0, dof, z[w], w)
+        member_z[g, :k] = z
+    return joint, n12, T, A, member_z
+
+
+def joint_verdict(joint, p_thr):
+    """joint_diff [G] int8 of the joint test: 1 where the test applies (p is a
+    number) and p is below fp32(p_thr), compared in fp32 as ``pods_verdict``
+    compares."""
+    p = np.asarray(joint, dtype=np.float32).reshape(-1, 6)[:, 1]
+    with np.errstate(invalid="ignore"):
+        return (~np.isnan(p) & (p < np.float32(p_thr))).astype(np.int8)
