@@ -52,7 +52,7 @@
 // tails and the verdict.  kPodMax is the wave width, so no pass loops over
 // pods.
 #include "fm_pairwise.h"
-#include "fm_lds_sort.h"
+#include "fm_segments.h"
 
 namespace {
 
@@ -86,25 +86,8 @@ struct PodWideShared {
 // profiles/pod_test_resources.txt; held to 128 the finishing pass spills)
 static_assert(sizeof(PodWideShared) <= kLaunchLds && 4 * sizeof(PodWideShared) <= 160 * 1024, "LDS of a workgroup");
 
-// LDS written by some lanes of this wave is read by others (wave tier): the
-// wave's LDS operations complete in order; this keeps the compiler from moving
-// them across and waits for the stores.
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __device__ __forceinline__ double lane_bcast_f64(double v, int lane) {
   return __hiloint2double(lane_bcast(__double2hiint(v), lane), lane_bcast(__double2loint(v), lane));
-}
-
-// The group of column i of the pooled row (0 = baseline, g + 1 = pod g, -1 =
-// none): columns [0, n_cur) are the current window's, the baseline follows.
-__device__ __forceinline__ int group_of(const unsigned* seg, int G, int i, int n_cur, int n_pooled) {
-  if (i >= n_cur) return i < n_pooled ? 0 : -1;
-  const int pod = count_le(seg, G, (unsigned)i);
-  return pod < G ? pod + 1 : -1;
 }
 
 // The finishing pass of a row, run by one whole wave once the bins are

@@ -85,6 +85,11 @@ class BrainConfig:
     # rank-sum statistic over the metrics of a job; a group it flags is "different" on every member row
     pairwise_joint_test: str = ""            # ML_PAIRWISE_JOINT_TEST: "" | OFF | RANK_SUM
     min_joint_points: int = 20               # MIN_JOINT_DATA_POINTS (kept columns each side needs; >= 1)
+    # drift test of the pairwise verdict (docs/BRAIN_SPEC.md 4.5, K31; off by default): the Mann-Kendall trend of the
+    # canary's samples over time, stratified by pod, against the baseline's own trend; a row it flags is "different"
+    pairwise_drift_test: str = ""            # ML_PAIRWISE_DRIFT_TEST: "" | OFF | MANN_KENDALL
+    min_drift_points: int = 10               # MIN_DRIFT_DATA_POINTS (finite samples a pod, and the baseline, need; >= 3)
+    drift_min_tau: float = 0.0               # ML_PAIRWISE_DRIFT_MIN_TAU (floor on |tau| of the current side; in [0, 1])
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -248,6 +253,9 @@ class BrainConfig:
         c.min_pod_points = _i(env, "MIN_POD_DATA_POINTS", c.min_pod_points)
         c.pairwise_joint_test = str(env.get("ML_PAIRWISE_JOINT_TEST", "") or "").strip() or c.pairwise_joint_test
         c.min_joint_points = _i(env, "MIN_JOINT_DATA_POINTS", c.min_joint_points)
+        c.pairwise_drift_test = str(env.get("ML_PAIRWISE_DRIFT_TEST", "") or "").strip() or c.pairwise_drift_test
+        c.min_drift_points = _i(env, "MIN_DRIFT_DATA_POINTS", c.min_drift_points)
+        c.drift_min_tau = _f(env, "ML_PAIRWISE_DRIFT_MIN_TAU", c.drift_min_tau)
         c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
         c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_scale_both

@@ -151,6 +151,8 @@ class Brain(BrainStateMixin):
         C.ScaleTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_SCALE_TEST or a ratio below 1 fails here
         C.PodTest.from_config(self.cfg)        # an unknown ML_PAIRWISE_POD_TEST or MIN_POD_DATA_POINTS < 1 fails here
         C.JointTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_JOINT_TEST or MIN_JOINT_DATA_POINTS < 1 fails here
+        C.DriftTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_DRIFT_TEST, MIN_DRIFT_DATA_POINTS < 3 or a tau
+        #                                        floor outside [0, 1] fails here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -283,6 +285,8 @@ class Brain(BrainStateMixin):
             diff = C.scale_diff(diff, cur, base, C.ScaleTest.from_config(self.cfg))
             # per-pod test (K29, off by default), last: it only ever sets a verdict
             diff = C.pods_diff(diff, cur, seg_end, base, C.PodTest.from_config(self.cfg))
+            # drift test (K31, off by default), over the same pods in time order: it only ever sets a verdict
+            diff = C.drift_diff(diff, cur, seg_end, base, C.DriftTest.from_config(self.cfg))
             # joint test over the metrics of a job (K30, off by default), last: it only ever sets a verdict
             joint = C.JointTest.from_config(self.cfg)
             if joint.enabled:

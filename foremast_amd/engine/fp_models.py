@@ -290,14 +290,16 @@ class ModelsMixin:
                 diff = C.gate_diff(diff, ga.cur_dev, ga.base_d, gate, bound, M)
             # scale test (K27, off by default): a row whose spread differs is "different" whatever the gate said
             diff = C.scale_diff(diff, ga.cur_dev, ga.base_d, C.ScaleTest.from_config(cfg))
-            pods = C.PodTest.from_config(cfg)
-            if pods.enabled:
+            pods, drift = C.PodTest.from_config(cfg), C.DriftTest.from_config(cfg)
+            if pods.enabled or drift.enabled:
                 # per-pod test (K29): the window table keeps one slot per pod; windows fetched per job were
                 # concatenated before they got here and count as one pod each (the test then does not apply)
                 ends = (self.wt.pod_ends(ga.wcur) if ga.wcur is not None
                         else np.asarray(ga.cur_len, np.int32).reshape(-1, 1))
                 seg = torch.from_numpy(np.minimum(ends, n).astype(np.int32)).to(dev)
                 diff = C.pods_diff(diff, ga.cur_dev, seg, ga.base_d, pods)
+                # drift test (K31) over the same segments; one pod is one segment in time order, still a trend
+                diff = C.drift_diff(diff, ga.cur_dev, seg, ga.base_d, drift)
             joint = C.JointTest.from_config(cfg)
             if joint.enabled and M >= 2:
                 # joint test (K30): the M rows of a job whose columns line up with its first row's -- the same

@@ -226,6 +226,10 @@ class CanaryScorer:
         self.joint = C.JointTest.from_config(cfg or BrainConfig())
         if self.joint.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the joint test (ML_PAIRWISE_JOINT_TEST) enabled")
+        # drift test (K31): needs the pod boundaries like the per-pod test; refused the same way (_no_pods)
+        self.drift = C.DriftTest.from_config(cfg or BrainConfig())
+        if self.drift.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the drift test (ML_PAIRWISE_DRIFT_TEST) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -336,8 +340,14 @@ class CanaryScorer:
             raise ValueError(f"{what} is not available with the per-pod test (ML_PAIRWISE_POD_TEST) enabled")
         if self.joint.enabled:
             raise ValueError(f"{what} is not available with the joint test (ML_PAIRWISE_JOINT_TEST) enabled")
+        if self.drift.enabled:
+            raise ValueError(f"{what} is not available with the drift test (ML_PAIRWISE_DRIFT_TEST) enabled")
 
     def _no_pods(self, base) -> None:
+        if self.drift.enabled and base is not None and base.shape[1] > 0:
+            raise ValueError("CanaryScorer does not run the drift test (ML_PAIRWISE_DRIFT_TEST): its rows carry no pod "
+                             "boundaries; score groups with a baseline op by op (ops.canary.drift_diff after "
+                             "pairwise_tests)")
         if self.joint.enabled and base is not None and base.shape[1] > 0:
             raise ValueError("CanaryScorer does not run the joint test (ML_PAIRWISE_JOINT_TEST) yet; score groups "
                              "with a baseline op by op (ops.canary.joint_diff after pairwise_tests)")

@@ -46,6 +46,10 @@ _SIGS: dict[str, list] = {
     # K30: cur ld_c n_cur base ld_b n_base R rows members G min_points p_thr joint n12 T A member_z joint_diff stream
     "fm_pairwise_joint": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p, c_i64, c_int,
                           c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # K31: cur ld_c n_cur seg_end G base ld_b n_base R min_points p_thr min_tau tier drift counts pod_S pod_n k
+    # drift_diff stream (seg_end and the [R, G] outputs may be null with G == 0)
+    "fm_pairwise_drift": [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_float,
+                          c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``pairwise_drift.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -861,6 +861,180 @@ def _joint_bucketed(cur, base, rows, K, test: JointTest) -> JointResult:
                         sub.numpy(), K.index_select(0, wd).cpu().numpy(), test)
         for dst, src in zip(o.tensors(), r.tensors()):
             dst[wd] = src.to(dev)
+    return o
+
+
+DRIFT_TESTS = {"": "", "OFF": "", "MANN_KENDALL": "MANN_KENDALL"}
+
+
+@dataclass(frozen=True)
+class DriftTest:
+    """Drift canary test (K31, docs/BRAIN_SPEC.md 4.5): the Mann-Kendall trend of
+    the canary's samples over time, stratified by pod, against the baseline's
+    own trend.  A row it flags counts as "different" whatever the other tests
+    say; it never clears a verdict.  ``test == ""`` = off."""
+
+    test: str = ""                  # ML_PAIRWISE_DRIFT_TEST: "" | OFF | MANN_KENDALL
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD
+    min_points: int = 10            # MIN_DRIFT_DATA_POINTS: finite samples a pod, and the baseline, need
+    min_tau: float = 0.0            # ML_PAIRWISE_DRIFT_MIN_TAU: floor on |tau| of the current side
+
+    def __post_init__(self):
+        name = str(self.test or "").strip().upper()
+        if name not in DRIFT_TESTS:
+            raise ValueError(f"unknown pairwise drift test {self.test!r} (MANN_KENDALL or OFF)")
+        object.__setattr__(self, "test", DRIFT_TESTS[name])
+        if int(self.min_points) < 3:
+            raise ValueError(f"min_points must be >= 3, got {self.min_points!r}")
+        if not 0.0 <= float(self.min_tau) <= 1.0:
+            raise ValueError(f"min_tau must lie in [0, 1], got {self.min_tau!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.test != ""
+
+    @classmethod
+    def from_config(cls, cfg) -> "DriftTest":
+        """The drift test of a ``BrainConfig`` (``pairwise_drift_test``, ``min_drift_points``, ``drift_min_tau`` and
+        the pairwise threshold)."""
+        return cls(cfg.pairwise_drift_test, float(cfg.pairwise_threshold), int(cfg.min_drift_points),
+                   float(cfg.drift_min_tau))
+
+
+@dataclass
+class DriftResult:
+    drift: torch.Tensor                  # [R, 6] fp32: z, p, z_c, tau_c, z_b, tau_b
+    counts: torch.Tensor                 # [R, 2, 4] int64: S, P, Tx2, V18 of the current side and the baseline
+    pod_S: torch.Tensor                  # [R, G] int32: S of every kept pod
+    pod_n: torch.Tensor                  # [R, G] int32: finite samples of every kept pod
+    k: torch.Tensor                      # [R] int32: kept pods
+    drift_diff: torch.Tensor             # [R] int8
+
+    def tensors(self) -> tuple:
+        return (self.drift, self.counts, self.pod_S, self.pod_n, self.k, self.drift_diff)
+
+
+def alloc_drift(R: int, G: int, device, fill: bool = False) -> DriftResult:
+    """Output buffers of K31, which writes all of them for every row; ``fill``:
+    holding what a row without samples gets (NaN, zeros)."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+    o = DriftResult(new((R, 6), torch.float32), new((R, 2, 4), torch.int64), new((R, G), torch.int32),
+                    new((R, G), torch.int32), new((R,), torch.int32), new((R,), torch.int8))
+    if fill:
+        for t in o.tensors():
+            t.fill_(float("nan") if t.dtype == torch.float32 else 0)
+    return o
+
+
+# rows ``pairwise_drift`` has sent down each route since the last reset:
+# "wave" / "wide" (K31's tiers), "host" (the numpy definition)
+_DRIFT_ROUTE_ROWS = {"wave": 0, "wide": 0, "host": 0}
+
+
+def drift_route_rows() -> dict[str, int]:
+    """Rows of GPU batches per drift-test route so far (a copy)."""
+    return dict(_DRIFT_ROUTE_ROWS)
+
+
+def reset_drift_route_rows() -> None:
+    for k in _DRIFT_ROUTE_ROWS:
+        _DRIFT_ROUTE_ROWS[k] = 0
+
+
+def _drift_host(cur, seg_end, base, test: DriftTest) -> DriftResult:
+    """The numpy definition on host arrays, as CPU tensors."""
+    o = ref.pairwise_drift(cur, seg_end, base, test.min_points)
+    return DriftResult(*(torch.from_numpy(a) for a in o),
+                       torch.from_numpy(ref.drift_verdict(o[0], test.p_threshold, test.min_tau)))
+
+
+def pairwise_drift(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+                   test: DriftTest = DriftTest("MANN_KENDALL"), tier: str = "auto",
+                   out: DriftResult | None = None) -> DriftResult:
+    """Drift test of current vs baseline per row and its verdict.
+
+    ``cur`` [R, n_cur] is pod-major, the samples of a pod in time order;
+    ``seg_end`` [R, G] int32 holds the column at which pod g's segment ends
+    (cumulative; an empty pod repeats the previous end); ``base`` is one
+    segment in column order.  CPU tensors run the numpy definition, GPU
+    tensors K31: its wave tier up to PAIRWISE_MAX pooled columns, its
+    workgroup tier up to PAIRWISE_WIDE_MAX (``tier="wide"`` runs it for any
+    batch that fits); a batch padded wider than that, or with more than
+    POD_MAX pod columns, is bucketed by the rows' own used widths, and only
+    rows really wider, or with more than POD_MAX non-empty pods, run the
+    definition on the host."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
+    check(seg_end.dim() == 2 and seg_end.shape[0] == R and seg_end.dtype == torch.int32 and seg_end.is_contiguous()
+          and seg_end.device == cur.device, "seg_end must be a contiguous int32 [R, G] tensor on the samples' device")
+    if not cur.is_cuda:
+        return _drift_host(cur.numpy(), seg_end.numpy(), base.numpy(), test)
+    require_native(cur)
+    n_cur, n_base, G = cur.shape[1], base.shape[1], seg_end.shape[1]
+    if n_cur + n_base > PAIRWISE_WIDE_MAX or G > POD_MAX:
+        return _drift_bucketed(cur, seg_end, base, test)
+    wide = tier == "wide" or n_cur + n_base > PAIRWISE_MAX
+    _DRIFT_ROUTE_ROWS["wide" if wide else "wave"] += R
+    o = out if out is not None else alloc_drift(R, G, cur.device)
+    LIB.call("fm_pairwise_drift", ptr(cur), ldc, n_cur, ptr(seg_end) if G else None, G, ptr(base), ldb, n_base, R,
+             int(test.min_points), float(test.p_threshold), float(test.min_tau), 2 if wide else 0, ptr(o.drift),
+             ptr(o.counts), ptr(o.pod_S), ptr(o.pod_n), ptr(o.k), ptr(o.drift_diff), stream_of(cur))
+    return o
+
+
+def drift_diff(diff: torch.Tensor, cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+               test: DriftTest) -> torch.Tensor:
+    """``diff | drift_diff`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``, after the gate and the other optional tests: the drift
+    test only ever sets a verdict)."""
+    if not test.enabled:
+        return diff
+    return diff | pairwise_drift(cur, seg_end, base, test).drift_diff.to(diff.dtype)
+
+
+def _drift_bucketed(cur, seg_end, base, test: DriftTest) -> DriftResult:
+    """A batch padded wider than K31 takes, or with more than POD_MAX pod
+    columns: rows bucketed by their own used widths exactly as
+    ``_pods_bucketed`` does (the wave tier, then the workgroup tier, each on a
+    narrowed copy whose segment ends are cut at the copy's width: the columns
+    cut off hold no finite sample, and dropping trailing missing samples
+    changes no pair).  A row whose pods past POD_MAX are all empty loses only
+    those columns; rows with more pods, and rows really wider than
+    PAIRWISE_WIDE_MAX, run the numpy definition on the host."""
+    R, G = seg_end.shape
+    dev = cur.device
+    Gk = min(G, POD_MAX)
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    many = (seg_end[:, POD_MAX - 1] != seg_end[:, -1]).cpu() if G > POD_MAX else torch.zeros((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, ~many, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~many & ~fit, PAIRWISE_WIDE_MAX)
+    o = alloc_drift(R, G, dev, fill=True)
+
+    def put(k, r):
+        for dst, src in zip(o.tensors(), r.tensors()):
+            if dst.dim() == 2 and dst.shape[1] == G and src.shape[1] != G:
+                dst[k, :src.shape[1]] = src.to(dev)
+            else:
+                dst[k] = src.to(dev)
+
+    for rows in (fit, wide):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            put(kd, pairwise_drift(cur.index_select(0, kd)[:, :a].contiguous(),
+                                   seg_end.index_select(0, kd)[:, :Gk].clamp(max=a).contiguous(),
+                                   base.index_select(0, kd)[:, :b].contiguous(), test))
+    w = torch.nonzero(~(fit | wide)).flatten()
+    if len(w):
+        _DRIFT_ROUTE_ROWS["host"] += len(w)
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        put(wd, _drift_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
+                            seg_end.index_select(0, wd).clamp(max=a).cpu().numpy(),
+                            base.index_select(0, wd)[:, :b].cpu().numpy(), test))
     return o
 
 

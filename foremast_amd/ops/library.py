@@ -117,6 +117,28 @@ def _(cur, base, rows, K, p_threshold, min_points):
     return (cur.new_empty((G, 6)), cur.new_empty((G, C.JOINT_MAX_K)), cur.new_empty((G,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K31
+@custom_op(f"{NS}::pairwise_drift", mutates_args=())
+def pairwise_drift(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor, p_threshold: float,
+                   min_points: int, min_tau: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(drift [R, 6] = z, p, z_c, tau_c, z_b, tau_b; counts [R, 2, 4] int64 = S,
+    P, Tx2, V18 per side; drift_diff [R] int8) of the stratified Mann-Kendall
+    drift test; pod g of a row owns the columns [seg_end[g - 1], seg_end[g])
+    of ``cur`` (K31)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(seg_end.dim() == 2 and seg_end.shape[0] == cur.shape[0] and seg_end.dtype == torch.int32,
+          "seg_end must be int32 [R, G]")
+    r = C.pairwise_drift(cur.contiguous(), seg_end.contiguous(), base.contiguous(),
+                         C.DriftTest("MANN_KENDALL", p_threshold, min_points, min_tau))
+    return r.drift.clone(), r.counts.clone(), r.drift_diff.clone()
+
+
+@register_fake(f"{NS}::pairwise_drift")
+def _(cur, seg_end, base, p_threshold, min_points, min_tau):
+    R = cur.shape[0]
+    return (cur.new_empty((R, 6)), cur.new_empty((R, 2, 4), dtype=torch.int64), cur.new_empty((R,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -243,5 +265,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

@@ -720,3 +720,93 @@ def joint_verdict(joint, p_thr):
     p = np.asarray(joint, dtype=np.float32).reshape(-1, 6)[:, 1]
     with np.errstate(invalid="ignore"):
         return (~np.isnan(p) & (p < np.float32(p_thr))).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# drift test of current vs baseline (K31): the Mann-Kendall trend of the
+# canary's samples over time, stratified by pod, against the baseline's own,
+# straight from the definition in docs/BRAIN_SPEC.md section 4.5
+
+
+def mann_kendall_counts(x):
+    """(S, P, Tx2, V18) of one segment's finite samples ``x`` in time order, as
+    exact integers: with g_j / l_j / c_j the earlier samples below / above /
+    equal to x_j, S = sum g_j - l_j, P = n (n - 1) / 2, Tx2 = sum 2 c_j and
+    V18 = n (n - 1) (2 n + 5) - sum (6 c_j^2 + 12 c_j), 18 times the
+    tie-corrected Mann-Kendall variance."""
+    x = np.asarray(x, dtype=np.float64)                             # (-0.0 == 0.0: a tie)
+    n = len(x)
+    S = c1 = c2 = 0
+    for a in range(0, n, 512):                                      # (blocks of j, to bound the pair matrix)
+        blk = x[a:a + 512, None]
+        earlier = np.arange(n)[None, :] < np.arange(a, a + len(blk))[:, None]
+        S += int(((x[None, :] < blk) & earlier).sum()) - int(((x[None, :] > blk) & earlier).sum())
+        c = ((x[None, :] == blk) & earlier).sum(1).astype(np.int64)
+        c1, c2 = c1 + int(c.sum()), c2 + int((c * c).sum())
+    return S, n * (n - 1) // 2, 2 * c1, n * (n - 1) * (2 * n + 5) - (6 * c2 + 12 * c1)
+
+
+def pairwise_drift(cur, seg_end, base, min_points: int = 10):
+    """(drift [R, 6] fp32 = (z, p, z_c, tau_c, z_b, tau_b), counts [R, 2, 4]
+    int64 = (S, P, Tx2, V18) of the current side and the baseline, pod_S [R, G]
+    int32, pod_n [R, G] int32, k [R] int32) per row.
+
+    ``cur`` is pod-major and pod g owns the columns [seg_end[g - 1],
+    seg_end[g]); ``base`` is one segment.  NaN / +-inf are missing, the rest
+    keep their column order as time.  A pod with fewer than max(min_points, 1)
+    finite samples is dropped (n = 0, S = 0).  The current side's integers are
+    those of ``mann_kendall_counts`` summed over the k kept pods (pods are never
+    compared with each other), the baseline's those of its one segment.  Then
+    in fp64, each line left to right, rounded to fp32 once, per side: z_side =
+    (S - sgn S) / sqrt(V18 / 18), tau_side = S / sqrt(P (P - Tx2 / 2)), both 0
+    for a side with V18 == 0; z = (z_c - z_b) / sqrt(1 + v_b) with v_b = 1 if
+    the baseline's V18 > 0 else 0; p = erfc(|z| / sqrt 2).  Not applicable (all
+    six NaN) when k == 0, the baseline has fewer than max(min_points, 1) finite
+    samples or the current side's V18 == 0; the integers and k are reported
+    regardless."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    seg = np.asarray(seg_end, dtype=np.int64)
+    R, G = seg.shape
+    drift = np.full((R, 6), np.nan, dtype=np.float32)
+    counts = np.zeros((R, 2, 4), dtype=np.int64)
+    pod_S = np.zeros((R, G), dtype=np.int32)
+    pod_n = np.zeros((R, G), dtype=np.int32)
+    k = np.zeros(R, dtype=np.int32)
+    need = max(int(min_points), 1)
+
+    def side(S, P, T2, V):
+        if V == 0:
+            return 0.0, 0.0
+        return ((S - np.sign(S)) / np.sqrt(float(V) / 18.0),
+                float(S) / np.sqrt(float(P) * (float(P) - float(T2) / 2.0)))
+
+    for r in range(R):
+        lo = 0
+        for g in range(G):
+            x = cur[r, lo:max(lo, seg[r, g])]
+            lo = max(lo, int(seg[r, g]))
+            x = x[np.isfinite(x)]
+            if len(x) >= need:
+                c = mann_kendall_counts(x)
+                counts[r, 0] += c
+                pod_S[r, g], pod_n[r, g] = c[0], len(x)
+                k[r] += 1
+        b = base[r][np.isfinite(base[r])]
+        counts[r, 1] = mann_kendall_counts(b)
+        if k[r] == 0 or len(b) < need or counts[r, 0, 3] == 0:
+            continue
+        (zc, tc), (zb, tb) = side(*(int(v) for v in counts[r, 0])), side(*(int(v) for v in counts[r, 1]))
+        z = (zc - zb) / np.sqrt(1.0 + (1.0 if counts[r, 1, 3] > 0 else 0.0))
+        drift[r] = (z, special.erfc(abs(z) / np.sqrt(2.0)), zc, tc, zb, tb)
+    return drift, counts, pod_S, pod_n, k
+
+
+def drift_verdict(drift, p_thr, min_tau: float = 0.0):
+    """drift_diff [R] int8 of the drift test: 1 where the test applies (p is a
+    number), p is below fp32(p_thr) and |tau_c| is at least fp32(min_tau),
+    compared in fp32 as ``pods_verdict`` compares."""
+    d = np.asarray(drift, dtype=np.float32).reshape(-1, 6)
+    with np.errstate(invalid="ignore"):
+        return (~np.isnan(d[:, 1]) & (d[:, 1] < np.float32(p_thr)) &
+                (np.abs(d[:, 3]) >= np.float32(min_tau))).astype(np.int8)
