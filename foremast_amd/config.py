@@ -90,6 +90,14 @@ class BrainConfig:
     pairwise_drift_test: str = ""            # ML_PAIRWISE_DRIFT_TEST: "" | OFF | MANN_KENDALL
     min_drift_points: int = 10               # MIN_DRIFT_DATA_POINTS (finite samples a pod, and the baseline, need; >= 3)
     drift_min_tau: float = 0.0               # ML_PAIRWISE_DRIFT_MIN_TAU (floor on |tau| of the current side; in [0, 1])
+    # tail test of the pairwise verdict (docs/BRAIN_SPEC.md 4.6, K32; off by default): the share of samples beyond the
+    # pooled q-quantiles, an exact conditional test per level; a row it flags is "different"
+    pairwise_tail_test: str = ""             # ML_PAIRWISE_TAIL_TEST: "" | OFF | EXCEEDANCE
+    pairwise_tail_quantiles: str = "0.9,0.95,0.99"  # ML_PAIRWISE_TAIL_QUANTILES (1 to 4 levels, increasing, in [0.5, 0.9999])
+    pairwise_tail_sides: str = "BOUND"       # ML_PAIRWISE_TAIL_SIDES: BOUND | UPPER | LOWER | BOTH
+    min_tail_data_points: int = 20           # MIN_TAIL_DATA_POINTS (finite samples each side needs; >= 2)
+    min_tail_points: int = 5                 # MIN_TAIL_POINTS (pooled samples beyond a level's threshold; >= 1)
+    tail_min_excess: float = 0.0             # ML_PAIRWISE_TAIL_MIN_EXCESS (floor on the exceedance-share difference; in [0, 1))
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -256,6 +264,13 @@ class BrainConfig:
         c.pairwise_drift_test = str(env.get("ML_PAIRWISE_DRIFT_TEST", "") or "").strip() or c.pairwise_drift_test
         c.min_drift_points = _i(env, "MIN_DRIFT_DATA_POINTS", c.min_drift_points)
         c.drift_min_tau = _f(env, "ML_PAIRWISE_DRIFT_MIN_TAU", c.drift_min_tau)
+        c.pairwise_tail_test = str(env.get("ML_PAIRWISE_TAIL_TEST", "") or "").strip() or c.pairwise_tail_test
+        c.pairwise_tail_quantiles = (str(env.get("ML_PAIRWISE_TAIL_QUANTILES", "") or "").strip()
+                                     or c.pairwise_tail_quantiles)
+        c.pairwise_tail_sides = str(env.get("ML_PAIRWISE_TAIL_SIDES", "") or "").strip() or c.pairwise_tail_sides
+        c.min_tail_data_points = _i(env, "MIN_TAIL_DATA_POINTS", c.min_tail_data_points)
+        c.min_tail_points = _i(env, "MIN_TAIL_POINTS", c.min_tail_points)
+        c.tail_min_excess = _f(env, "ML_PAIRWISE_TAIL_MIN_EXCESS", c.tail_min_excess)
         c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
         c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_scale_both

@@ -153,6 +153,8 @@ class Brain(BrainStateMixin):
         C.JointTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_JOINT_TEST or MIN_JOINT_DATA_POINTS < 1 fails here
         C.DriftTest.from_config(self.cfg)      # an unknown ML_PAIRWISE_DRIFT_TEST, MIN_DRIFT_DATA_POINTS < 3 or a tau
         #                                        floor outside [0, 1] fails here
+        C.TailTest.from_config(self.cfg)       # an unknown ML_PAIRWISE_TAIL_TEST / _SIDES, bad levels or point gates
+        #                                        or an excess floor outside [0, 1) fail here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -287,6 +289,8 @@ class Brain(BrainStateMixin):
             diff = C.pods_diff(diff, cur, seg_end, base, C.PodTest.from_config(self.cfg))
             # drift test (K31, off by default), over the same pods in time order: it only ever sets a verdict
             diff = C.drift_diff(diff, cur, seg_end, base, C.DriftTest.from_config(self.cfg))
+            # tail test (K32, off by default), with every row's own bound code as the gate: it only ever sets a verdict
+            diff = C.tail_diff(diff, cur, base, C.TailTest.from_config(self.cfg), tables.bound, R)
             # joint test over the metrics of a job (K30, off by default), last: it only ever sets a verdict
             joint = C.JointTest.from_config(self.cfg)
             if joint.enabled:

@@ -300,6 +300,11 @@ class ModelsMixin:
                 diff = C.pods_diff(diff, ga.cur_dev, seg, ga.base_d, pods)
                 # drift test (K31) over the same segments; one pod is one segment in time order, still a trend
                 diff = C.drift_diff(diff, ga.cur_dev, seg, ga.base_d, drift)
+            tail = C.TailTest.from_config(cfg)
+            if tail.enabled:
+                # tail test (K32): the sides follow the metrics' bound codes, as the gate's direction does
+                bound = torch.tensor([cfg.rule_for(a).bound for a in p0.aliases], dtype=torch.int32, device=dev)
+                diff = C.tail_diff(diff, ga.cur_dev, ga.base_d, tail, bound, M)
             joint = C.JointTest.from_config(cfg)
             if joint.enabled and M >= 2:
                 # joint test (K30): the M rows of a job whose columns line up with its first row's -- the same

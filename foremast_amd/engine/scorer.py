@@ -230,6 +230,10 @@ class CanaryScorer:
         self.drift = C.DriftTest.from_config(cfg or BrainConfig())
         if self.drift.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the drift test (ML_PAIRWISE_DRIFT_TEST) enabled")
+        # tail test (K32): not part of the captured ticks; refused the same way (_no_pods)
+        self.tail = C.TailTest.from_config(cfg or BrainConfig())
+        if self.tail.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the tail test (ML_PAIRWISE_TAIL_TEST) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -342,8 +346,13 @@ class CanaryScorer:
             raise ValueError(f"{what} is not available with the joint test (ML_PAIRWISE_JOINT_TEST) enabled")
         if self.drift.enabled:
             raise ValueError(f"{what} is not available with the drift test (ML_PAIRWISE_DRIFT_TEST) enabled")
+        if self.tail.enabled:
+            raise ValueError(f"{what} is not available with the tail test (ML_PAIRWISE_TAIL_TEST) enabled")
 
     def _no_pods(self, base) -> None:
+        if self.tail.enabled and base is not None and base.shape[1] > 0:
+            raise ValueError("CanaryScorer does not run the tail test (ML_PAIRWISE_TAIL_TEST); score groups with a "
+                             "baseline op by op (ops.canary.tail_diff after pairwise_tests)")
         if self.drift.enabled and base is not None and base.shape[1] > 0:
             raise ValueError("CanaryScorer does not run the drift test (ML_PAIRWISE_DRIFT_TEST): its rows carry no pod "
                              "boundaries; score groups with a baseline op by op (ops.canary.drift_diff after "

@@ -50,6 +50,11 @@ _SIGS: dict[str, list] = {
     # drift_diff stream (seg_end and the [R, G] outputs may be null with G == 0)
     "fm_pairwise_drift": [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_float,
                           c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # K32: cur ld_c n_cur base ld_b n_base R L q0 q1 q2 q3 sides bound M min_points min_tail p_thr min_excess lf tier
+    # tail which J n counts tail_diff stream (bound may be null unless sides == 0)
+    "fm_pairwise_tail": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_int,
+                         c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p,
+                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

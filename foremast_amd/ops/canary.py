@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``pairwise_drift.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``pairwise_drift.hip``, ``pairwise_tail.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -1035,6 +1035,209 @@ def _drift_bucketed(cur, seg_end, base, test: DriftTest) -> DriftResult:
         put(wd, _drift_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
                             seg_end.index_select(0, wd).clamp(max=a).cpu().numpy(),
                             base.index_select(0, wd)[:, :b].cpu().numpy(), test))
+    return o
+
+
+TAIL_TESTS = {"": "", "OFF": "", "EXCEEDANCE": "EXCEEDANCE"}
+TAIL_MAX_LEVELS = 4
+
+
+@dataclass(frozen=True)
+class TailTest:
+    """Tail canary test (K32, docs/BRAIN_SPEC.md 4.6): the share of each side's
+    samples beyond the pooled q-quantiles, an exact conditional test per level,
+    Bonferroni over the levels that count.  A row it flags counts as
+    "different" whatever the other tests say; it never clears a verdict.
+    ``test == ""`` = off."""
+
+    test: str = ""                  # ML_PAIRWISE_TAIL_TEST: "" | OFF | EXCEEDANCE
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD
+    quantiles: tuple = (0.9, 0.95, 0.99)   # ML_PAIRWISE_TAIL_QUANTILES (a comma list as a string is parsed)
+    sides: str = "BOUND"            # ML_PAIRWISE_TAIL_SIDES: BOUND | UPPER | LOWER | BOTH
+    min_points: int = 20            # MIN_TAIL_DATA_POINTS: finite samples each side needs
+    min_tail_points: int = 5        # MIN_TAIL_POINTS: pooled samples beyond a level's threshold
+    min_excess: float = 0.0         # ML_PAIRWISE_TAIL_MIN_EXCESS: floor on the exceedance-share difference
+
+    def __post_init__(self):
+        name = str(self.test or "").strip().upper()
+        if name not in TAIL_TESTS:
+            raise ValueError(f"unknown pairwise tail test {self.test!r} (EXCEEDANCE or OFF)")
+        object.__setattr__(self, "test", TAIL_TESTS[name])
+        qs = self.quantiles
+        try:
+            qs = tuple(float(v) for v in (qs.split(",") if isinstance(qs, str) else qs))
+        except (TypeError, ValueError):
+            raise ValueError(f"tail quantiles must be numbers, got {self.quantiles!r}") from None
+        q_i = tuple(int(round(q * 10000)) for q in qs if q == q)
+        if not (1 <= len(qs) <= TAIL_MAX_LEVELS and len(q_i) == len(qs) and all(5000 <= q <= 9999 for q in q_i)
+                and all(a < b for a, b in zip(q_i, q_i[1:]))):
+            raise ValueError(f"tail quantiles must be 1 to {TAIL_MAX_LEVELS} strictly increasing levels in "
+                             f"[0.5, 0.9999], got {self.quantiles!r}")
+        object.__setattr__(self, "quantiles", qs)
+        side = str(self.sides or "").strip().upper()
+        if side not in ref.TAIL_SIDES:
+            raise ValueError(f"unknown tail sides {self.sides!r} (BOUND, UPPER, LOWER or BOTH)")
+        object.__setattr__(self, "sides", side)
+        if int(self.min_points) < 2:
+            raise ValueError(f"min_points must be >= 2, got {self.min_points!r}")
+        if int(self.min_tail_points) < 1:
+            raise ValueError(f"min_tail_points must be >= 1, got {self.min_tail_points!r}")
+        if not 0.0 <= float(self.min_excess) < 1.0:
+            raise ValueError(f"min_excess must lie in [0, 1), got {self.min_excess!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.test != ""
+
+    @property
+    def q_i(self) -> tuple:
+        """The levels in parts per 10,000, rounded once; every rank is integer arithmetic on these."""
+        return tuple(int(round(q * 10000)) for q in self.quantiles)
+
+    @classmethod
+    def from_config(cls, cfg) -> "TailTest":
+        """The tail test of a ``BrainConfig`` (``pairwise_tail_test``, ``pairwise_tail_quantiles``,
+        ``pairwise_tail_sides``, ``min_tail_data_points``, ``min_tail_points``, ``tail_min_excess`` and the pairwise
+        threshold)."""
+        return cls(cfg.pairwise_tail_test, float(cfg.pairwise_threshold), cfg.pairwise_tail_quantiles,
+                   cfg.pairwise_tail_sides, int(cfg.min_tail_data_points), int(cfg.min_tail_points),
+                   float(cfg.tail_min_excess))
+
+
+@dataclass
+class TailResult:
+    tail: torch.Tensor                   # [R, 4] fp32: p, p_min, excess, t of the deciding level
+    which: torch.Tensor                  # [R] int32: side * L + level of the deciding level, or -1
+    J: torch.Tensor                      # [R] int32: counting levels
+    n: torch.Tensor                      # [R, 2] int32: finite samples per side
+    counts: torch.Tensor                 # [R, 2, L, 3] int32: (a, b, k) per side and level
+    tail_diff: torch.Tensor              # [R] int8
+
+    def tensors(self) -> tuple:
+        return (self.tail, self.which, self.J, self.n, self.counts, self.tail_diff)
+
+
+def alloc_tail(R: int, L: int, device) -> TailResult:
+    """Output buffers of K32, which writes all of them for every row."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+    return TailResult(new((R, 4), torch.float32), new((R,), torch.int32), new((R,), torch.int32),
+                      new((R, 2), torch.int32), new((R, 2, L, 3), torch.int32), new((R,), torch.int8))
+
+
+# rows ``pairwise_tail`` has sent down each route since the last reset:
+# "wave" / "wide" (K32's tiers), "host" (the numpy definition)
+_TAIL_ROUTE_ROWS = {"wave": 0, "wide": 0, "host": 0}
+_TAIL_TABLES: dict = {}
+
+
+def tail_route_rows() -> dict[str, int]:
+    """Rows of GPU batches per tail-test route so far (a copy)."""
+    return dict(_TAIL_ROUTE_ROWS)
+
+
+def reset_tail_route_rows() -> None:
+    for k in _TAIL_ROUTE_ROWS:
+        _TAIL_ROUTE_ROWS[k] = 0
+
+
+def _tail_table(device) -> torch.Tensor:
+    """lf[n] = lgamma(n + 1), n = 0 .. 8,192, fp64 on ``device``: the reference's own table, built once per device."""
+    t = _TAIL_TABLES.get(device)
+    if t is None:
+        t = _TAIL_TABLES[device] = torch.from_numpy(ref.tail_log_factorials().copy()).to(device)
+    return t
+
+
+def _tail_host(cur, base, test: TailTest, bound_per_row) -> TailResult:
+    """The numpy definition on host arrays, as CPU tensors."""
+    o = ref.pairwise_tail(cur, base, test.q_i, test.sides, bound_per_row, test.min_points, test.min_tail_points)
+    return TailResult(*(torch.from_numpy(a) for a in o),
+                      torch.from_numpy(ref.tail_verdict(o[0], test.p_threshold, test.min_excess)))
+
+
+def pairwise_tail(cur: torch.Tensor, base: torch.Tensor, test: TailTest = TailTest("EXCEEDANCE"),
+                  bound: torch.Tensor | None = None, M: int = 1, out: TailResult | None = None,
+                  tier: str = "auto") -> TailResult:
+    """Tail test of current vs baseline per row and its verdict.
+
+    ``bound`` (int32 [M], the bound code of metric r % M) is needed when
+    ``test.sides`` is BOUND: code 1 runs the upper side alone, 2 the lower side
+    alone, anything else both.  CPU tensors run the numpy definition, GPU
+    tensors K32: its wave tier up to PAIRWISE_MAX pooled columns, its workgroup
+    tier up to PAIRWISE_WIDE_MAX (``tier="wide"`` runs it for any batch that
+    fits); a batch padded wider than that is bucketed by the rows' own used
+    widths, and only rows really wider run the definition on the host."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(M >= 1, "M must be >= 1")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
+    by_bound = test.sides == "BOUND"
+    check(not by_bound or (bound is not None and bound.numel() == M and bound.dtype == torch.int32
+                           and bound.device == cur.device),
+          "sides BOUND needs the per-metric bound codes, int32 [M] on the samples' device")
+    if not cur.is_cuda:
+        return _tail_host(cur.numpy(), base.numpy(), test, bound.numpy()[np.arange(R) % M] if by_bound else None)
+    require_native(cur)
+    n_cur, n_base = cur.shape[1], base.shape[1]
+    if n_cur + n_base > PAIRWISE_WIDE_MAX:
+        return _tail_bucketed(cur, base, test, bound, M)
+    wide = tier == "wide" or n_cur + n_base > PAIRWISE_MAX
+    _TAIL_ROUTE_ROWS["wide" if wide else "wave"] += R
+    q = test.q_i
+    o = out if out is not None else alloc_tail(R, len(q), cur.device)
+    check(o.counts.shape == (R, 2, len(q), 3), "out was allocated for another batch or number of levels")
+    q4 = q + (9999,) * (TAIL_MAX_LEVELS - len(q))
+    LIB.call("fm_pairwise_tail", ptr(cur), ldc, n_cur, ptr(base), ldb, n_base, R, len(q), *q4,
+             ref.TAIL_SIDES[test.sides], ptr(bound.contiguous()) if by_bound else None, M, int(test.min_points),
+             int(test.min_tail_points), float(test.p_threshold), float(test.min_excess), ptr(_tail_table(cur.device)),
+             2 if wide else 0, ptr(o.tail), ptr(o.which), ptr(o.J), ptr(o.n), ptr(o.counts), ptr(o.tail_diff),
+             stream_of(cur))
+    return o
+
+
+def tail_diff(diff: torch.Tensor, cur: torch.Tensor, base: torch.Tensor, test: TailTest, bound: torch.Tensor,
+              M: int) -> torch.Tensor:
+    """``diff | tail_diff`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``, after the gate and the other optional tests: the tail
+    test only ever sets a verdict; row r is judged by bound code ``bound[r % M]``)."""
+    if not test.enabled:
+        return diff
+    return diff | pairwise_tail(cur, base, test, bound, M).tail_diff.to(diff.dtype)
+
+
+def _tail_bucketed(cur, base, test: TailTest, bound, M: int) -> TailResult:
+    """A batch padded wider than K32 takes: rows bucketed by their own used
+    widths exactly as ``_drift_bucketed`` does (the wave tier, then the
+    workgroup tier, each on a narrowed copy: the columns cut off hold no finite
+    sample); rows really wider than PAIRWISE_WIDE_MAX run the numpy definition
+    on the host.  Every row brings its own bound code (the ORIGINAL row index r
+    % M), so the narrowed batches run with M = their row count."""
+    R = cur.shape[0]
+    dev = cur.device
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    fit = _bucket(lc, lb, torch.ones((R,), dtype=torch.bool), PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~fit, PAIRWISE_WIDE_MAX)
+    o = alloc_tail(R, len(test.q_i), dev)
+    per_row = bound[torch.arange(R, device=bound.device) % M] if test.sides == "BOUND" else None
+    for rows in (fit, wide):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            r = pairwise_tail(cur.index_select(0, kd)[:, :a].contiguous(), base.index_select(0, kd)[:, :b].contiguous(),
+                              test, None if per_row is None else per_row.index_select(0, kd).contiguous(), len(k))
+            for dst, src in zip(o.tensors(), r.tensors()):
+                dst[kd] = src
+    w = torch.nonzero(~(fit | wide)).flatten()
+    if len(w):
+        _TAIL_ROUTE_ROWS["host"] += len(w)
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        r = _tail_host(cur.index_select(0, wd)[:, :a].cpu().numpy(), base.index_select(0, wd)[:, :b].cpu().numpy(), test,
+                       None if per_row is None else per_row.index_select(0, wd).cpu().numpy())
+        for dst, src in zip(o.tensors(), r.tensors()):
+            dst[wd] = src.to(dev)
     return o
 
 

@@ -139,6 +139,30 @@ def _(cur, seg_end, base, p_threshold, min_points, min_tau):
     return (cur.new_empty((R, 6)), cur.new_empty((R, 2, 4), dtype=torch.int64), cur.new_empty((R,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K32
+@custom_op(f"{NS}::pairwise_tail", mutates_args=())
+def pairwise_tail(cur: torch.Tensor, base: torch.Tensor, bound: torch.Tensor, quantiles: str, sides: str,
+                  p_threshold: float, min_points: int, min_tail_points: int,
+                  min_excess: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(tail [R, 4] = p, p_min, excess, t of the deciding level; which [R] int32;
+    counts [R, 2, L, 3] int32 = a, b, k per side and level; tail_diff [R] int8)
+    of the quantile exceedance test at the levels of the comma list
+    ``quantiles``; under ``sides`` = BOUND row r is judged by bound code
+    ``bound[r % len(bound)]`` (K32)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(bound.dim() == 1 and bound.numel() >= 1 and bound.dtype == torch.int32, "bound must be int32 [M]")
+    test = C.TailTest("EXCEEDANCE", p_threshold, quantiles, sides, min_points, min_tail_points, min_excess)
+    r = C.pairwise_tail(cur.contiguous(), base.contiguous(), test, bound.contiguous(), bound.numel())
+    return r.tail.clone(), r.which.clone(), r.counts.clone(), r.tail_diff.clone()
+
+
+@register_fake(f"{NS}::pairwise_tail")
+def _(cur, base, bound, quantiles, sides, p_threshold, min_points, min_tail_points, min_excess):
+    R, L = cur.shape[0], len(quantiles.split(","))
+    return (cur.new_empty((R, 4)), cur.new_empty((R,), dtype=torch.int32),
+            cur.new_empty((R, 2, L, 3), dtype=torch.int32), cur.new_empty((R,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -265,5 +289,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

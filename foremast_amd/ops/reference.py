@@ -810,3 +810,118 @@ def drift_verdict(drift, p_thr, min_tau: float = 0.0):
     with np.errstate(invalid="ignore"):
         return (~np.isnan(d[:, 1]) & (d[:, 1] < np.float32(p_thr)) &
                 (np.abs(d[:, 3]) >= np.float32(min_tau))).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# tail test of current vs baseline (K32): the share of samples beyond the
+# pooled q-quantiles, an exact conditional (Fisher / Mood) test per level,
+# straight from the definition in docs/BRAIN_SPEC.md section 4.6
+
+TAIL_SIDES = {"BOUND": 0, "UPPER": 1, "LOWER": 2, "BOTH": 3}
+TAIL_TABLE_MAX = 8192
+_TAIL_LF = np.zeros(0, dtype=np.float64)
+
+
+def tail_log_factorials(n: int = TAIL_TABLE_MAX):
+    """lf[i] = lgamma(i + 1) for i = 0 .. max(n, 8,192) in fp64 (``math.lgamma``):
+    the table the kernel is handed, so device and definition read the same
+    numbers."""
+    global _TAIL_LF
+    n = max(int(n), TAIL_TABLE_MAX)
+    if len(_TAIL_LF) < n + 1:
+        import math
+        _TAIL_LF = np.array([math.lgamma(i + 1.0) for i in range(n + 1)], dtype=np.float64)
+    return _TAIL_LF[:n + 1]
+
+
+def hypergeom_upper_tail(a: int, m: int, n_c: int, n_b: int) -> float:
+    """P(X >= a) for X the current side's share of the m pooled samples beyond
+    a threshold, n_c of the N = n_c + n_b samples being the current side's:
+    the sum over x = max(a, m - n_b) .. min(m, n_c) of C(m, x) C(N - m, n_c -
+    x) / C(N, n_c), each term exp of nine table entries added left to right;
+    exactly 1 when a <= max(0, m - n_b), capped at 1."""
+    N = n_c + n_b
+    if a <= max(0, m - n_b):
+        return 1.0
+    lf = tail_log_factorials(N)
+    x = np.arange(max(a, m - n_b), min(m, n_c) + 1)
+    s = lf[m] - lf[x] - lf[m - x] + lf[N - m] - lf[n_c - x] - lf[N - m - n_c + x] - lf[N] + lf[n_c] + lf[n_b]
+    return min(1.0, float(np.exp(s).sum()))
+
+
+def pairwise_tail(cur, base, q_i=(9000, 9500, 9900), sides="BOUND", bound_per_row=None, min_points: int = 20,
+                  min_tail_points: int = 5):
+    """(tail [R, 4] fp32 = (p, p_min, excess, t of the deciding level), which
+    [R] int32 = side * L + level of the deciding level or -1, J [R] int32, n
+    [R, 2] int32 = finite samples per side, counts [R, 2, L, 3] int32 = (a, b,
+    k) per side and level) per row.
+
+    ``q_i`` are the L levels in parts per 10,000.  NaN / +-inf are missing;
+    samples compare as fp32 (-0.0 == 0.0).  The row applies when both sides
+    have max(min_points, 1) finite samples.  ``sides`` names the sides that
+    run; under BOUND the row's code in ``bound_per_row`` decides (1 upper, 2
+    lower, anything else both).  Upper side, level l: k = min(N - 1, ceil(q_i
+    N / 10,000)), t the k-th smallest pooled value, a / b the current /
+    baseline samples above t, m = a + b.  The lower side is the upper side of
+    the negated samples: t the k-th largest pooled value (reported in the
+    samples' own sign), a / b the samples below it.  A level counts when m >=
+    min_tail_points and m differs from the previous counting level's m on its
+    side; its p-value is ``hypergeom_upper_tail``.  J = counting levels over
+    the sides that run; the deciding level has the smallest p (ties: the upper
+    side, then the lower level); p = min(1, J p_min), excess = a / n_c - b /
+    n_b in fp64, each rounded to fp32 once.  Rows that do not apply report
+    zero counts; tail is NaN and which -1 there and where J == 0."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    R, L = cur.shape[0], len(q_i)
+    tail = np.full((R, 4), np.nan, dtype=np.float32)
+    which = np.full(R, -1, dtype=np.int32)
+    J = np.zeros(R, dtype=np.int32)
+    n = np.zeros((R, 2), dtype=np.int32)
+    counts = np.zeros((R, 2, L, 3), dtype=np.int32)
+    need = max(int(min_points), 1)
+    fixed = TAIL_SIDES[str(sides).upper()]
+    for r in range(R):
+        c, b = cur[r][np.isfinite(cur[r])], base[r][np.isfinite(base[r])]
+        n_c, n_b = len(c), len(b)
+        n[r] = (n_c, n_b)
+        if n_c < need or n_b < need:
+            continue
+        code = fixed if fixed else int(bound_per_row[r])
+        N = n_c + n_b
+        pooled = np.sort(np.concatenate([c, b]))
+        best = None
+        for s in (0, 1):
+            if code == (2, 1)[s]:
+                continue
+            prev = -1
+            for l, q in enumerate(q_i):
+                k = min(N - 1, -(-int(q) * N // 10000))
+                if s == 0:
+                    t = pooled[k - 1]
+                    a, bb = int((c > t).sum()), int((b > t).sum())
+                else:
+                    t = pooled[N - k]
+                    a, bb = int((c < t).sum()), int((b < t).sum())
+                counts[r, s, l] = (a, bb, k)
+                m = a + bb
+                if m < min_tail_points or m == prev:
+                    continue
+                prev = m
+                J[r] += 1
+                p = hypergeom_upper_tail(a, m, n_c, n_b)
+                if best is None or p < best[0]:
+                    best = (p, s * L + l, a / n_c - bb / n_b, t)
+        if best is not None:
+            tail[r] = (min(1.0, int(J[r]) * best[0]), best[0], best[2], best[3])
+            which[r] = best[1]
+    return tail, which, J, n, counts
+
+
+def tail_verdict(tail, p_thr, min_excess: float = 0.0):
+    """tail_diff [R] int8 of the tail test: 1 where the test applies with J >=
+    1 (p is a number), p is below fp32(p_thr) and the excess is at least
+    fp32(min_excess), compared in fp32 as ``drift_verdict`` compares."""
+    d = np.asarray(tail, dtype=np.float32).reshape(-1, 4)
+    with np.errstate(invalid="ignore"):
+        return (~np.isnan(d[:, 0]) & (d[:, 0] < np.float32(p_thr)) & (d[:, 2] >= np.float32(min_excess))).astype(np.int8)
