@@ -98,6 +98,11 @@ class BrainConfig:
     min_tail_data_points: int = 20           # MIN_TAIL_DATA_POINTS (finite samples each side needs; >= 2)
     min_tail_points: int = 5                 # MIN_TAIL_POINTS (pooled samples beyond a level's threshold; >= 1)
     tail_min_excess: float = 0.0             # ML_PAIRWISE_TAIL_MIN_EXCESS (floor on the exceedance-share difference; in [0, 1))
+    # dependence gate of the pairwise verdict (docs/BRAIN_SPEC.md 4.7, K33; off by default): the rank-sum z re-evaluated
+    # with each side's sample size deflated by the autocorrelation of the pooled midranks along time; it only clears
+    pairwise_dependence: str = ""            # ML_PAIRWISE_DEPENDENCE: "" | OFF | RANK_ACF
+    pairwise_acf_max_lag: int = 8            # ML_PAIRWISE_ACF_MAX_LAG (L, the lags of the estimate; 1..16)
+    min_acf_points: int = 12                 # MIN_ACF_DATA_POINTS (finite samples a segment needs to contribute; >= 4)
     # ML_MULTIVARIATE_THRESHOLD: sigma-unit threshold of multivariate_normal (None = ``threshold``; the
     # per-metric thresholdN are per-axis multiples and do not apply to the whitened joint distance)
     multivariate_threshold: float | None = None
@@ -271,6 +276,9 @@ class BrainConfig:
         c.min_tail_data_points = _i(env, "MIN_TAIL_DATA_POINTS", c.min_tail_data_points)
         c.min_tail_points = _i(env, "MIN_TAIL_POINTS", c.min_tail_points)
         c.tail_min_excess = _f(env, "ML_PAIRWISE_TAIL_MIN_EXCESS", c.tail_min_excess)
+        c.pairwise_dependence = str(env.get("ML_PAIRWISE_DEPENDENCE", "") or "").strip() or c.pairwise_dependence
+        c.pairwise_acf_max_lag = _i(env, "ML_PAIRWISE_ACF_MAX_LAG", c.pairwise_acf_max_lag)
+        c.min_acf_points = _i(env, "MIN_ACF_DATA_POINTS", c.min_acf_points)
         c.pairwise_scale_min_ratio = _f(env, "ML_PAIRWISE_SCALE_MIN_RATIO", c.pairwise_scale_min_ratio)
         c.pairwise_scale_both = str(env.get("ML_PAIRWISE_SCALE_BOTH", "") or "").strip().lower() in (
             "1", "true", "yes", "on") or c.pairwise_scale_both

@@ -155,6 +155,8 @@ class Brain(BrainStateMixin):
         #                                        floor outside [0, 1] fails here
         C.TailTest.from_config(self.cfg)       # an unknown ML_PAIRWISE_TAIL_TEST / _SIDES, bad levels or point gates
         #                                        or an excess floor outside [0, 1) fail here
+        C.DependenceGate.from_config(self.cfg)  # an unknown ML_PAIRWISE_DEPENDENCE, a lag limit outside 1..16 or
+        #                                         MIN_ACF_DATA_POINTS < 4 fails here
         # auto_robust: the model each row took, kept between cycles (not checkpointed), and what the
         # last cycle ran: rows per model, and how many of them were selected anew
         from ..models.cache import AutoChoices
@@ -283,6 +285,9 @@ class Brain(BrainStateMixin):
             # effect-size gate (K19, off by default): rows are in no fixed
             # metric order here, so every row brings its own bound code
             diff = C.gate_diff(diff, cur, base, C.EffectGate.from_config(self.cfg), tables.bound, R)
+            # dependence gate (K33, off by default), before the optional tests, whose verdicts it does not touch: it
+            # only ever clears a verdict
+            diff = C.dependence_diff(diff, cur, seg_end, base, C.DependenceGate.from_config(self.cfg))
             # scale test (K27, off by default), after the gate: the gate never clears a scale verdict
             diff = C.scale_diff(diff, cur, base, C.ScaleTest.from_config(self.cfg))
             # per-pod test (K29, off by default), last: it only ever sets a verdict

@@ -394,6 +394,9 @@ class ArraysMixin:
         if ga.base_d is not None and C.DriftTest.from_config(self.b.cfg).enabled:
             # the drift test (K31) needs the pod boundaries too
             return self._score_models(works, now, ga, store)
+        if ga.base_d is not None and C.DependenceGate.from_config(self.b.cfg).enabled:
+            # the dependence gate (K33) needs the pod boundaries too
+            return self._score_models(works, now, ga, store)
         if ga.base_d is not None and C.TailTest.from_config(self.b.cfg).enabled:
             # the tail test (K32) is not part of the resident tick
             return self._score_models(works, now, ga, store)

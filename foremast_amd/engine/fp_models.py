@@ -288,15 +288,19 @@ class ModelsMixin:
                 # effect-size gate (K19): a verdict the tests set is kept only where the difference is large enough
                 bound = torch.tensor([cfg.rule_for(a).bound for a in p0.aliases], dtype=torch.int32, device=dev)
                 diff = C.gate_diff(diff, ga.cur_dev, ga.base_d, gate, bound, M)
-            # scale test (K27, off by default): a row whose spread differs is "different" whatever the gate said
-            diff = C.scale_diff(diff, ga.cur_dev, ga.base_d, C.ScaleTest.from_config(cfg))
-            pods, drift = C.PodTest.from_config(cfg), C.DriftTest.from_config(cfg)
-            if pods.enabled or drift.enabled:
+            pods, drift, dep = C.PodTest.from_config(cfg), C.DriftTest.from_config(cfg), C.DependenceGate.from_config(cfg)
+            if pods.enabled or drift.enabled or dep.enabled:
                 # per-pod test (K29): the window table keeps one slot per pod; windows fetched per job were
                 # concatenated before they got here and count as one pod each (the test then does not apply)
                 ends = (self.wt.pod_ends(ga.wcur) if ga.wcur is not None
                         else np.asarray(ga.cur_len, np.int32).reshape(-1, 1))
                 seg = torch.from_numpy(np.minimum(ends, n).astype(np.int32)).to(dev)
+                # dependence gate (K33), directly after the effect-size gate: it only ever clears a verdict, and the
+                # optional tests below set theirs after it
+                diff = C.dependence_diff(diff, ga.cur_dev, seg, ga.base_d, dep)
+            # scale test (K27, off by default): a row whose spread differs is "different" whatever the gates said
+            diff = C.scale_diff(diff, ga.cur_dev, ga.base_d, C.ScaleTest.from_config(cfg))
+            if pods.enabled or drift.enabled:
                 diff = C.pods_diff(diff, ga.cur_dev, seg, ga.base_d, pods)
                 # drift test (K31) over the same segments; one pod is one segment in time order, still a trend
                 diff = C.drift_diff(diff, ga.cur_dev, seg, ga.base_d, drift)

@@ -234,6 +234,10 @@ class CanaryScorer:
         self.tail = C.TailTest.from_config(cfg or BrainConfig())
         if self.tail.enabled and self.mode == "fused":
             raise ValueError("mode='fused' is not available with the tail test (ML_PAIRWISE_TAIL_TEST) enabled")
+        # dependence gate (K33): needs the pod boundaries like the drift test; refused the same way (_no_pods)
+        self.dependence = C.DependenceGate.from_config(cfg or BrainConfig())
+        if self.dependence.enabled and self.mode == "fused":
+            raise ValueError("mode='fused' is not available with the dependence gate (ML_PAIRWISE_DEPENDENCE) enabled")
         self.overlap = self.mode == "overlap"
         # workgroup caps of the two concurrent kernels of the overlap tick
         # (0 = one workgroup per row / per 4 rows); see tools/tick_breakdown.py
@@ -348,8 +352,14 @@ class CanaryScorer:
             raise ValueError(f"{what} is not available with the drift test (ML_PAIRWISE_DRIFT_TEST) enabled")
         if self.tail.enabled:
             raise ValueError(f"{what} is not available with the tail test (ML_PAIRWISE_TAIL_TEST) enabled")
+        if self.dependence.enabled:
+            raise ValueError(f"{what} is not available with the dependence gate (ML_PAIRWISE_DEPENDENCE) enabled")
 
     def _no_pods(self, base) -> None:
+        if self.dependence.enabled and base is not None and base.shape[1] > 0:
+            raise ValueError("CanaryScorer does not run the dependence gate (ML_PAIRWISE_DEPENDENCE): its rows carry "
+                             "no pod boundaries; score groups with a baseline op by op (ops.canary.dependence_diff "
+                             "after pairwise_tests)")
         if self.tail.enabled and base is not None and base.shape[1] > 0:
             raise ValueError("CanaryScorer does not run the tail test (ML_PAIRWISE_TAIL_TEST); score groups with a "
                              "baseline op by op (ops.canary.tail_diff after pairwise_tests)")

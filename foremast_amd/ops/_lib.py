@@ -55,6 +55,11 @@ _SIGS: dict[str, list] = {
     "fm_pairwise_tail": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_int, c_int, c_int, c_int,
                          c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_int, c_void_p, c_void_p,
                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    # K33: cur ld_c n_cur seg_end G base ld_b n_base R max_lag min_points p_thr tier dep rho n TA kept pairs dep_keep
+    # stream (seg_end may be null with G == 0)
+    "fm_pairwise_dependence": [c_void_p, c_i64, c_int, c_void_p, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_int,
+                               c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p],
     "fm_stats_decide": [c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p,
                         c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     "fm_service_reduce": [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p],

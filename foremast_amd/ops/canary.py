@@ -3,7 +3,7 @@ anomaly decision (K1+K7), service reduce, anomaly compaction, synthetic fleet
 (K11).
 
 GPU tensors run the hand-written CDNA4 kernels in ``csrc/kernels/``
-(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``pairwise_drift.hip``, ``pairwise_tail.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
+(``pairwise.hip``, ``pairwise_wide.hip``, ``pairwise_effect.hip``, ``pairwise_scale.hip``, ``pairwise_pods.hip``, ``pairwise_joint.hip``, ``pairwise_drift.hip``, ``pairwise_tail.hip``, ``pairwise_dependence.hip``, ``hist_stats.hip``, ``tick_front.hip``, ``canary_rows.hip``,
 ``decide.hip``, ``decide_2s.hip``, ``synth.hip``);
 CPU tensors run the vectorised numpy reference in
 :mod:`foremast_amd.ops.reference` (the BASELINE config-1 CPU path and the
@@ -1238,6 +1238,188 @@ def _tail_bucketed(cur, base, test: TailTest, bound, M: int) -> TailResult:
                        None if per_row is None else per_row.index_select(0, wd).cpu().numpy())
         for dst, src in zip(o.tensors(), r.tensors()):
             dst[wd] = src.to(dev)
+    return o
+
+
+DEPENDENCE_GATES = {"": "", "OFF": "", "RANK_ACF": "RANK_ACF"}
+ACF_MAX_LAG = ref.ACF_MAX_LAG
+
+
+@dataclass(frozen=True)
+class DependenceGate:
+    """Dependence gate of the pairwise verdict (K33, docs/BRAIN_SPEC.md 4.7): the
+    rank-sum z of current vs baseline with each side's sample size deflated by
+    a variance-inflation factor from the autocorrelation of the pooled midranks
+    along time inside each pod.  A row keeps its "different" verdict only while
+    the adjusted p-value is still below the threshold; the gate never sets a
+    verdict.  ``gate == ""`` = off."""
+
+    gate: str = ""                  # ML_PAIRWISE_DEPENDENCE: "" | OFF | RANK_ACF
+    p_threshold: float = 0.05       # ML_PAIRWISE_THRESHOLD
+    max_lag: int = 8                # ML_PAIRWISE_ACF_MAX_LAG: L, 1..16
+    min_points: int = 12            # MIN_ACF_DATA_POINTS: finite samples a segment needs to contribute
+
+    def __post_init__(self):
+        name = str(self.gate or "").strip().upper()
+        if name not in DEPENDENCE_GATES:
+            raise ValueError(f"unknown pairwise dependence gate {self.gate!r} (RANK_ACF or OFF)")
+        object.__setattr__(self, "gate", DEPENDENCE_GATES[name])
+        if not 1 <= int(self.max_lag) <= ACF_MAX_LAG:
+            raise ValueError(f"max_lag must lie in 1..{ACF_MAX_LAG}, got {self.max_lag!r}")
+        if int(self.min_points) < 4:
+            raise ValueError(f"min_points must be >= 4, got {self.min_points!r}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.gate != ""
+
+    @classmethod
+    def from_config(cls, cfg) -> "DependenceGate":
+        """The dependence gate of a ``BrainConfig`` (``pairwise_dependence``, ``pairwise_acf_max_lag``,
+        ``min_acf_points`` and the pairwise threshold)."""
+        return cls(cfg.pairwise_dependence, float(cfg.pairwise_threshold), int(cfg.pairwise_acf_max_lag),
+                   int(cfg.min_acf_points))
+
+
+@dataclass
+class DependenceResult:
+    dep: torch.Tensor                    # [R, 6] fp32: p_adj, z_adj, z, VIF_c, VIF_b, N
+    rho: torch.Tensor                    # [R, 2, 16] fp32: entry j = lag j + 1 of the current side / the baseline
+    n: torch.Tensor                      # [R, 2] int32: finite samples per side
+    TA: torch.Tensor                     # [R, 2] int64: T, A
+    kept: torch.Tensor                   # [R, 2] int32: kept segments per side
+    pairs: torch.Tensor                  # [R, 2, 16] int32: pairs per lag over the kept segments
+    dep_keep: torch.Tensor               # [R] int8
+
+    def tensors(self) -> tuple:
+        return (self.dep, self.rho, self.n, self.TA, self.kept, self.pairs, self.dep_keep)
+
+
+def alloc_dependence(R: int, device) -> DependenceResult:
+    """Output buffers of K33, which writes all of them for every row."""
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=device)  # noqa: E731
+    return DependenceResult(new((R, 6), torch.float32), new((R, 2, ACF_MAX_LAG), torch.float32),
+                            new((R, 2), torch.int32), new((R, 2), torch.int64), new((R, 2), torch.int32),
+                            new((R, 2, ACF_MAX_LAG), torch.int32), new((R,), torch.int8))
+
+
+# rows ``pairwise_dependence`` has sent down each route since the last reset:
+# "wave" / "wide" (K33's tiers), "host" (the numpy definition)
+_DEPENDENCE_ROUTE_ROWS = {"wave": 0, "wide": 0, "host": 0}
+
+
+def dependence_route_rows() -> dict[str, int]:
+    """Rows of GPU batches per dependence-gate route so far (a copy)."""
+    return dict(_DEPENDENCE_ROUTE_ROWS)
+
+
+def reset_dependence_route_rows() -> None:
+    for k in _DEPENDENCE_ROUTE_ROWS:
+        _DEPENDENCE_ROUTE_ROWS[k] = 0
+
+
+def _dependence_host(cur, seg_end, base, gate: DependenceGate) -> DependenceResult:
+    """The numpy definition on host arrays, as CPU tensors."""
+    o = ref.pairwise_dependence(cur, seg_end, base, gate.max_lag, gate.min_points)
+    return DependenceResult(*(torch.from_numpy(a) for a in o),
+                            torch.from_numpy(ref.dependence_verdict(o[0], gate.p_threshold)))
+
+
+def pairwise_dependence(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+                        gate: DependenceGate = DependenceGate("RANK_ACF"), tier: str = "auto",
+                        out: DependenceResult | None = None) -> DependenceResult:
+    """Dependence-adjusted rank-sum test of current vs baseline per row and
+    which rows keep a "different" verdict.
+
+    ``cur`` [R, n_cur] is pod-major, the samples of a pod in time order, one
+    column per time step; ``seg_end`` [R, G] int32 holds the column at which
+    pod g's segment ends (cumulative); ``base`` is one segment in column
+    order.  CPU tensors run the numpy definition, GPU tensors K33: its wave
+    tier up to PAIRWISE_MAX pooled columns, its workgroup tier up to
+    PAIRWISE_WIDE_MAX (``tier="wide"`` runs it for any batch that fits); a
+    batch padded wider than that, or with more than POD_MAX pod columns, is
+    bucketed by the rows' own used widths, and only rows really wider, or
+    with more than POD_MAX non-empty pods, run the definition on the host.
+    ``out``: buffers from ``alloc_dependence`` that take the result on every
+    route (the kernel writes them directly; the host and the bucketed routes
+    copy theirs in)."""
+    R, ldc = _rows(cur)
+    Rb, ldb = _rows(base)
+    check(R == Rb, "current/baseline row mismatch")
+    check(tier in ("auto", "wide"), "tier is 'auto' or 'wide'")
+    check(seg_end.dim() == 2 and seg_end.shape[0] == R and seg_end.dtype == torch.int32 and seg_end.is_contiguous()
+          and seg_end.device == cur.device, "seg_end must be a contiguous int32 [R, G] tensor on the samples' device")
+    def into_out(r: DependenceResult) -> DependenceResult:
+        if out is None:
+            return r
+        for dst, src in zip(out.tensors(), r.tensors()):
+            dst.copy_(src)
+        return out
+
+    if not cur.is_cuda:
+        return into_out(_dependence_host(cur.numpy(), seg_end.numpy(), base.numpy(), gate))
+    require_native(cur)
+    n_cur, n_base, G = cur.shape[1], base.shape[1], seg_end.shape[1]
+    if n_cur + n_base > PAIRWISE_WIDE_MAX or G > POD_MAX:
+        return into_out(_dependence_bucketed(cur, seg_end, base, gate))
+    wide = tier == "wide" or n_cur + n_base > PAIRWISE_MAX
+    _DEPENDENCE_ROUTE_ROWS["wide" if wide else "wave"] += R
+    o = out if out is not None else alloc_dependence(R, cur.device)
+    LIB.call("fm_pairwise_dependence", ptr(cur), ldc, n_cur, ptr(seg_end) if G else None, G, ptr(base), ldb, n_base,
+             R, int(gate.max_lag), int(gate.min_points), float(gate.p_threshold), 2 if wide else 0, ptr(o.dep),
+             ptr(o.rho), ptr(o.n), ptr(o.TA), ptr(o.kept), ptr(o.pairs), ptr(o.dep_keep), stream_of(cur))
+    return o
+
+
+def dependence_diff(diff: torch.Tensor, cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor,
+                    gate: DependenceGate) -> torch.Tensor:
+    """``diff & dep_keep`` for the op-by-op model paths (``diff`` from
+    ``pairwise_tests``, after the effect-size gate and before the optional
+    tests, whose own verdicts the gate does not touch: it only ever clears a
+    verdict).  ``diff`` itself when the gate is off."""
+    if not gate.enabled:
+        return diff
+    return diff & pairwise_dependence(cur, seg_end, base, gate).dep_keep.to(diff.dtype)
+
+
+def _dependence_bucketed(cur, seg_end, base, gate: DependenceGate) -> DependenceResult:
+    """A batch padded wider than K33 takes, or with more than POD_MAX pod
+    columns: rows bucketed by their own used widths exactly as
+    ``_drift_bucketed`` does (the wave tier, then the workgroup tier, each on a
+    narrowed copy whose segment ends are cut at the copy's width: the columns
+    cut off hold no finite sample, and dropping trailing missing samples
+    changes no rank and no pair).  A row whose pods past POD_MAX are all empty
+    loses only those columns; rows with more pods, and rows really wider than
+    PAIRWISE_WIDE_MAX, run the numpy definition on the host."""
+    R, G = seg_end.shape
+    dev = cur.device
+    Gk = min(G, POD_MAX)
+    lc, lb = used_width(cur).cpu(), used_width(base).cpu()
+    many = (seg_end[:, POD_MAX - 1] != seg_end[:, -1]).cpu() if G > POD_MAX else torch.zeros((R,), dtype=torch.bool)
+    fit = _bucket(lc, lb, ~many, PAIRWISE_MAX)
+    wide = _bucket(lc, lb, ~many & ~fit, PAIRWISE_WIDE_MAX)
+    o = alloc_dependence(R, dev)
+
+    def put(k, r):
+        for dst, src in zip(o.tensors(), r.tensors()):
+            dst[k] = src.to(dev)
+
+    for rows in (fit, wide):
+        k = torch.nonzero(rows).flatten()
+        if len(k):
+            a, b = max(1, int(lc[k].max())), max(1, int(lb[k].max()))
+            kd = k.to(dev)
+            put(kd, pairwise_dependence(cur.index_select(0, kd)[:, :a].contiguous(),
+                                        seg_end.index_select(0, kd)[:, :Gk].clamp(max=a).contiguous(),
+                                        base.index_select(0, kd)[:, :b].contiguous(), gate))
+    w = torch.nonzero(~(fit | wide)).flatten()
+    if len(w):
+        _DEPENDENCE_ROUTE_ROWS["host"] += len(w)
+        a, b = max(1, int(lc[w].max())), max(1, int(lb[w].max()))
+        wd = w.to(dev)
+        put(wd, _dependence_host(cur.index_select(0, wd)[:, :a].cpu().numpy(),
+                                 seg_end.index_select(0, wd).clamp(max=a).cpu().numpy(),
+                                 base.index_select(0, wd)[:, :b].cpu().numpy(), gate))
     return o
 
 

@@ -163,6 +163,28 @@ def _(cur, base, bound, quantiles, sides, p_threshold, min_points, min_tail_poin
             cur.new_empty((R, 2, L, 3), dtype=torch.int32), cur.new_empty((R,), dtype=torch.int8))
 
 
+# --------------------------------------------------------------------------- K33
+@custom_op(f"{NS}::pairwise_dependence", mutates_args=())
+def pairwise_dependence(cur: torch.Tensor, seg_end: torch.Tensor, base: torch.Tensor, p_threshold: float,
+                        max_lag: int, min_points: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(dep [R, 6] = p_adj, z_adj, z, VIF_c, VIF_b, N; rho [R, 2, 16] = the rank
+    autocorrelations of the current side and the baseline at lags 1..16;
+    dep_keep [R] int8) of the dependence gate; pod g of a row owns the columns
+    [seg_end[g - 1], seg_end[g]) of ``cur`` (K33)."""
+    _need(cur.dim() == 2 and base.dim() == 2 and cur.shape[0] == base.shape[0], "cur/base must be [R, n] with equal R")
+    _need(seg_end.dim() == 2 and seg_end.shape[0] == cur.shape[0] and seg_end.dtype == torch.int32,
+          "seg_end must be int32 [R, G]")
+    r = C.pairwise_dependence(cur.contiguous(), seg_end.contiguous(), base.contiguous(),
+                              C.DependenceGate("RANK_ACF", p_threshold, max_lag, min_points))
+    return r.dep.clone(), r.rho.clone(), r.dep_keep.clone()
+
+
+@register_fake(f"{NS}::pairwise_dependence")
+def _(cur, seg_end, base, p_threshold, max_lag, min_points):
+    R = cur.shape[0]
+    return (cur.new_empty((R, 6)), cur.new_empty((R, 2, C.ACF_MAX_LAG)), cur.new_empty((R,), dtype=torch.int8))
+
+
 # --------------------------------------------------------------------------- K1 + K7
 @custom_op(f"{NS}::stats_decide", mutates_args=())
 def stats_decide(hist: torch.Tensor, cur: torch.Tensor, n_hist: int, M: int, thr: torch.Tensor, bound: torch.Tensor,
@@ -289,5 +311,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "prophet_fit")

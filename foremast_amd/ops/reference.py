@@ -925,3 +925,102 @@ def tail_verdict(tail, p_thr, min_excess: float = 0.0):
     d = np.asarray(tail, dtype=np.float32).reshape(-1, 4)
     with np.errstate(invalid="ignore"):
         return (~np.isnan(d[:, 0]) & (d[:, 0] < np.float32(p_thr)) & (d[:, 2] >= np.float32(min_excess))).astype(np.int8)
+
+
+# ---------------------------------------------------------------------------
+# dependence gate of the pairwise verdict (K33): the rank-sum z of current vs
+# baseline with each side's sample size deflated by a variance-inflation factor
+# from the autocorrelation of the pooled midranks along time, straight from the
+# definition in docs/BRAIN_SPEC.md section 4.7
+
+ACF_MAX_LAG = 16
+
+
+def pairwise_dependence(cur, seg_end, base, max_lag: int = 8, min_points: int = 12):
+    """(dep [R, 6] fp32 = (p_adj, z_adj, z, VIF_c, VIF_b, N), rho [R, 2, 16]
+    fp32, n [R, 2] int32, TA [R, 2] int64 = (T, A), kept [R, 2] int32, pairs
+    [R, 2, 16] int32) per row; entry j of ``rho`` / ``pairs`` is lag j + 1.
+
+    ``cur`` is pod-major and pod g owns the columns [seg_end[g - 1],
+    seg_end[g]) in time order; ``base`` is one segment.  NaN / +-inf are
+    missing; samples compare as fp32 (-0.0 == 0.0).  n = the finite counts
+    (n1, n2), N their sum.  Over the N pooled finite values rank2 = 2 lt + t +
+    1 and a = rank2 - (N + 1); T = sum of a over the current side, A = sum of
+    a^2 over both, exact.  A lag is a column distance: the pair (i, i + k)
+    counts when both columns lie in the same segment and both are finite;
+    nothing is compacted.  A segment with n_s finite samples is kept when n_s
+    >= max(min_points, 1), with lags up to L_s = min(max_lag, n_s // 4): mean
+    = (sum a) / n_s, e = a - mean, c0 = sum e^2, c_k = sum over its pairs of
+    e_i e_(i+k), in fp64.  Per side C0 / C_k / pairs sum the kept segments,
+    rho_k = C_k / C0 (0 where C0 == 0), VIF = min(max(1, 1 + 2 sum_k (1 - k /
+    (L + 1)) rho_k), max(1, n_side / 2)).  z = T / sqrt(n1 n2 / (N (N - 1))
+    A), z_adj = z sqrt((1 / n1 + 1 / n2) / (VIF_c / n1 + VIF_b / n2)), p_adj =
+    erfc(|z_adj| / sqrt 2), in fp64, rounded to fp32 once; NaN when n1 < 2, n2
+    < 2 or A == 0.  The integers, rho and the VIFs are reported regardless."""
+    cur = np.asarray(cur, dtype=np.float32)
+    base = np.asarray(base, dtype=np.float32)
+    seg = np.asarray(seg_end, dtype=np.int64)
+    R, G = seg.shape
+    L = int(max_lag)
+    if not 1 <= L <= ACF_MAX_LAG:
+        raise ValueError(f"max_lag must lie in 1..{ACF_MAX_LAG}, got {max_lag!r}")
+    need = max(int(min_points), 1)
+    n_cur = cur.shape[1]
+    dep = np.full((R, 6), np.nan, dtype=np.float32)
+    rho = np.zeros((R, 2, ACF_MAX_LAG), dtype=np.float32)
+    n = np.zeros((R, 2), dtype=np.int32)
+    TA = np.zeros((R, 2), dtype=np.int64)
+    kept = np.zeros((R, 2), dtype=np.int32)
+    pairs = np.zeros((R, 2, ACF_MAX_LAG), dtype=np.int32)
+    w = 1.0 - np.arange(1, L + 1) / (L + 1.0)
+    for r in range(R):
+        x = np.concatenate([cur[r], base[r]]).astype(np.float64)
+        fin = np.isfinite(x)
+        n1, n2 = int(fin[:n_cur].sum()), int(fin[n_cur:].sum())
+        N = n1 + n2
+        v = np.sort(x[fin])
+        lt, le = np.searchsorted(v, x[fin], "left"), np.searchsorted(v, x[fin], "right")
+        a = np.zeros(len(x), dtype=np.int64)
+        a[fin] = 2 * lt + (le - lt) + 1 - (N + 1)
+        T, A = int(a[:n_cur][fin[:n_cur]].sum()), int((a * a).sum())
+        n[r], TA[r] = (n1, n2), (T, A)
+        # the segments: the pods of the current side, then the baseline
+        segs, lo = [], 0
+        for g in range(G):
+            hi = max(lo, min(int(seg[r, g]), n_cur))
+            segs.append((0, lo, hi))
+            lo = hi
+        segs.append((1, n_cur, len(x)))
+        C0, Ck = np.zeros(2), np.zeros((2, L))
+        for s, lo, hi in segs:
+            f, n_s = fin[lo:hi], int(fin[lo:hi].sum())
+            if n_s < need:
+                continue
+            kept[r, s] += 1
+            e = np.where(f, a[lo:hi] - float(a[lo:hi][f].sum()) / n_s, 0.0)
+            C0[s] += float((e * e).sum())
+            for k in range(1, min(L, n_s // 4) + 1):
+                both = f[:-k] & f[k:]
+                Ck[s, k - 1] += float((e[:-k] * e[k:])[both].sum())
+                pairs[r, s, k - 1] += int(both.sum())
+        vif = np.ones(2)
+        for s, n_s in ((0, n1), (1, n2)):
+            rk = Ck[s] / C0[s] if C0[s] > 0 else np.zeros(L)
+            rho[r, s, :L] = rk
+            vif[s] = min(max(1.0, 1.0 + 2.0 * float((w * rk).sum())), max(1.0, n_s / 2.0))
+        dep[r, 3:] = (vif[0], vif[1], N)
+        if n1 < 2 or n2 < 2 or A == 0:
+            continue
+        z = T / np.sqrt(float(n1) * n2 / (float(N) * (N - 1.0)) * A)
+        z_adj = z * np.sqrt((1.0 / n1 + 1.0 / n2) / (vif[0] / n1 + vif[1] / n2))
+        dep[r, :3] = (special.erfc(abs(z_adj) / np.sqrt(2.0)), z_adj, z)
+    return dep, rho, n, TA, kept, pairs
+
+
+def dependence_verdict(dep, p_thr):
+    """dep_keep [R] int8 of the dependence gate: 1 where the gate does not apply
+    (p_adj is NaN: the row keeps its verdict) or p_adj is below fp32(p_thr),
+    compared in fp32 as ``drift_verdict`` compares."""
+    p = np.asarray(dep, dtype=np.float32).reshape(-1, 6)[:, 0]
+    with np.errstate(invalid="ignore"):
+        return (np.isnan(p) | (p < np.float32(p_thr))).astype(np.int8)
