@@ -865,17 +865,27 @@ def make_tables(aliases_per_row: list[str], cfg, device) -> Tables:
 
 
 def rolling_bands(hist: torch.Tensor, T: int, M: int, tables: Tables, window: int = 60,
-                  min_count: int | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                  min_count: int | None = None,
+                  model: str = "moving_average") -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """moving_average bands at every time point of the history (the
     dashboard's metric bands, foremast-dashboard/src/config/metrics.js:21-29):
     center = trailing-window mean, upper = center + thr * std, lower =
     max(center - thr * std, min_lower_bound), with the metric's bound code
     masking the side it does not judge (NaN).  Row r uses table entry r % M.
-    Returns (center, upper, lower) [R, T] fp32 (K1 rolling kernel on GPU)."""
+    Returns (center, upper, lower) [R, T] fp32 (K1 rolling kernel on GPU).
+    ``model="robust"`` (alias ``"robust_moving_average"``) takes center and
+    std from the trailing window's median and MAD sigma instead (K34), so an
+    incident inside the window does not widen the band behind it."""
     from ..ops import misc as MI
     mc = tables.min_hist if min_count is None else min_count
-    w = max(1, min(int(window), MI.ROLLING_MAX_WINDOW, T))
-    mean, sd = MI.rolling_stats(hist, T, w, max(1, min(mc, w)))
+    if model in ("robust", "robust_moving_average"):
+        w = max(1, min(int(window), MI.ROLLING_ROBUST_MAX_WINDOW, T))
+        mean, sd, _ = MI.rolling_robust_stats(hist, T, w, max(1, min(mc, w)))
+    elif model == "moving_average":
+        w = max(1, min(int(window), MI.ROLLING_MAX_WINDOW, T))
+        mean, sd = MI.rolling_stats(hist, T, w, max(1, min(mc, w)))
+    else:
+        raise ValueError(f"rolling_bands: unknown model {model!r}")
     R = hist.shape[0]
     idx = torch.arange(R, device=mean.device) % M
     thr = tables.thr.to(mean.device)[idx].unsqueeze(1)

@@ -296,6 +296,21 @@ def _(x, T, w, min_count):
     return x.new_empty((x.shape[0], T)), x.new_empty((x.shape[0], T))
 
 
+# --------------------------------------------------------------------------- K34 rolling robust
+@custom_op(f"{NS}::rolling_robust_stats", mutates_args=())
+def rolling_robust_stats(x: torch.Tensor, T: int, w: int,
+                         min_count: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Trailing-window median / MAD sigma / finite count at every point of every row."""
+    c, s, n = MI.rolling_robust_stats(x, T, w, min_count)
+    return c.clone(), s.clone(), n.clone()
+
+
+@register_fake(f"{NS}::rolling_robust_stats")
+def _(x, T, w, min_count):
+    shape = (x.shape[0], T)
+    return x.new_empty(shape), x.new_empty(shape), x.new_empty(shape, dtype=torch.int32)
+
+
 # --------------------------------------------------------------------------- K10
 @custom_op(f"{NS}::prophet_fit", mutates_args=())
 def prophet_fit(Y: torch.Tensor, T: int, H: int, step_s: float) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -312,4 +327,4 @@ def _(Y, T, H, step_s):
 
 
 OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
-       "downstream_impact", "rolling_stats", "prophet_fit")
+       "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit")

@@ -1573,6 +1573,64 @@ def ref_rolling_stats(x: np.ndarray, w: int, min_count: int = 1) -> tuple[np.nda
 
 
 # ---------------------------------------------------------------------------
+# K34 rolling robust bands (csrc/kernels/rolling_robust.hip)
+# ---------------------------------------------------------------------------
+ROLLING_ROBUST_MAX_WINDOW = 1024     # one wave's register window: 64 lanes x 16 keys
+ROLLING_ROBUST_CHUNK = 512           # outputs a wave slides through (kChunk)
+
+
+def ref_rolling_robust_stats(x, w: int, min_count: int = 1):
+    """The definition of K34: :func:`ref_robust_stats` of the trailing window
+    ``x[r, max(0, t-w+1) : t+1]`` at every ``t`` of every row -> (center
+    [R, T] f32, sigma [R, T] f32, n [R, T] int32).  ``center`` and ``sigma``
+    are NaN where the window holds fewer than ``max(min_count, 1)`` finite
+    samples; ``n`` is reported regardless.  The windows at the start of a row
+    are the partial ones (the samples before the row count as missing)."""
+    x = np.asarray(x, np.float32)
+    R, T = x.shape
+    w = int(w)
+    center = np.empty((R, T), np.float32)
+    sigma = np.empty((R, T), np.float32)
+    n = np.empty((R, T), np.int32)
+    if R == 0 or T == 0:
+        return center, sigma, n
+    pad = np.concatenate([np.full((R, w - 1), np.nan, np.float32), x], axis=1)
+    win = np.lib.stride_tricks.sliding_window_view(pad, w, axis=1)          # [R, T, w], a view
+    step = max(1, (1 << 24) // (T * w))                                      # rows per pass: 64 MiB of windows
+    for r0 in range(0, R, step):
+        blk = win[r0:r0 + step]
+        c, s, k = ref_robust_stats(blk.reshape(-1, w), w)
+        center[r0:r0 + step], sigma[r0:r0 + step], n[r0:r0 + step] = (a.reshape(blk.shape[:2]) for a in (c, s, k))
+    few = n < max(int(min_count), 1)
+    center[few] = np.nan
+    sigma[few] = np.nan
+    return center, sigma, n
+
+
+def rolling_robust_stats(x: torch.Tensor, T: int, w: int, min_count: int = 1):
+    """K34: per-time-point (center, sigma, n) of :func:`ref_rolling_robust_stats`
+    over ``x[:, :T]``: the median / MAD band of the trailing window of ``w``
+    points, by a sorted window that slides on the GPU.  ``x`` may be any
+    column view with unit column stride: rows need 4-byte alignment only.
+    Returns (center [R, T] f32, sigma [R, T] f32, n [R, T] int32)."""
+    check(1 <= w <= ROLLING_ROBUST_MAX_WINDOW, f"rolling window must be in [1, {ROLLING_ROBUST_MAX_WINDOW}]")
+    check(x.dim() == 2 and x.dtype == torch.float32 and 0 < T <= x.shape[1], "x must be fp32 [R, >= T], T >= 1")
+    if not x.is_cuda:
+        c, s, n = ref_rolling_robust_stats(x.numpy()[:, :T], w, min_count)
+        return torch.from_numpy(c), torch.from_numpy(s), torch.from_numpy(n)
+    require_native(x)
+    check(x.stride(1) == 1 or x.shape[1] <= 1, "rows must have unit column stride")
+    R = x.shape[0]
+    center = torch.empty((R, T), dtype=torch.float32, device=x.device)
+    sigma = torch.empty((R, T), dtype=torch.float32, device=x.device)
+    n = torch.empty((R, T), dtype=torch.int32, device=x.device)
+    if R:
+        LIB.call("fm_rolling_robust_stats", ptr(x), x.stride(0) if R > 1 else max(x.stride(0), T), T, R, int(w), int(min_count), ptr(center),
+                 ptr(sigma), ptr(n), T, stream_of(x))
+    return center, sigma, n
+
+
+# ---------------------------------------------------------------------------
 # resident-history row gather (csrc/kernels/gather.hip)
 def gather_cols(src: torch.Tensor, rm: torch.Tensor | None, off: torch.Tensor, lim: torch.Tensor, ncols: int,
                 out: torch.Tensor) -> torch.Tensor:
