@@ -454,12 +454,19 @@ class Brain(BrainStateMixin):
                 "scale_smooth": self.cfg.seasonal_scale_smooth, "scale_floor": max(1e-3, self.cfg.seasonal_scale_floor),
                 "tail_z": min(3.0, max(0.5, float(self.cfg.quantile_tail_z)))}
 
+    def _hw_robust_args(self, algorithm: str) -> dict:
+        """``hw_k`` of a zoo call: ML_HW_ROBUST_K for ``robust_holt_winters``,
+        nothing for any other model."""
+        if zoo.canonical(algorithm) != "robust_holt_winters":
+            return {}
+        return {"hw_k": float(self.cfg.hw_robust_k)}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
                 **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm),
                 **self._auto_args(algorithm), **self._quantile_args(algorithm),
-                **self._seasonal_quantile_args(algorithm)}
+                **self._seasonal_quantile_args(algorithm), **self._hw_robust_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -1015,7 +1022,8 @@ class Brain(BrainStateMixin):
                                  **self._trend_args(self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_scale_args(self.cfg.hpa_forecast_algorithm),
-                                 **self._seasonal_quantile_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._seasonal_quantile_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._hw_robust_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

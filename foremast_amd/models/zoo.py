@@ -14,6 +14,8 @@ exponential_smoothing           SES, alpha grid                         K2 + ban
 double_exponential_smoothing    Holt, (alpha, beta) grid                K2 + band decide
 holt_winters                    additive HW, period from the FFT        K3 + K2 + band
 holt_winters_multiplicative     multiplicative HW (seasonal ratio)      K3 + K2 + band
+robust_holt_winters             additive HW, errors Huber-clipped at    K3 + K13 + K35 + band
+                                k sigma of the seasonal differences
 prophet                         trend+hinges+daily/weekly Fourier LSQ   K10 (f32 MFMA)
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
@@ -60,7 +62,7 @@ ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
               "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust",
-              "quantile_robust", "seasonal_quantile_robust")
+              "quantile_robust", "seasonal_quantile_robust", "robust_holt_winters")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -68,6 +70,8 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "double_exponential_smoothing": "double_exponential_smoothing", "holt": "double_exponential_smoothing",
            "holt_winters": "holt_winters", "hw": "holt_winters", "triple_exponential_smoothing": "holt_winters",
            "holt_winters_multiplicative": "holt_winters_multiplicative", "hw_mul": "holt_winters_multiplicative",
+           "robust_holt_winters": "robust_holt_winters", "robust_hw": "robust_holt_winters",
+           "hw_robust": "robust_holt_winters",
            "prophet": "prophet", "lstm": "lstm", "bivariate_normal": "bivariate_normal", "bivariate": "bivariate_normal",
            "multivariate_normal": "multivariate_normal", "multivariate": "multivariate_normal",
            "mvn": "multivariate_normal",
@@ -161,7 +165,7 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
            mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1, holdout: int = 0,
            candidates=None, zcap: float = 8.0, margin: float = 0.05, auto: "AutoContext | None" = None,
-           trend_block: int | None = None, tail_z: float = 2.0) -> RowDecision:
+           trend_block: int | None = None, tail_z: float = 2.0, hw_k: float = 3.0) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -183,7 +187,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     there is one.  ``tail_z`` is ``quantile_robust``'s: the threshold at which
     its band ends on the history's own tail quantiles;
     ``seasonal_quantile_robust`` takes it too, with ``seasonal_scale_robust``'s
-    parameters."""
+    parameters.  ``hw_k`` is ``robust_holt_winters``'s: its one-step errors are
+    clipped at ``hw_k`` sigmas (``ops.smoothing.hw_robust_clip``)."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -224,6 +229,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (fit.nfin.to(cur.device) >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fit.forecast, fit.sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "robust_holt_winters":
+        # refitted on every call (no model cache); gated on the fit's own finite count
+        fc, sigma, nfin = _robust_holt_winters(hist, T, H, period, hw_k)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin.to(cur.device) >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
     if algo == "seasonal_robust":
         # the kernel counts the finite samples it models: no separate history pass
         fc, sigma, nfin = _seasonal_robust(hist, T, H, period, smooth)
@@ -367,7 +378,24 @@ def _shift_robust(hist, T, cur, horizon, M, tables, diff, block, k, min_blocks) 
 ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt_winters": 2,
             "holt_winters_multiplicative": 3}
 FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust",
-                                 "seasonal_scale_robust", "auto_robust", "seasonal_quantile_robust")
+                                 "seasonal_scale_robust", "auto_robust", "seasonal_quantile_robust",
+                                 "robust_holt_winters")
+
+
+def _robust_holt_winters(hist, T, H, period, k):
+    """Additive Holt-Winters whose one-step errors are Huber-clipped at ``k``
+    sigmas of the row's seasonal differences (K35, ``ops.smoothing.es_fit_robust``)
+    -> (forecast [R, H], sigma [R], finite count [R]).  ``period`` None:
+    detected from the history, as for ``holt_winters``.  A history shorter
+    than two periods gets ``robust_moving_average_all``'s constant forecast
+    (median, MAD sigma: K13).  Refitted on every call: no model cache."""
+    m = int(period or _detect_period(hist, T))
+    if 2 * m > T:
+        from ..ops import misc as MI
+        center, sigma, nfin = MI.robust_stats(hist[:, :T], T)
+        return center[:, None].expand(-1, H), sigma, nfin
+    fit = SM.es_fit_robust(hist, T, H, m, k=k)
+    return fit.forecast, fit.sigma, fit.nfin
 
 
 def seasonal_start(T: int, period: int | None) -> int:
@@ -625,7 +653,7 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
              scale_floor: float = 0.1, shift_threshold: float = 4.0, min_blocks: int = 2, holdout: int = 0,
              candidates=None, zcap: float = 8.0, margin: float = 0.05,
              auto: AutoContext | None = None, trend_block: int | None = None,
-             tail_z: float = 2.0) -> tuple[torch.Tensor, torch.Tensor]:
+             tail_z: float = 2.0, hw_k: float = 3.0) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]; sigma [R, H],
     one per step, from ``seasonal_scale_robust`` unless it fell back; a pair
@@ -646,6 +674,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
                 kind, m = 1, 1
         fit = SM.es_fit(hist, T, kind, H, m, prune=SM.HW_SCAN_PRUNE)
         return fit.forecast, fit.sigma
+    if algo == "robust_holt_winters":
+        return _robust_holt_winters(hist, T, H, period, hw_k)[:2]      # (a CacheContext is ignored: refitted)
     if algo == "prophet":
         fit = LQ.prophet_fit(hist, T, H)
         return fit.forecast, fit.sigma

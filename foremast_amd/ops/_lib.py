@@ -74,6 +74,10 @@ _SIGS: dict[str, list] = {
                       + [c_float, c_int, c_void_p],
     "fm_hw_scan_supported": [c_int, c_int, c_int],
     "fm_hw_scan_set_probe": [c_void_p],
+    # K35: x ld T R cand G m H clip loss nobs nclip state fc sigma best nfin season_out stream
+    "fm_hw_robust_fit": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_int, c_int, c_int] + [c_void_p] * 11,
+    "fm_hw_robust_supported": [c_int, c_int, c_int],
+    "fm_hw_robust_set_probe": [c_void_p],
     "fm_ipc_handle_size": [],
     "fm_ipc_get_handle": [c_void_p, c_void_p, c_void_p],
     "fm_ipc_open": [c_void_p, c_void_p],

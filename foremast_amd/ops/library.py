@@ -234,6 +234,26 @@ def _(x, T, kind, H, m, grid):
     return (x.new_empty((R, H)), x.new_empty((R,)), x.new_empty((R,), dtype=torch.int32), x.new_empty((R, G)))
 
 
+# --------------------------------------------------------------------------- K35
+@custom_op(f"{NS}::es_fit_robust", mutates_args=())
+def es_fit_robust(x: torch.Tensor, T: int, H: int, m: int, grid: torch.Tensor,
+                  clip: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Huber-clipped additive Holt-Winters grid fit at the per-row thresholds
+    ``clip`` [R]: (forecast [R,H], sigma [R], best candidate [R] int32,
+    truncated loss [R,G], clipped steps [R,G] int32)."""
+    _need(grid.dim() == 2 and grid.shape[1] == 3, "grid must be [G, 3] (alpha, beta, gamma)")
+    f = SM.es_fit_robust(x, T, H, m, grid=grid.detach().cpu().numpy().astype(np.float32), clip=clip)
+    return (f.forecast.clone(), f.sigma.clone(), f.best.to(torch.int32).clone(), f.sse.clone(),
+            f.nclip.to(torch.int32).clone())
+
+
+@register_fake(f"{NS}::es_fit_robust")
+def _(x, T, H, m, grid, clip):
+    R, G = x.shape[0], grid.shape[0]
+    return (x.new_empty((R, H)), x.new_empty((R,)), x.new_empty((R,), dtype=torch.int32), x.new_empty((R, G)),
+            x.new_empty((R, G), dtype=torch.int32))
+
+
 # --------------------------------------------------------------------------- K3
 @custom_op(f"{NS}::fft_seasonal", mutates_args=())
 def fft_seasonal(x: torch.Tensor, nr: int, min_period: float,
@@ -326,5 +346,5 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
-OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "fft_seasonal", "lstm_stack",
+OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "es_fit_robust", "fft_seasonal", "lstm_stack",
        "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit")

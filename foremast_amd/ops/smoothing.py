@@ -57,6 +57,7 @@ class ESFit:
     sse: torch.Tensor        # [R, G]
     model: ESState | None = None
     nfin: torch.Tensor | None = None   # [R] int32 finite history samples (a by-product of the fit)
+    nclip: torch.Tensor | None = None  # [R, G] int32 clipped steps (es_fit_robust only)
 
 
 HALF_SEASON_MIN_M = 1000     # <= ~10 laps of a 7-day history: measured within 2e-3 of fp32 (tests)
@@ -216,6 +217,94 @@ def _hw_scan_fit(x: torch.Tensor, T: int, R: int, cand: torch.Tensor, G: int, m:
         model = ESState(2, m, cand[b].contiguous(), state[pid].contiguous(), season,
                         sse.gather(1, b[:, None])[:, 0].contiguous(), nobs[pid].contiguous())
     return ESFit(fc, sig, best, sse, model, nfin)
+
+
+def hw_robust_supported(T: int, G: int, m: int) -> bool:
+    """Shapes the Huber-clipped scan fit covers (csrc/kernels/hw_robust_scan.hip,
+    the launcher's own plan): 192 <= m <= 1536, G <= 32, 2 m <= T, fewer than
+    128 laps and the row within a workgroup's LDS."""
+    return bool(LIB.load().fm_hw_robust_supported(int(T), int(G), int(m)))
+
+
+def hw_robust_clip(x: torch.Tensor, T: int | None, m: int, k: float = 3.0) -> torch.Tensor:
+    """The per-row clipping threshold of :func:`es_fit_robust`, ``k * sigma_d /
+    sqrt(2)`` [R] fp32: ``sigma_d`` is the median/MAD sigma
+    (:func:`ops.misc.ref_robust_stats`, K13 on the GPU) of the seasonal
+    differences ``d[t] = x[t] - x[t - m]``, ``m <= t < T`` (missing where either
+    sample is); a difference of two one-step errors has twice their variance,
+    hence the ``sqrt(2)``.  ``+inf`` (no clipping) for a row with fewer than 2
+    finite differences or ``sigma_d == 0``."""
+    from . import misc as MI
+    check(x.dim() == 2 and x.dtype == torch.float32, "x must be [R, T] float32")
+    T = x.shape[1] if T is None else int(T)
+    inf = torch.full((x.shape[0],), float("inf"), dtype=torch.float32, device=x.device)
+    if T - m < 2 or x.shape[0] == 0:
+        return inf
+    d = x[:, m:T] - x[:, :T - m]
+    d = torch.where(torch.isfinite(d), d, torch.full_like(d, float("nan")))
+    _, sd, nd = MI.robust_stats(d, T - m)
+    c = sd * np.float32(float(k) / np.sqrt(2.0))
+    return torch.where((nd >= 2) & (sd > 0) & torch.isfinite(c), c, inf)
+
+
+def es_fit_robust(x: torch.Tensor, T: int | None, H: int, m: int = 1440, grid: np.ndarray | None = None,
+                  k: float = 3.0, clip: torch.Tensor | None = None, keep_state: bool = False) -> ESFit:
+    """Additive Holt-Winters grid fit whose one-step errors are Huber-clipped at
+    a per-row threshold (:func:`ref_es_fit_robust` is the definition): a past
+    incident moves level, trend and seasonal indices by at most the threshold
+    per step, adds at most its square to a candidate's loss, and so neither
+    widens sigma nor steers the grid search.  ``clip`` [R] fp32 is the
+    threshold (default :func:`hw_robust_clip` at ``k``; not finite or <= 0: that
+    row runs unclipped, the plain fit).  ``sse`` holds the truncated losses,
+    ``nclip`` [R, G] the clipped steps of every candidate.  No consistency
+    correction is applied to sigma (at k = 3 the truncation removes under 1 %
+    of a normal's variance).
+
+    A GPU tensor runs the speculate-and-verify scan kernel
+    (csrc/kernels/hw_robust_scan.hip) where :func:`hw_robust_supported`;
+    shapes outside the kernel's range, and CPU tensors, run the numpy
+    definition on the host."""
+    check(x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1, "x must be [R, T] float32")
+    R = x.shape[0]
+    T = x.shape[1] if T is None else int(T)
+    m = int(m)
+    check(m >= 1 and H >= 0, "m >= 1 and H >= 0")
+    grid = default_grid(2) if grid is None else np.asarray(grid, np.float32)
+    G = grid.shape[0]
+    if clip is None:
+        clip = hw_robust_clip(x, T, m, k)
+    check(clip.dim() == 1 and clip.shape[0] == R, "clip must be [R]")
+    clip = clip.to(device=x.device, dtype=torch.float32).contiguous()
+    d = x.device
+    if x.is_cuda:
+        require_native(x)
+    if not x.is_cuda or not hw_robust_supported(T, G, m):
+        fc, sig, best, sse, ncl, st = ref_es_fit_robust(x[:, :T].cpu().numpy(), H, m, grid, clip.cpu().numpy(),
+                                                        return_state=True)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+        model = None
+        if keep_state:
+            model = ESState(2, m, t(grid[best]), t(st["state"]), t(st["season"]), t(st["sse"]), t(st["nobs"]))
+        nfin = torch.isfinite(x[:, :T]).sum(1).to(torch.int32)
+        return ESFit(t(fc), t(sig), t(best), t(sse), model, nfin, t(ncl))
+    cand = torch.from_numpy(grid).to(d)
+    sse = torch.empty((R, G), dtype=torch.float32, device=d)
+    nobs = torch.empty((R, G), dtype=torch.int32, device=d)
+    ncl = torch.empty((R, G), dtype=torch.int32, device=d)
+    state = torch.empty((R, 3), dtype=torch.float32, device=d)
+    fc = torch.empty((R, H), dtype=torch.float32, device=d)
+    sig = torch.empty((R,), dtype=torch.float32, device=d)
+    best = torch.empty((R,), dtype=torch.int32, device=d)
+    nfin = torch.empty((R,), dtype=torch.int32, device=d)
+    season = torch.empty((R, m), dtype=torch.float32, device=d) if keep_state else None
+    LIB.call("fm_hw_robust_fit", ptr(x), x.stride(0), T, R, ptr(cand), G, m, H, ptr(clip), ptr(sse), ptr(nobs),
+             ptr(ncl), ptr(state), ptr(fc), ptr(sig), ptr(best), ptr(nfin), ptr(season), stream_of(x))
+    model = None
+    if keep_state:
+        b = best.long()[:, None]
+        model = ESState(2, m, cand[b[:, 0]].contiguous(), state, season, sse.gather(1, b)[:, 0].contiguous(),
+                        nobs.gather(1, b)[:, 0].contiguous())
+    return ESFit(fc, sig, best, sse, model, nfin, ncl)
 
 
 def _half_season_of(season: torch.Tensor, best: torch.Tensor, R: int, GP: int, m: int,
@@ -396,6 +485,93 @@ def ref_es_fit(x: np.ndarray, kind: int, H: int, m: int, grid: np.ndarray, retur
               .astype(np.float32), "season": None if season is None else season[pid],
               "sse": sse[np.arange(R), best].astype(np.float32), "nobs": n[pid].astype(np.int32)}
         out = out + (st,)
+    return out
+
+
+def ref_es_fit_robust(x: np.ndarray, H: int, m: int, grid: np.ndarray, clip: np.ndarray, return_state: bool = False):
+    """The definition of the Huber-clipped additive Holt-Winters fit (fp32
+    recursion in numpy, vectorised over rows x candidates).  Initialisation,
+    absolute phases and the ragged-row / missing-sample rules are
+    :func:`ref_es_fit`'s for kind 2.  Every later step, with the row's
+    threshold ``c = clip[r]``::
+
+        lt = lvl + tr;  pred = lt + s;  e = x - pred;  clipped = |e| > c
+        x* = x if not clipped else pred + copysign(c, e)
+        ec = e if not clipped else copysign(c, e)
+        level / trend / season: the kind-2 formulas of _step with x* for x
+        loss += ec^2 (fp64);  n += 1;  nclip += clipped
+
+    A candidate's loss is the truncated squared error; ``best``, ``sigma`` and
+    the forecast follow from the losses as in :func:`ref_es_fit`.  A ``clip``
+    that is not finite or <= 0 leaves its row unclipped (``clip = +inf``
+    reproduces ``ref_es_fit(kind=2)`` bit for bit).  Returns (forecast [R, H],
+    sigma [R], best [R] int32, loss [R, G] fp32, nclip [R, G] int32) and, with
+    ``return_state``, the winner's state as :func:`ref_es_fit` returns it."""
+    x = np.asarray(x, dtype=np.float32)
+    R, T = x.shape
+    G = grid.shape[0]
+    al, be, ga = (np.tile(grid[:, i], R) for i in range(3))
+    c = np.asarray(clip, np.float32)
+    c = np.repeat(np.where(np.isfinite(c) & (c > 0), c, np.float32(np.inf)), G).astype(np.float32)
+    xr = np.repeat(x, G, axis=0)
+    P = R * G
+    rows = np.arange(P)
+    fin = np.isfinite(xr)
+    base = np.where(fin.any(1), fin.argmax(1), T) if T else np.zeros(P, np.int64)
+    none = base >= T
+
+    def nanmean(lo, hi):
+        idx = lo[:, None] + np.arange(m)[None, :]
+        v = np.take_along_axis(xr, np.minimum(idx, T - 1), 1)
+        ok = (idx < hi[:, None]) & np.isfinite(v)
+        s = np.where(ok, v, 0).sum(1, dtype=np.float32)
+        return (s / np.maximum(ok.sum(1), 1)).astype(np.float32), ok.sum(1), v, ok
+    e1 = np.minimum(base + m, T)
+    e2 = np.minimum(base + 2 * m, T)
+    s1, _, v1, ok1 = nanmean(np.minimum(base, T - 1), e1)
+    s2, c2, _, _ = nanmean(np.minimum(e1, T - 1), e2)
+    c2 = np.where(e1 >= T, 0, c2)
+    lvl = np.where(none, np.float32(np.nan), s1).astype(np.float32)
+    tr = np.where(c2 > 0, (s2 - s1) / np.float32(m), 0).astype(np.float32)
+    season = np.zeros((P, m), np.float32)
+    np.put_along_axis(season, (base[:, None] + np.arange(m)[None, :]) % m, np.where(ok1, v1 - s1[:, None], 0)
+                      .astype(np.float32), 1)
+    t0 = base + m
+    loss = np.zeros(P, np.float64)
+    n = np.zeros(P, np.int64)
+    ncl = np.zeros(P, np.int64)
+    f1 = np.float32(1)
+    for t in range(int(t0.min()) if P else T, T):
+        xt = xr[:, t]
+        ok = (t >= t0) & np.isfinite(xt)
+        miss = (t >= t0) & ~ok
+        x0 = np.where(ok, xt, 0).astype(np.float32)
+        s_old = season[:, t % m]
+        pred = lvl + tr + s_old
+        e = np.where(ok, x0 - pred, 0).astype(np.float32)
+        clipped = ok & (np.abs(e) > c)
+        ce = np.copysign(c, e)
+        xs = np.where(clipped, pred + ce, x0).astype(np.float32)
+        ec = np.where(clipped, ce, e).astype(np.float32)
+        nl = al * (xs - s_old) + (f1 - al) * (lvl + tr)
+        nt = be * (nl - lvl) + (f1 - be) * tr
+        s_new = ga * (xs - nl) + (f1 - ga) * s_old
+        lvl = np.where(ok, nl, np.where(miss, lvl + tr, lvl)).astype(np.float32)
+        tr = np.where(ok, nt, tr).astype(np.float32)
+        season[rows, t % m] = np.where(ok, s_new, s_old).astype(np.float32)
+        loss += ec.astype(np.float64) ** 2
+        n += ok
+        ncl += clipped
+    with np.errstate(over="ignore"):
+        loss = np.where(np.isfinite(loss) & ~np.isfinite(loss.astype(np.float32)), np.inf, loss).reshape(R, G)
+    best = np.argmin(np.where(np.isfinite(loss), loss, np.inf), axis=1)
+    pid = np.arange(R) * G + best
+    fc, sig = _forecast(2, m, lvl[pid], tr[pid], season[pid], T % m, loss[np.arange(R), best], n[pid], H)
+    out = (fc, sig, best.astype(np.int32), loss.astype(np.float32), ncl.reshape(R, G).astype(np.int32))
+    if return_state:
+        out = out + ({"state": np.stack([lvl[pid], tr[pid], np.full(R, T % m, np.float32)], 1).astype(np.float32),
+                      "season": season[pid], "sse": loss[np.arange(R), best].astype(np.float32),
+                      "nobs": n[pid].astype(np.int32)},)
     return out
 
 
