@@ -139,6 +139,10 @@ class BrainConfig:
     # robust_holt_winters: one-step errors are clipped at this many sigmas of the row's seasonal differences
     # (<= 0: nothing is clipped, the plain additive fit)
     hw_robust_k: float = 3.0                 # ML_HW_ROBUST_K
+    # robust_prophet: Huber threshold in MAD sigmas of the residuals (<= 0: least squares over the finite
+    # samples) and the reweighted passes after the least-squares one, clamped to 0 ... 16
+    prophet_robust_k: float = 3.0            # ML_PROPHET_ROBUST_K
+    prophet_robust_iters: int = 5            # ML_PROPHET_ROBUST_ITERS
     max_stuck_seconds: float = 90.0          # MAX_STUCK_IN_SECONDS
     max_cache_size: int = 100000             # MAX_CACHE_SIZE (fitted models kept between cycles, models/cache.py)
     model_refit_seconds: float = 6 * 3600.0  # MODEL_REFIT_SECONDS: re-run the grid fit of a cached model after this
@@ -305,6 +309,8 @@ class BrainConfig:
         c.auto_candidates = env.get("AUTO_CANDIDATES", c.auto_candidates) or ""
         c.quantile_tail_z = min(3.0, max(0.5, _f(env, "QUANTILE_TAIL_Z", c.quantile_tail_z)))
         c.hw_robust_k = _f(env, "ML_HW_ROBUST_K", c.hw_robust_k)
+        c.prophet_robust_k = _f(env, "ML_PROPHET_ROBUST_K", c.prophet_robust_k)
+        c.prophet_robust_iters = min(16, max(0, _i(env, "ML_PROPHET_ROBUST_ITERS", c.prophet_robust_iters)))
         c.max_stuck_seconds = _f(env, "MAX_STUCK_IN_SECONDS", c.max_stuck_seconds)
         c.max_cache_size = _i(env, "MAX_CACHE_SIZE", c.max_cache_size)
         c.model_refit_seconds = _f(env, "MODEL_REFIT_SECONDS", c.model_refit_seconds)

@@ -461,12 +461,21 @@ class Brain(BrainStateMixin):
             return {}
         return {"hw_k": float(self.cfg.hw_robust_k)}
 
+    def _prophet_robust_args(self, algorithm: str) -> dict:
+        """``prophet_k`` and ``prophet_iters`` of a zoo call: ML_PROPHET_ROBUST_K and
+        ML_PROPHET_ROBUST_ITERS for ``robust_prophet``, nothing for any other model."""
+        if zoo.canonical(algorithm) != "robust_prophet":
+            return {}
+        return {"prophet_k": float(self.cfg.prophet_robust_k),
+                "prophet_iters": min(16, max(0, int(self.cfg.prophet_robust_iters)))}
+
     def _model_args(self, algorithm: str) -> dict:
         """The configured parameters of a zoo decision by ``algorithm``."""
         return {**self._seasonal_args(algorithm), **self._shift_args(algorithm), **self._trend_args(algorithm),
                 **self._seasonal_trend_args(algorithm), **self._seasonal_scale_args(algorithm),
                 **self._auto_args(algorithm), **self._quantile_args(algorithm),
-                **self._seasonal_quantile_args(algorithm), **self._hw_robust_args(algorithm)}
+                **self._seasonal_quantile_args(algorithm), **self._hw_robust_args(algorithm),
+                **self._prophet_robust_args(algorithm)}
 
     def _lstm_model(self):
         """The configured forecaster (LSTM_HIDDEN / LSTM_LAYERS / LSTM_MULTIVARIATE),
@@ -1023,7 +1032,8 @@ class Brain(BrainStateMixin):
                                  **self._seasonal_trend_args(self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_scale_args(self.cfg.hpa_forecast_algorithm),
                                  **self._seasonal_quantile_args(self.cfg.hpa_forecast_algorithm),
-                                 **self._hw_robust_args(self.cfg.hpa_forecast_algorithm))
+                                 **self._hw_robust_args(self.cfg.hpa_forecast_algorithm),
+                                 **self._prophet_robust_args(self.cfg.hpa_forecast_algorithm))
         except (ValueError, RuntimeError) as e:
             log.warning("HPA forecast skipped: %s", e)
             return

@@ -678,6 +678,8 @@ class ModelsMixin:
             return zoo.forecast(algo, lazy.materialize(zoo.trend_start(sub.T)), sub.T, H, **b._trend_args(algo))
         elif algo == "robust_holt_winters":
             return zoo.forecast(algo, lazy.materialize(0), sub.T, H, **b._hw_robust_args(algo))
+        elif algo == "robust_prophet":
+            return zoo.forecast(algo, lazy.materialize(0), sub.T, H, **b._prophet_robust_args(algo))
         elif algo == "auto_robust":
             # its candidates read different spans: gathered from column 0; the rows' remembered
             # choices go in, what is selected now comes back into the brain's memory and counters

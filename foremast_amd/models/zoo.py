@@ -17,6 +17,8 @@ holt_winters_multiplicative     multiplicative HW (seasonal ratio)      K3 + K2 
 robust_holt_winters             additive HW, errors Huber-clipped at    K3 + K13 + K35 + band
                                 k sigma of the seasonal differences
 prophet                         trend+hinges+daily/weekly Fourier LSQ   K10 (f32 MFMA)
+robust_prophet                  the same design, Huber IRLS at k sigma, K36 (f32 MFMA) + band
+                                missing samples weighted zero
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
 multivariate_normal             joint Mahalanobis over all metrics      K12
@@ -62,7 +64,7 @@ ALGORITHMS = ("moving_average_all", "moving_average", "exponential_smoothing", "
               "holt_winters", "holt_winters_multiplicative", "prophet", "lstm", "bivariate_normal", "multivariate_normal",
               "robust_moving_average_all", "robust_moving_average", "seasonal_robust", "shift_robust",
               "trend_robust", "robust_multivariate", "seasonal_trend_robust", "seasonal_scale_robust", "auto_robust",
-              "quantile_robust", "seasonal_quantile_robust", "robust_holt_winters")
+              "quantile_robust", "seasonal_quantile_robust", "robust_holt_winters", "robust_prophet")
 
 ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average_all",
            "moving_average": "moving_average", "ma": "moving_average",
@@ -72,6 +74,7 @@ ALIASES = {"moving_average_all": "moving_average_all", "ma_all": "moving_average
            "holt_winters_multiplicative": "holt_winters_multiplicative", "hw_mul": "holt_winters_multiplicative",
            "robust_holt_winters": "robust_holt_winters", "robust_hw": "robust_holt_winters",
            "hw_robust": "robust_holt_winters",
+           "robust_prophet": "robust_prophet", "prophet_robust": "robust_prophet", "huber_prophet": "robust_prophet",
            "prophet": "prophet", "lstm": "lstm", "bivariate_normal": "bivariate_normal", "bivariate": "bivariate_normal",
            "multivariate_normal": "multivariate_normal", "multivariate": "multivariate_normal",
            "mvn": "multivariate_normal",
@@ -165,7 +168,8 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            shift_threshold: float = 4.0, min_blocks: int = 2, trend_min_blocks: int = 3,
            mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1, holdout: int = 0,
            candidates=None, zcap: float = 8.0, margin: float = 0.05, auto: "AutoContext | None" = None,
-           trend_block: int | None = None, tail_z: float = 2.0, hw_k: float = 3.0) -> RowDecision:
+           trend_block: int | None = None, tail_z: float = 2.0, hw_k: float = 3.0, prophet_k: float = 3.0,
+           prophet_iters: int = 5) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -188,7 +192,11 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     its band ends on the history's own tail quantiles;
     ``seasonal_quantile_robust`` takes it too, with ``seasonal_scale_robust``'s
     parameters.  ``hw_k`` is ``robust_holt_winters``'s: its one-step errors are
-    clipped at ``hw_k`` sigmas (``ops.smoothing.hw_robust_clip``)."""
+    clipped at ``hw_k`` sigmas (``ops.smoothing.hw_robust_clip``).
+    ``prophet_k`` and ``prophet_iters`` are ``robust_prophet``'s: the Huber
+    threshold in MAD sigmas of the residuals (not finite or <= 0: least squares
+    over the finite samples) and the reweighted passes after the first
+    (``ops.lsq.prophet_fit_robust``)."""
     algo = canonical(algorithm)
     n = cur.shape[1]
     if algo == "moving_average_all":
@@ -232,6 +240,12 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     if algo == "robust_holt_winters":
         # refitted on every call (no model cache); gated on the fit's own finite count
         fc, sigma, nfin = _robust_holt_winters(hist, T, H, period, hw_k)
+        has_cur = torch.isfinite(cur).any(1).to(torch.int32)
+        valid = (nfin.to(cur.device) >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
+        return band(fc, sigma, horizon, cur, M, tables, diff, valid)
+    if algo == "robust_prophet":
+        # refitted on every call (no model cache); gated on the fit's own finite count
+        fc, sigma, nfin = _robust_prophet(hist, T, H, prophet_k, prophet_iters)
         has_cur = torch.isfinite(cur).any(1).to(torch.int32)
         valid = (nfin.to(cur.device) >= max(tables.min_hist, 1)).to(torch.int32) | (has_cur << 1)
         return band(fc, sigma, horizon, cur, M, tables, diff, valid)
@@ -379,7 +393,18 @@ ES_KINDS = {"exponential_smoothing": 0, "double_exponential_smoothing": 1, "holt
             "holt_winters_multiplicative": 3}
 FORECASTERS = tuple(ES_KINDS) + ("prophet", "lstm", "seasonal_robust", "trend_robust", "seasonal_trend_robust",
                                  "seasonal_scale_robust", "auto_robust", "seasonal_quantile_robust",
-                                 "robust_holt_winters")
+                                 "robust_holt_winters", "robust_prophet")
+
+
+def _robust_prophet(hist, T, H, k, iters):
+    """``prophet``'s design fitted by Huber-reweighted least squares at ``k``
+    MAD sigmas of the residuals over ``iters`` passes, missing samples weighted
+    zero (K36, ``ops.lsq.prophet_fit_robust``) -> (forecast [R, H], MAD sigma
+    [R], finite count [R]).  A row with fewer finite samples than twice the
+    design's rank gets ``robust_moving_average_all``'s constant forecast.
+    Refitted on every call: no model cache."""
+    fit = LQ.prophet_fit_robust(hist, T, H, k=k, iters=iters)
+    return fit.forecast, fit.sigma, fit.nfin
 
 
 def _robust_holt_winters(hist, T, H, period, k):
@@ -653,7 +678,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
              scale_floor: float = 0.1, shift_threshold: float = 4.0, min_blocks: int = 2, holdout: int = 0,
              candidates=None, zcap: float = 8.0, margin: float = 0.05,
              auto: AutoContext | None = None, trend_block: int | None = None,
-             tail_z: float = 2.0, hw_k: float = 3.0) -> tuple[torch.Tensor, torch.Tensor]:
+             tail_z: float = 2.0, hw_k: float = 3.0, prophet_k: float = 3.0,
+             prophet_iters: int = 5) -> tuple[torch.Tensor, torch.Tensor]:
     """H-step forecast past the end of the history for every row with a
     forecasting model -> (forecast [R, H], residual sigma [R]; sigma [R, H],
     one per step, from ``seasonal_scale_robust`` unless it fell back; a pair
@@ -676,6 +702,8 @@ def forecast(algorithm: str, hist: torch.Tensor, T: int, H: int, period: int | N
         return fit.forecast, fit.sigma
     if algo == "robust_holt_winters":
         return _robust_holt_winters(hist, T, H, period, hw_k)[:2]      # (a CacheContext is ignored: refitted)
+    if algo == "robust_prophet":
+        return _robust_prophet(hist, T, H, prophet_k, prophet_iters)[:2]  # (a CacheContext is ignored: refitted)
     if algo == "prophet":
         fit = LQ.prophet_fit(hist, T, H)
         return fit.forecast, fit.sigma

@@ -194,6 +194,9 @@ _SIGS: dict[str, list] = {
     "fm_lsq_project": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p,
                        c_void_p],
     "fm_lsq_residual": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p],
+    # K36: Y ld_y T R XT ld_x p k iters rows Z shift sigma nfin wsum fallback stream
+    "fm_lsq_robust_fit": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_float, c_int, c_int] + [c_void_p] * 7,
+    "fm_lsq_robust_supported": [c_int],
     "fm_stream_read": [c_void_p, c_i64, c_void_p, c_int, c_void_p],
     "fm_lstm_forward": [c_void_p, c_i64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                         c_void_p],

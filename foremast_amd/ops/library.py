@@ -346,5 +346,24 @@ def _(Y, T, H, step_s):
     return Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,))
 
 
+# --------------------------------------------------------------------------- K36
+@custom_op(f"{NS}::prophet_fit_robust", mutates_args=())
+def prophet_fit_robust(Y: torch.Tensor, T: int, H: int, step_s: float, k: float,
+                       iters: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                            torch.Tensor]:
+    """Huber-reweighted prophet fit, missing samples weighted zero: (beta [R,32],
+    forecast [R,H], MAD sigma [R], finite count [R] int32, weight sum [R],
+    fallback [R] bool)."""
+    f = LQ.prophet_fit_robust(Y, T, H, step_s, k, iters)
+    return (f.beta.clone(), f.forecast.clone(), f.sigma.clone(), f.nfin.clone(), f.wsum.clone(), f.fallback.clone())
+
+
+@register_fake(f"{NS}::prophet_fit_robust")
+def _(Y, T, H, step_s, k, iters):
+    R = Y.shape[0]
+    return (Y.new_empty((R, LQ.F)), Y.new_empty((R, H)), Y.new_empty((R,)), Y.new_empty((R,), dtype=torch.int32),
+            Y.new_empty((R,)), Y.new_empty((R,), dtype=torch.bool))
+
+
 OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "es_fit_robust", "fft_seasonal", "lstm_stack",
-       "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit")
+       "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit", "prophet_fit_robust")
