@@ -35,6 +35,7 @@
 // LDS per workgroup: the shared block below (bins, 4 tiles a row, G, partials)
 // and ROWS rows of keys rounded up to whole 64-sample chunks; at T = 10,080
 // and ROWS = 1 that is 70 KB, so two workgroups share a CU's 160 KB.
+#include "fm_chol_regs.h"
 #include "fm_common.h"
 #include "fm_radix_select.h"
 
@@ -68,11 +69,6 @@ constexpr size_t lds_bytes(int T) {
   return sizeof(RobustShared<ROWS>) + (size_t)ROWS * padded(T) * sizeof(unsigned);
 }
 
-__device__ __forceinline__ double bcast_f64(double v, int lane) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), lane),
-                          __builtin_amdgcn_readlane(__double2loint(v), lane));
-}
-
 // Huber weight of the sample with key `key` at threshold ks = k s (+inf: plain
 // least squares); r = the residual, 0 for a missing sample, whose weight is 0.
 __device__ __forceinline__ float huber_weight(unsigned key, float ks, float& r) {
@@ -99,24 +95,9 @@ __device__ __forceinline__ void solve_row(const float* G, const float (*gpart)[k
   for (int w = 0; w < kWaves; ++w) g += gpart[w][j];
   const double zj = z[j];
   a[kF] = j < p ? (double)g : 0.0;
-  // Cholesky, right-looking.  Step k: lane k scales its column to L[:, k] and
-  // keeps 1 / L[k][k] in a[k]; lane j > k subtracts L[i][k] L[j][k] from all of
-  // its column (the full symmetric matrix is carried, so L[j][k] is its own
-  // a[k]).  The augmented row turns into y = L^-1 g.
-#pragma unroll
-  for (int k = 0; k < kF; ++k) {
-    const double pk = bcast_f64(a[k], k);
-    const double inv = pk > 0.0 ? 1.0 / sqrt(pk) : 0.0;
-    const double cj = j > k ? a[k] * inv : 0.0;
-    const double scl = j == k ? inv : 1.0;
-    a[k] = j == k ? inv : a[k];
-#pragma unroll
-    for (int i = k + 1; i <= kF; ++i) {
-      a[i] *= scl;
-      const double ci = bcast_f64(a[i], k);
-      a[i] = fma(-ci, cj, a[i]);
-    }
-  }
+  // right-looking Cholesky (fm_chol_regs.h): a[i] = L[i][j] below the diagonal,
+  // a[j] = 1 / L[j][j], and the augmented row turns into y = L^-1 g
+  chol_columns<kF, kF + 1>(a, j);
   // L^T x = y: lane m finishes x_m, the lanes below it take L[m][j] x_m off
   double acc = a[kF], x = 0.0;
 #pragma unroll

@@ -109,6 +109,9 @@ class BrainConfig:
     # ML_MULTIVARIATE_REJECT: robust_multivariate sets aside the history columns where a member lies more than
     # this many of its MAD-sigmas from its median (<= 0: nothing is rejected, the model is multivariate_normal)
     multivariate_reject: float = 3.5
+    # ML_MVN_MAX_MEMBERS: the joint detectors judge a job's metrics in groups of at most this many (8 to 32);
+    # above 8 a job of 9 to 32 metrics is one group on the wide tier (K37) instead of chunks of 8
+    mvn_max_members: int = 8
     # seasonal_robust: period in samples (0 = one day at the brain's step, < 0 = detect from the history)
     # and the half width of the profile's smoothing window in phases
     seasonal_period: int = 0                 # SEASONAL_PERIOD
@@ -292,6 +295,7 @@ class BrainConfig:
         if env.get("ML_MULTIVARIATE_THRESHOLD", "") != "":
             c.multivariate_threshold = _f(env, "ML_MULTIVARIATE_THRESHOLD", c.threshold)
         c.multivariate_reject = _f(env, "ML_MULTIVARIATE_REJECT", c.multivariate_reject)
+        c.mvn_max_members = min(32, max(8, _i(env, "ML_MVN_MAX_MEMBERS", c.mvn_max_members)))
         c.seasonal_period = _i(env, "SEASONAL_PERIOD", c.seasonal_period)
         c.seasonal_smooth = _i(env, "SEASONAL_SMOOTH", c.seasonal_smooth)
         c.seasonal_scale_smooth = _i(env, "SEASONAL_SCALE_SMOOTH", c.seasonal_scale_smooth)

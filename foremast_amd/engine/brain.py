@@ -318,7 +318,7 @@ class Brain(BrainStateMixin):
             dec = zoo.decide(algo, hist, T, cur, hor, R, tables, diff,
                              lstm_model=self._lstm_for(rows) if algo == "lstm" else self.lstm_model,
                              pairs=pairs, cache=self._cache_ctx(rows, algo),
-                             groups=self._groups(rows) if algo in zoo.MVN_MODELS else None,
+                             groups=self._groups(rows, self.cfg.mvn_max_members) if algo in zoo.MVN_MODELS else None,
                              mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
                              auto=auto, **self._model_args(algo))
             for i, nm in enumerate(self.auto_note(auto)):
@@ -338,7 +338,7 @@ class Brain(BrainStateMixin):
                                  None if diff is None else diff.index_select(0, it),
                                  lstm_model=self._lstm_for(sub) if algo == "lstm" else self.lstm_model,
                                  pairs=pairs, cache=self._cache_ctx(sub, algo),
-                                 groups=self._groups(sub) if algo in zoo.MVN_MODELS else None,
+                                 groups=self._groups(sub, self.cfg.mvn_max_members) if algo in zoo.MVN_MODELS else None,
                                  mvn_threshold=self.cfg.mvn_threshold(), mvn_reject=self.cfg.multivariate_reject,
                                  auto=auto, **self._model_args(algo))
                 for i, nm in zip(idx, self.auto_note(auto)):
@@ -531,12 +531,13 @@ class Brain(BrainStateMixin):
         return f(ia), f(ib), f(singles)
 
     @staticmethod
-    def _groups(rows: list[Row]):
-        """Joint-detector groups: the rows of each job, in chunks of 8."""
+    def _groups(rows: list[Row], max_k: int = 8):
+        """Joint-detector groups: the rows of each job, in chunks of ``max_k``
+        (``BrainConfig.mvn_max_members``)."""
         by_job: dict[int, list[int]] = {}
         for i, r in enumerate(rows):
             by_job.setdefault(r.job, []).append(i)
-        return zoo.mvn_groups(by_job.values())
+        return zoo.mvn_groups(by_job.values(), max_k)
 
     @staticmethod
     def _joint_groups(rows: list[Row]):

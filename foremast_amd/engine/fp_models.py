@@ -353,7 +353,8 @@ class ModelsMixin:
                     lo_col = zoo.shift_start(sub.T)
                 dec = zoo.decide(algo, lazy.materialize(lo_col), sub.T, cur, sub.hor, sub.M, sub.tables, dsub,
                                  mvn_threshold=cfg.mvn_threshold(), mvn_reject=cfg.multivariate_reject,
-                                 **b._shift_args(algo), **b._quantile_args(algo))
+                                 mvn_max_members=cfg.mvn_max_members, **b._shift_args(algo),
+                                 **b._quantile_args(algo))
             else:
                 H = sub.H
                 if hpa_algo == algo:

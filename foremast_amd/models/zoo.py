@@ -21,8 +21,9 @@ robust_prophet                  the same design, Huber IRLS at k sigma, K36 (f32
                                 missing samples weighted zero
 lstm                            LSTM forecaster (bf16 MFMA)             K6 + band decide
 bivariate_normal                Mahalanobis over metric pairs           K5
-multivariate_normal             joint Mahalanobis over all metrics      K12
-robust_multivariate             the same, past incident columns aside   K13 + K17
+multivariate_normal             joint Mahalanobis over all metrics      K12 (groups of <= 8), K37
+                                                                        (9 to 32 members)
+robust_multivariate             the same, past incident columns aside   K13 + K17, K13 + K37
 robust_moving_average_all       median / MAD over the whole history     K13 + band decide
 robust_moving_average           median / MAD over the last ``window``   K13 (view) + band
 seasonal_robust                 per-phase median profile + residual MAD K14 + band decide
@@ -46,7 +47,9 @@ by ``pairwise_threshold_factor`` on rows whose canary distribution differs.
 ``multivariate_normal`` takes one joint threshold (``mvn_threshold``), turned
 into a cut on the Mahalanobis distance per number of live members;
 ``robust_multivariate`` shares it and sets aside the history columns where a
-member lies more than ``mvn_reject`` MAD-sigmas from its median.
+member lies more than ``mvn_reject`` MAD-sigmas from its median.  A job's
+metrics are judged in groups of at most ``mvn_max_members`` (8 to 32,
+``BrainConfig.mvn_max_members``); groups of more than 8 take the wide tier.
 """
 from __future__ import annotations
 
@@ -169,7 +172,7 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
            mvn_reject: float = 3.5, scale_smooth: int = 30, scale_floor: float = 0.1, holdout: int = 0,
            candidates=None, zcap: float = 8.0, margin: float = 0.05, auto: "AutoContext | None" = None,
            trend_block: int | None = None, tail_z: float = 2.0, hw_k: float = 3.0, prophet_k: float = 3.0,
-           prophet_iters: int = 5) -> RowDecision:
+           prophet_iters: int = 5, mvn_max_members: int = 8) -> RowDecision:
     """Score current points of every row.
 
     ``horizon`` [R, n] int64: steps past the end of the history of each current
@@ -181,7 +184,9 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     too and fits a slope from ``trend_min_blocks`` non-empty ones, and
     ``seasonal_trend_robust`` from as many non-empty cycles of ``period``.
     ``mvn_reject`` is ``robust_multivariate``'s rejection limit in MAD-sigmas
-    (<= 0: nothing is rejected).  ``scale_smooth`` and ``scale_floor`` are
+    (<= 0: nothing is rejected) and ``mvn_max_members`` the largest group the
+    joint detectors cut a service's M rows into when ``groups`` is not given
+    (:func:`mvn_groups`).  ``scale_smooth`` and ``scale_floor`` are
     ``seasonal_scale_robust``'s: the half width of the window that smooths
     its per-phase scale, and that scale's floor as a share of the pooled MAD.
     ``holdout``, ``candidates``, ``zcap`` and ``margin`` are ``auto_robust``'s
@@ -219,9 +224,10 @@ def decide(algorithm: str, hist: torch.Tensor, T: int, cur: torch.Tensor, horizo
     if algo == "bivariate_normal":
         return _bivariate(hist, T, cur, M, tables, pairs)
     if algo == "multivariate_normal":
-        return _multivariate(hist, T, cur, M, tables, diff, groups, mvn_threshold)
+        return _multivariate(hist, T, cur, M, tables, diff, groups, mvn_threshold, max_k=mvn_max_members)
     if algo == "robust_multivariate":
-        return _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups, mvn_threshold, mvn_reject)
+        return _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups, mvn_threshold, mvn_reject,
+                                    mvn_max_members)
     if H is None:
         H = int(horizon.max().item()) if horizon.numel() else 1
     H = max(int(H), 1)
@@ -805,44 +811,54 @@ def _bivariate(hist, T, cur, M, tables, pairs=None) -> RowDecision:
 
 
 MVN_MAX_K = 8
+MVN_WIDE_MAX_K = 32
 
 
-def mvn_groups(jobs) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def mvn_groups(jobs, max_k: int = MVN_MAX_K) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Row groups of the joint detector; ``jobs`` holds each job's row indices.
-    A job's rows are cut into chunks of 8 in row order; a leftover of one row
-    (and a job with one metric) is a single.  Returns (rows [G, 8] int32, -1
-    padded; K [G] int64; singles int64)."""
+    A job's rows are cut into chunks of ``max_k`` (8 to 32) in row order; a
+    leftover of one row (and a job with one metric) is a single.  Returns
+    (rows [G, W] int32, -1 padded; K [G] int64; singles int64) with W = 8, or
+    32 when ``max_k > 8`` (the wide tier, K37)."""
+    max_k = int(max_k)
+    if not MVN_MAX_K <= max_k <= MVN_WIDE_MAX_K:
+        raise ValueError(f"max_k must be in [{MVN_MAX_K}, {MVN_WIDE_MAX_K}]")
+    W = MVN_MAX_K if max_k == MVN_MAX_K else MVN_WIDE_MAX_K
     rows, ks, singles = [], [], []
     for idx in jobs:
-        for c0 in range(0, len(idx), MVN_MAX_K):
-            part = list(idx[c0:c0 + MVN_MAX_K])
+        for c0 in range(0, len(idx), max_k):
+            part = list(idx[c0:c0 + max_k])
             if len(part) == 1:
                 singles.append(part[0])
             else:
-                rows.append(part + [-1] * (MVN_MAX_K - len(part)))
+                rows.append(part + [-1] * (W - len(part)))
                 ks.append(len(part))
-    return (torch.tensor(rows, dtype=torch.int32).reshape(-1, MVN_MAX_K), torch.tensor(ks, dtype=torch.int64),
+    return (torch.tensor(rows, dtype=torch.int32).reshape(-1, W), torch.tensor(ks, dtype=torch.int64),
             torch.tensor(singles, dtype=torch.int64))
 
 
 MVN_MODELS = ("multivariate_normal", "robust_multivariate")
 
 
-def _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups=None, thr=None, reject=3.5) -> RowDecision:
+def _multivariate_robust(hist, T, cur, horizon, M, tables, diff, groups=None, thr=None, reject=3.5,
+                         max_k=MVN_MAX_K) -> RowDecision:
     """``_multivariate`` with the moments taken past the incident columns of
     the history (K13 + K17, ``ops/misc.py:ref_mvn_robust``): a complete
     column where any member lies more than ``reject`` of its MAD-sigmas from
     its median is set aside, unless that would set aside more than half.
     Singles go through ``robust_moving_average_all``."""
-    return _multivariate(hist, T, cur, M, tables, diff, groups, thr, reject=float(reject), horizon=horizon)
+    return _multivariate(hist, T, cur, M, tables, diff, groups, thr, reject=float(reject), horizon=horizon,
+                         max_k=max_k)
 
 
-def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=None, horizon=None) -> RowDecision:
-    """All metrics of a job scored jointly (K12): every member row of a group
+def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=None, horizon=None,
+                  max_k=MVN_MAX_K) -> RowDecision:
+    """All metrics of a job scored jointly (K12; K37 for the groups of more
+    than 8): every member row of a group
     gets the group's decision, bounds in Mahalanobis units (upper = the cut
-    the group used, lower = 0).  ``groups`` = (rows [G, 8] int32, K [G],
+    the group used, lower = 0).  ``groups`` = (rows [G, 8 or 32] int32, K [G],
     singles) as :func:`mvn_groups` makes them; default: each service's M
-    consecutive rows.  Singles go through ``moving_average_all``.  ``thr`` is
+    consecutive rows in chunks of ``max_k``.  Singles go through ``moving_average_all``.  ``thr`` is
     the joint threshold in sigma units (default: the largest of the table);
     a group is judged at ``thr * pair_factor`` when any member's canary
     distribution differs.  ``reject`` not None: the robust model (K17) with
@@ -852,7 +868,7 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=N
     R, n = cur.shape
     device = hist.device
     if groups is None:
-        groups = mvn_groups([range(s * M, (s + 1) * M) for s in range(R // M)])
+        groups = mvn_groups([range(s * M, (s + 1) * M) for s in range(R // M)], max_k)
     grows, gk, singles = (g.to(device) for g in groups)
     NW = max(1, (n + 63) // 64)
     flags_all = torch.zeros((R, NW), dtype=torch.int64, device=device)
@@ -868,7 +884,10 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=N
         if thr is None:
             thr = float(tables.thr[0].item()) if tables.thr.numel() == 1 else float(tables.thr.max().item())
         cuts = MI.mvn_cuts(thr, tables.pair_factor)
-        cuts_d = torch.from_numpy(cuts).to(device)
+        wide = grows.shape[1] > MVN_MAX_K
+        # (the wide table's first nine columns are the narrow table)
+        wcuts = MI.mvn_cuts(thr, tables.pair_factor, MVN_WIDE_MAX_K) if wide else cuts
+        cuts_d = torch.from_numpy(wcuts).to(device)
         member = grows >= 0
         safe = grows.clamp(min=0).long()
         if diff is None:
@@ -877,11 +896,20 @@ def _multivariate(hist, T, cur, M, tables, diff, groups=None, thr=None, reject=N
             lowered = ((diff.to(device)[safe] != 0) & member).any(1).to(torch.uint8)
         for K in sorted(set(gk.tolist())):
             sel = (gk == K).nonzero().squeeze(1)
-            if reject is None:
-                params, dist, flags, cnt, gvalid = MI.mvn(hist, T, cur, grows[sel].contiguous(), K, cuts,
-                                                          lowered[sel], tables.min_hist)
+            if K > MVN_MAX_K:                                 # the wide tier (K37)
+                if reject is None:
+                    params, dist, flags, cnt, gvalid = MI.mvn_wide(hist, T, cur, grows[sel].contiguous(), K, wcuts,
+                                                                   lowered[sel], tables.min_hist)
+                else:
+                    params, dist, flags, cnt, gvalid, _ = MI.mvn_wide_robust(hist, T, cur, grows[sel].contiguous(), K,
+                                                                             wcuts, lowered[sel], tables.min_hist,
+                                                                             reject)
+            elif reject is None:
+                params, dist, flags, cnt, gvalid = MI.mvn(hist, T, cur, grows[sel][:, :MVN_MAX_K].contiguous(), K,
+                                                          cuts, lowered[sel], tables.min_hist)
             else:
-                params, dist, flags, cnt, gvalid, _ = MI.mvn_robust(hist, T, cur, grows[sel].contiguous(), K, cuts,
+                params, dist, flags, cnt, gvalid, _ = MI.mvn_robust(hist, T, cur,
+                                                                    grows[sel][:, :MVN_MAX_K].contiguous(), K, cuts,
                                                                     lowered[sel], tables.min_hist, reject)
             sc = torch.nan_to_num(dist, nan=0.0).amax(1)
             used = cuts_d[lowered[sel].long(), params[:, 1].long()]

@@ -120,6 +120,16 @@ _SIGS: dict[str, list] = {
     "fm_mvn_robust": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p,
                       c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                       c_void_p],
+    # K37: fm_mvn's arguments without form, rows [G, 32], cuts [2, 33]
+    "fm_mvn_wide": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p,
+                    c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # fm_mvn_wide with a flush interval after min_n (the benchmark's)
+    "fm_mvn_wide_flush": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p,
+                          c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    # K37: fm_mvn_robust's arguments, rows [G, 32], cuts [2, 33]
+    "fm_mvn_wide_robust": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_i64, c_int, c_void_p, c_i64, c_int, c_void_p,
+                           c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                           c_void_p, c_void_p, c_void_p],
     # hist ld T R out stream
     "fm_robust_stats": [c_void_p, c_i64, c_int, c_i64, c_void_p, c_void_p],
     # hist ld T R out rowmap cache valid expect_miss blocks stream

@@ -365,5 +365,25 @@ def _(Y, T, H, step_s, k, iters):
             Y.new_empty((R,)), Y.new_empty((R,), dtype=torch.bool))
 
 
+# --------------------------------------------------------------------------- K37
+@custom_op(f"{NS}::mvn_wide", mutates_args=())
+def mvn_wide(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, lowered: torch.Tensor,
+             threshold: float, pair_factor: float,
+             min_n: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Joint multivariate-normal detector over groups of 9 to 32 member rows
+    ``rows`` [G, 32] int32 (-1 padded): (params [G, 2 + K + K(K+1)/2], dist
+    [G, n], flags [G, NW] int64, count [G] int32, valid [G] int32)."""
+    cuts = MI.mvn_cuts(threshold, pair_factor, MI.MVN_WIDE_MAX_K)
+    return tuple(t.clone() for t in MI.mvn_wide(hist, T, cur, rows, K, cuts, lowered, min_n))
+
+
+@register_fake(f"{NS}::mvn_wide")
+def _(hist, T, cur, rows, K, lowered, threshold, pair_factor, min_n):
+    G, n = rows.shape[0], cur.shape[1]
+    return (cur.new_empty((G, 2 + K + K * (K + 1) // 2)), cur.new_empty((G, n)),
+            cur.new_empty((G, max(1, (n + 63) // 64)), dtype=torch.int64), cur.new_empty((G,), dtype=torch.int32),
+            cur.new_empty((G,), dtype=torch.int32))
+
+
 OPS = ("pairwise_tests", "pairwise_effect", "pairwise_pods", "pairwise_joint", "pairwise_drift", "pairwise_tail", "pairwise_dependence", "stats_decide", "service_reduce", "es_fit", "es_fit_robust", "fft_seasonal", "lstm_stack",
-       "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit", "prophet_fit_robust")
+       "downstream_impact", "rolling_stats", "rolling_robust_stats", "prophet_fit", "prophet_fit_robust", "mvn_wide")

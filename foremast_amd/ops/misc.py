@@ -1,4 +1,5 @@
-"""K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K13 robust (median / MAD) statistics,
+"""K5 bivariate normal, K12 multivariate normal, K17 robust multivariate, K37 their wide tier
+(csrc/kernels/mvn_wide.hip), K13 robust (median / MAD) statistics,
 K14 seasonal robust model, K15 level-shift robust model, K16 trend robust model, K22 seasonal scale robust
 model, K23 hold-out score, K24 quantile robust statistics (csrc/kernels/quantile_robust.hip), K26 seasonal
 quantile robust model (csrc/kernels/seasonal_quantile_robust.hip), K8 HPA score,
@@ -92,17 +93,18 @@ MVN_RIDGE = 1e-6
 MVN_FORM = 1
 
 
-def mvn_cuts(thr: float, factor: float = 1.0) -> np.ndarray:
-    """Flag cuts of the joint detector, [2, 9] fp32: row 0 for ``thr``, row 1
+def mvn_cuts(thr: float, factor: float = 1.0, max_k: int = MVN_MAX_K) -> np.ndarray:
+    """Flag cuts of the joint detector, [2, max_k + 1] fp32 ([2, 9] for the
+    narrow tier, [2, 33] for K37's): row 0 for ``thr``, row 1
     for ``thr * factor`` (groups with a differing canary), column k for k
     live members.  The threshold stays in sigma units: the cut is the
     Mahalanobis distance whose chi-square(k) upper tail equals the two-sided
     normal tail of ``thr``, so ``cut(thr, 1) == thr``; column 0 is 0."""
     from scipy.special import chdtri, erfc
-    out = np.zeros((2, MVN_MAX_K + 1), np.float64)
+    out = np.zeros((2, int(max_k) + 1), np.float64)
     for r, t in enumerate((float(thr), float(thr) * float(factor))):
         p = erfc(t / np.sqrt(2.0))
-        out[r, 1:] = np.sqrt(chdtri(np.arange(1, MVN_MAX_K + 1), p))
+        out[r, 1:] = np.sqrt(chdtri(np.arange(1, int(max_k) + 1), p))
         out[r, 1] = t
     return out.astype(np.float32)
 
@@ -171,17 +173,17 @@ def ref_mvn(hist, cur, rows, K: int, cuts, lowered, min_n: int):
     return params, dist, _pack_words(flag), flag.sum(1).astype(np.int32), valid
 
 
-def _mvn_args(hist, T, cur, rows, K, cuts, lowered) -> np.ndarray:
+def _mvn_args(hist, T, cur, rows, K, cuts, lowered, min_k: int = 2, max_k: int = MVN_MAX_K) -> np.ndarray:
     """The argument checks of the joint detectors' wrappers (nothing is
-    launched when one fails) -> ``cuts`` as fp32 [2, 9]."""
-    check(2 <= int(K) <= MVN_MAX_K, f"group size must be in [2, {MVN_MAX_K}]")
-    check(rows.dim() == 2 and rows.shape[1] == MVN_MAX_K and rows.dtype == torch.int32, "rows must be int32 [G, 8]")
+    launched when one fails) -> ``cuts`` as fp32 [2, max_k + 1]."""
+    check(min_k <= int(K) <= max_k, f"group size must be in [{min_k}, {max_k}]")
+    check(rows.dim() == 2 and rows.shape[1] == max_k and rows.dtype == torch.int32, f"rows must be int32 [G, {max_k}]")
     check(hist.dtype == torch.float32 and cur.dtype == torch.float32 and hist.shape[0] == cur.shape[0]
           and 0 < T <= hist.shape[1], "hist / cur must be fp32 with the same rows")
     G = rows.shape[0]
     check(lowered.numel() == G and lowered.dtype == torch.uint8, "lowered must be uint8 [G]")
     cuts = np.asarray(cuts, np.float32)
-    check(cuts.shape == (2, MVN_MAX_K + 1), "cuts must be [2, 9]")
+    check(cuts.shape == (2, max_k + 1), f"cuts must be [2, {max_k + 1}]")
     if G:
         used = rows[:, :K]
         check(int(used.min().item()) >= 0 and int(used.max().item()) < hist.shape[0], "row ids out of range")
@@ -228,7 +230,8 @@ def mvn(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: in
 MVN_REJECT = 3.5
 
 
-def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: float = MVN_REJECT):
+def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: float = MVN_REJECT,
+                   width: int = MVN_MAX_K):
     """Oracle of the robust joint detector: :func:`ref_mvn` over the history
     columns that are not incident columns -> its five arrays and ``rejected``
     [G] int32, the columns set aside.
@@ -245,7 +248,8 @@ def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: f
     through :func:`ref_mvn` itself, so N, the ``valid`` gate ``N >=
     max(min_n, K + 2)`` and everything after are taken over the columns kept,
     and with nothing rejected the result is :func:`ref_mvn`'s.  No
-    consistency correction is applied for the trimmed tails."""
+    consistency correction is applied for the trimmed tails.  ``width`` is
+    the width of the row table (32 for the wide tier)."""
     hist = np.asarray(hist, np.float32)
     cur = np.asarray(cur, np.float32)
     rows = np.asarray(rows)
@@ -261,7 +265,7 @@ def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: f
     c[members], s, _ = ref_robust_stats(hist[members], T)
     if rj > 0 and np.isfinite(rj):
         lim[members] = rj * s
-    own = np.full((1, MVN_MAX_K), -1, np.int32)
+    own = np.full((1, int(width)), -1, np.int32)
     own[0, :K] = np.arange(K)
     parts = []
     for g in range(G):
@@ -275,6 +279,22 @@ def ref_mvn_robust(hist, cur, rows, K: int, cuts, lowered, min_n: int, reject: f
             h[:, out] = np.nan
         parts.append(ref_mvn(h, cur[r], own, K, cuts, lowered[g:g + 1], min_n))
     return tuple(np.concatenate([p[i] for p in parts]) for i in range(5)) + (rejected,)
+
+
+def _member_stats(hist, T, rows, K) -> torch.Tensor:
+    """[R, 3] median / MAD statistics (``fm_robust_stats``) of the groups'
+    member rows of a GPU buffer; the other rows are left unwritten."""
+    R, G, d = hist.shape[0], rows.shape[0], hist.device
+    stats = torch.empty((R, 3), dtype=torch.float32, device=d)
+    if 2 * G * int(K) >= R:
+        LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), int(T), R, ptr(stats), stream_of(hist))
+    else:
+        ids = torch.unique(rows[:, :K]).long()
+        sub = hist.index_select(0, ids)
+        part = torch.empty((ids.numel(), 3), dtype=torch.float32, device=d)
+        LIB.call("fm_robust_stats", ptr(sub), sub.stride(0), int(T), ids.numel(), ptr(part), stream_of(hist))
+        stats[ids] = part
+    return stats
 
 
 def mvn_robust(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts,
@@ -298,20 +318,65 @@ def mvn_robust(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor
         return out + (rejected,)
     params, dist, flags, cnt, valid = out
     R = hist.shape[0]
-    stats = torch.empty((R, 3), dtype=torch.float32, device=d)
-    if 2 * G * int(K) >= R:
-        LIB.call("fm_robust_stats", ptr(hist), hist.stride(0), int(T), R, ptr(stats), stream_of(hist))
-    else:
-        ids = torch.unique(rows[:, :K]).long()
-        sub = hist.index_select(0, ids)
-        part = torch.empty((ids.numel(), 3), dtype=torch.float32, device=d)
-        LIB.call("fm_robust_stats", ptr(sub), sub.stride(0), int(T), ids.numel(), ptr(part), stream_of(hist))
-        stats[ids] = part
+    stats = _member_stats(hist, T, rows, K)
     ct = torch.from_numpy(cuts).to(d)
     rows = rows.contiguous()
     LIB.call("fm_mvn_robust", ptr(hist), hist.stride(0), int(T), R, ptr(cur), cur.stride(0), n, ptr(rows), G, int(K),
              ptr(ct), ptr(lowered.contiguous()), int(min_n), ptr(stats), float(reject), ptr(params), ptr(dist),
              ptr(flags), flags.shape[1], ptr(cnt), ptr(valid), ptr(rejected), stream_of(hist))
+    return params, dist, flags, cnt, valid, rejected
+
+
+# --------------------------------------------------------------------------- K37
+MVN_WIDE_MAX_K = 32
+
+
+def mvn_wide(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts, lowered: torch.Tensor,
+             min_n: int):
+    """:func:`mvn` for groups of ``9 <= K <= 32`` member rows (K37,
+    csrc/kernels/mvn_wide.hip: the Gram matrix on MFMA): ``rows`` [G, 32]
+    int32, ``cuts`` [2, 33] from ``mvn_cuts(..., max_k=32)``.  Returns what
+    :func:`ref_mvn` returns, which is also the CPU path."""
+    cuts = _mvn_args(hist, T, cur, rows, K, cuts, lowered, MVN_MAX_K + 1, MVN_WIDE_MAX_K)
+    G, n = rows.shape[0], cur.shape[1]
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_mvn(hist.numpy()[:, :T], cur.numpy(), rows.numpy(), K, cuts,
+                                                          lowered.numpy(), min_n))
+    require_native(hist)
+    params, dist, flags, cnt, valid = _mvn_outputs(G, n, K, hist.device)
+    if G == 0 or n == 0:
+        return params, dist, flags, cnt, valid
+    ct = torch.from_numpy(cuts).to(hist.device)
+    rows = rows.contiguous()
+    LIB.call("fm_mvn_wide", ptr(hist), hist.stride(0), int(T), hist.shape[0], ptr(cur), cur.stride(0), n, ptr(rows), G,
+             int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), ptr(params), ptr(dist), ptr(flags),
+             flags.shape[1], ptr(cnt), ptr(valid), stream_of(hist))
+    return params, dist, flags, cnt, valid
+
+
+def mvn_wide_robust(hist: torch.Tensor, T: int, cur: torch.Tensor, rows: torch.Tensor, K: int, cuts,
+                    lowered: torch.Tensor, min_n: int, reject: float = MVN_REJECT):
+    """:func:`mvn_robust` for groups of ``9 <= K <= 32`` member rows (K13 +
+    K37): :func:`mvn_wide`'s arguments and ``reject``; returns what
+    :func:`ref_mvn_robust` returns, which is also the CPU path."""
+    cuts = _mvn_args(hist, T, cur, rows, K, cuts, lowered, MVN_MAX_K + 1, MVN_WIDE_MAX_K)
+    G, n = rows.shape[0], cur.shape[1]
+    if not hist.is_cuda:
+        return tuple(torch.from_numpy(a) for a in ref_mvn_robust(hist.numpy()[:, :T], cur.numpy(), rows.numpy(), K,
+                                                                 cuts, lowered.numpy(), min_n, reject,
+                                                                 MVN_WIDE_MAX_K))
+    require_native(hist)
+    d = hist.device
+    params, dist, flags, cnt, valid = _mvn_outputs(G, n, K, d)
+    rejected = torch.zeros((G,), dtype=torch.int32, device=d)
+    if G == 0 or n == 0:
+        return params, dist, flags, cnt, valid, rejected
+    stats = _member_stats(hist, T, rows, K)
+    ct = torch.from_numpy(cuts).to(d)
+    rows = rows.contiguous()
+    LIB.call("fm_mvn_wide_robust", ptr(hist), hist.stride(0), int(T), hist.shape[0], ptr(cur), cur.stride(0), n,
+             ptr(rows), G, int(K), ptr(ct), ptr(lowered.contiguous()), int(min_n), ptr(stats), float(reject),
+             ptr(params), ptr(dist), ptr(flags), flags.shape[1], ptr(cnt), ptr(valid), ptr(rejected), stream_of(hist))
     return params, dist, flags, cnt, valid, rejected
 
 
